@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """bench.py — decoded frames/s of the DiffCodec decode hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--frames F] [--config c2|c4] [--no-graphs]
+    python bench.py --gpus N --steps K --warmup W [--frames F] [--config c2|c4] [--no-graphs] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the outputs of the last timed step if --dump-outputs is given, and
+prints the JSON line.  Everything else it can measure runs only with --full, after the timed region: the C3 strong-scaling
+clip, the single-frame and GOP-12 batches, the U-Net forward, the VAE encode, the validation configuration, the in-situ roofline,
+the CPU baseline and the multi-rank uint8 gather; their keys in the line are null without --full.
+--dump-outputs DIR writes what the timed path returned in its last step (`decode_units`: fp32 [units, 3, 512, 512] in [0,1],
+rank 0's units) as DIR/decoded_units.npy; inputs and weights are seeded, so equal arguments give equal inputs on every run.
 
 A "step" is one pass of the hot path over one batch of F synthetic inter frames resident in HBM, driven exactly as a clip is
 decoded (`clip_decode`): GOP-12 clip -> decode units -> round-robin shard over the ranks -> one batched `pipe(...)` call per
@@ -11,13 +18,14 @@ checkpoint is reachable offline), bf16 compute with fp32 accumulation.
   --config c2 (default)  BASELINE configs[1]: 512x512 frames, one DualFlowControlNet (the configuration `metric` is quoted on)
   --config c4            BASELINE configs[3]: 960x512 frames = two 512x512 windows each, GOP-4, DualFlowControlNet +
                          ResControlNet (warp_cond); frames/s counts whole 960x512 frames
-  (the line also carries `validation_config`: what validation.py:37,106,132-146 runs — UniPC multistep, 40 steps, FreeU, CFG,
-   a string prompt through the text tower — timed after the headline region)
+  (with --full the line also carries `validation_config`: what validation.py:37,106,132-146 runs — UniPC multistep, 40 steps,
+   FreeU, CFG, a string prompt through the text tower — timed after the headline region)
 N > 1: one process per GPU (torch.distributed / RCCL); units are sharded across ranks with no data-path collective; rank 0
 synthesises the weights and broadcasts the packed tensors once (outside the timed region).  Prints ONE JSON line on rank 0.
 `python bench.py --gpus N` with no launcher around it starts its own N ranks (child processes, before this process makes any
 GPU call); under `torch.distributed.run` (WORLD_SIZE set) it is one of the ranks.  The timed step is the decode of this rank's
-units only — decoded frames stay on the rank that decoded them; the optional uint8 gather is timed separately (`gather_ms`).
+units only — decoded frames stay on the rank that decoded them; the optional uint8 gather (--full) is timed separately
+(`gather_ms`).
 """
 import argparse
 import json
@@ -36,6 +44,7 @@ SIZE = 512
 TFLOP_PER_FRAME = (20 * 2 * (803.3 + 268.6) + 30.2 + 19.9 + 2514.5) / 1000.0
 PEAK_BF16_TFLOPS = 2500.0      # dense bf16 MFMA peak, /opt/skills/guides/MI355X_MICROARCH.md
 PEAK_HBM_GBS = 8000.0          # HBM3E spec (≈6300 achievable), same guide
+DUMP_BYTES = 64_000_000        # --dump-outputs writes at most this much in all
 
 
 def log(*a):
@@ -52,8 +61,10 @@ def build_pipeline(rank, device, dual=False):
     from diffcodec_amd.vae import HipAutoencoderKL
     t0 = time.time()
     specs = [W.unet_spec(), W.controlnet_spec(), W.vae_spec()] + ([W.rescontrolnet_spec()] if dual else [])
-    if rank == 0:
-        sds = [W.synthesize(s, seed=i) for i, s in enumerate(specs)]
+    if rank == 0:   # one seeded generator per spec: independent streams, drawn on concurrent host threads (same values)
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(len(specs)) as ex:
+            sds = list(ex.map(lambda a: W.synthesize(a[1], seed=a[0]), enumerate(specs)))
     else:   # shapes only; the packed device tensors are overwritten by the broadcast from rank 0
         sds = [{k: torch.empty(shape) for k, (_, shape) in s.items()} for s in specs]
     log(f"[rank {rank}] state dicts ready in {time.time() - t0:.1f}s")
@@ -65,6 +76,25 @@ def build_pipeline(rank, device, dual=False):
                                                      scheduler=DDIMScheduler(), safety_checker=None, feature_extractor=None)
     log(f"[rank {rank}] operators packed + uploaded in {time.time() - t0:.1f}s")
     return pipe, (sds if rank == 0 else None)
+
+
+def dump_outputs(path, units):
+    """--dump-outputs: `units` (the decoded units of the last timed step) as fp32 path/decoded_units.npy.  Above DUMP_BYTES, a
+    fixed seeded subset of whole units is written instead, with their indices in path/decoded_units_index.npy (float64)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    a = units.detach().float().cpu().numpy()
+    idx_path = os.path.join(path, "decoded_units_index.npy")
+    if os.path.exists(idx_path):
+        os.remove(idx_path)
+    per = a[0].nbytes + 8 if len(a) else 1
+    keep = (DUMP_BYTES - 4096) // per
+    if keep < len(a):
+        idx = np.sort(np.random.default_rng(0).choice(len(a), size=keep, replace=False))
+        a = a[idx]
+        np.save(idx_path, idx.astype(np.float64))
+    np.save(os.path.join(path, "decoded_units.npy"), np.ascontiguousarray(a))
+    log(f"wrote {a.shape} float32 of the last timed step to {path}")
 
 
 def cpu_baseline(sds, threads, device_decode=None):
@@ -173,7 +203,13 @@ def main():
     ap.add_argument("--no-roofline", action="store_true", help="skip the post-timing legs (profiling runs)")
     ap.add_argument("--c3-batch", type=int, default=44, help="units per pipe call of the strong-scaling C3 pass")
     ap.add_argument("--shapes-out", default=None, help="write the in-situ per-shape launch table of the roofline leg to this file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the decoded units of the last timed step (rank 0) "
+                    "to DIR/decoded_units.npy")
+    ap.add_argument("--full", action="store_true", help="after the timed region also run the C3 clip, single-frame / GOP-12 "
+                    "batches, U-Net forward, VAE encode, validation config, roofline, CPU baseline and multi-rank gather")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args.gpus)                                  # does not return
     if int(os.environ.get("WORLD_SIZE", "1")) != args.gpus:
@@ -255,10 +291,12 @@ def main():
         dt = max(per)                                            # the contract's MAX over ranks
         rank_ms = dict(min=round(min(per) / args.steps * 1e3, 3), max=round(max(per) / args.steps * 1e3, 3),
                        per_rank=[round(p / args.steps * 1e3, 3) for p in per])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
 
     # ---- the optional exchange, timed on its own (never part of `value`): uint8 gather of one step's units onto rank 0
     gather_ms = None
-    if world > 1:
+    if world > 1 and args.full:
         u8 = CD.units_to_u8(out)
         torch.cuda.synchronize()
         dist.barrier()
@@ -273,7 +311,7 @@ def main():
     # ---- BASELINE configs[2] as a STRONG-scaling job (every rank takes part): one 97-frame GOP-12 clip = 88 inter-frame units
     #      dealt round-robin over the ranks (11 per rank at 8 ranks), decoded in batches of at most --c3-batch units
     c3 = None
-    if not c4 and not args.no_roofline and args.config == "c2":
+    if args.full and not c4 and not args.no_roofline and args.config == "c2":
         units3 = CD.plan_units(97, 12, SIZE, SIZE)
         mine3 = CD.shard(units3, rank, world)
         b3 = max(1, min(args.c3_batch, len(mine3)))
@@ -303,7 +341,7 @@ def main():
                   note="BASELINE configs[2]: the 88 inter frames of one 97-frame GOP-12 clip at 512x512, sharded round-robin over the ranks")
         del o3, src3
 
-    extras = rank == 0 and not args.no_roofline
+    extras = rank == 0 and args.full and not args.no_roofline
 
     def timed_units(units, reps=3):
         for i in range(2):
@@ -476,7 +514,7 @@ def main():
         pipe.enable_dual_stream(bool(args.dual_stream))
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not c4:      # host-core baseline: single-GPU runs only
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not c4:   # host-core baseline: 1-GPU runs only
         single_pipe = pipe
         dev_decode = lambda inp, kw_: single_pipe(**{k: v.to(device) for k, v in inp.items()}, output_type="pt", **kw_).images
         cpu = cpu_baseline(sds, threads=max(1, min(len(os.sched_getaffinity(0)), int(os.environ.get("DC_CPU_THREADS", "16")))),

@@ -9,7 +9,7 @@ for spec in sys.argv[1:]:
     for kv in filter(None, envs.split(",")):
         k, _, v = kv.partition("=")
         env[k] = v.replace("$ROOT", ROOT)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"],
                          env=env, capture_output=True, text=True)
     try:
         d = json.loads(out.stdout.strip().splitlines()[-1])
