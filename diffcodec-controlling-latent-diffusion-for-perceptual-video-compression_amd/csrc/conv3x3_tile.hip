@@ -638,6 +638,16 @@ __global__ __launch_bounds__(256, 2) void conv3x3_tile_kernel(const dc_conv_desc
 #endif
 }
 
+}  // namespace
+
+// Specialised epilogue mode of a halo-tile launch (0 = generic run-time flags, 1 = plain, 2 = residual).
+int dc_conv3x3_tile_epi(const dc_conv_desc& d)
+{
+    return (!DC_EPI_SPECIALIZE || d.splitk > 1 || d.out_f32 || d.act) ? 0 : (d.residual ? 2 : 1);
+}
+
+namespace {
+
 template <int TM, int TN, int NSTB, bool FAST = false, bool UPS = false, bool SH = false>
 int launch_tile(const dc_conv_desc& d, hipStream_t st)
 {
@@ -652,7 +662,7 @@ int launch_tile(const dc_conv_desc& d, hipStream_t st)
 #else
     const size_t lds = HALO_ROWS * (FAST ? (SH ? DC_SH_HP : 160) : 128) + NSTB * BN * 128;
 #endif
-    const int epi = (!DC_EPI_SPECIALIZE || d.splitk > 1 || d.out_f32 || d.act) ? 0 : (d.residual ? 2 : 1);
+    const int epi = dc_conv3x3_tile_epi(d);
     // tile order inside an XCD's range (see the kernel): pixel tiles fastest when the weight tensor is larger than the activations
     static const int force_order = DC_KNOB("DC_CONV_ORDER", -1);   // developer A/B knob: 0 = n fastest, 1 = m fastest
     const int order = force_order >= 0 ? force_order : ((long long)d.Cout * 9 > (long long)d.N * d.H * d.W ? 1 : 0);
@@ -714,6 +724,8 @@ static int tile_variant(const dc_conv_desc& d)
         return 8;
     return 2;
 }
+
+int dc_conv3x3_tile_variant(const dc_conv_desc& d) { return tile_variant(d); }
 
 // gn_part_out chunks per sample of this launch (0: not available — split-K partial tiles are finished elsewhere).
 int dc_conv3x3_tile_gn_chunks(const dc_conv_desc& d)

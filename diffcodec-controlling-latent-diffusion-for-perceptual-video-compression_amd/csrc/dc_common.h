@@ -19,6 +19,16 @@ typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
 
 #define DC_WAVE 64
 
+// Kernel choice for one dc_conv_desc (DC_ROUTE_* of diffcodec_hip.h): computed once by the routing functions and read both by the
+// launchers and by the dc_conv_route query, so that the two cannot disagree.
+struct dc_route {
+    int kernel;     // DC_ROUTE_*
+    int variant;    // template / tile form inside the kernel family (see dc_conv_route)
+    int epi;        // specialised epilogue mode (0 = generic)
+    int splitk;     // effective split-K
+    int ln_first;   // the LayerNorm finalize pass runs first, into ln_scratch
+};
+
 // Developer A/B switches of the launchers (tile shape, ring depth, kernel selection).  The product library is built WITHOUT
 // DC_DEV_KNOBS, so every DC_KNOB folds to its default and no dispatch decision depends on the environment; scratch builds of
 // tools/ (-DDC_DEV_KNOBS) read the variable once.

@@ -547,32 +547,52 @@ int dc_gemm_rowpanel_wanted(const dc_conv_desc& d, int epi);
 int dc_gemm_rowpanel_launch(const dc_conv_desc& d, int epi, hipStream_t st);
 int dc_gemm_rowpanel_gn_chunks(const dc_conv_desc& d);
 
-int dc_gemm_dma_launch(const dc_conv_desc& d, hipStream_t st)
+// The decision of dc_gemm_dma_launch for a 1x1 descriptor: kernel, gemm_dma template (variant = TM*10000 + TN*1000 + stages*100 +
+// A_REG*10 + PROD), epilogue mode, and whether the LayerNorm finalize runs first.  The launch and dc_conv_route both read it.
+int dc_gemm_dma_route(const dc_conv_desc& d, dc_route& r)
 {
     const long long M = (long long)d.N * d.Ho * d.Wo;
     // the folded LayerNorm and the row statistics live in the staged (bf16, unsplit) epilogue only
     if ((d.ln_stats || d.stats_out || d.gn_part_out) && (d.out_f32 || d.splitk > 1)) return DC_ERR_INVALID;
     if (d.gn_part_out && dc_gemm_dma_gn_chunks(d) == 0) return DC_ERR_INVALID;
+    r.variant = 0;
     {
         const int epi = epi_mode(d);
-        if (dc_gemm_rowpanel_wanted(d, epi)) return dc_gemm_rowpanel_launch(d, epi, st);
+        r.epi = epi;
+        if (dc_gemm_rowpanel_wanted(d, epi)) {
+            if (d.gn_part_out && epi > 2) return DC_ERR_INVALID;
+            if ((epi == 3 || epi == 5) && !d.ln_colsum) return DC_ERR_INVALID;
+            r.kernel = DC_ROUTE_GEMM_ROWPANEL;
+            return DC_OK;
+        }
         if (d.ln_stats && d.ln_parts > 0) {
-            // raw LayerNorm partials and a kernel whose waves do not own whole rows: the finalize pass runs here, into the
+            // raw LayerNorm partials and a kernel whose waves do not own whole rows: the finalize pass runs first, into the
             // caller's scratch, and the launch proceeds on (mean, rstd) pairs — the same bits as finalizing beforehand
-            if (!d.ln_scratch) return DC_ERR_INVALID;
-            const int rc = dc_ln_finalize(d.ln_stats, d.ln_scratch, M, d.ln_parts, d.C1 + d.C2, d.ln_eps, (void*)st);
-            if (rc != DC_OK) return rc;
             dc_conv_desc q = d;
-            q.ln_stats = d.ln_scratch;
+            if (q.ln_scratch) q.ln_stats = q.ln_scratch;
             q.ln_parts = 0;
-            return dc_gemm_dma_launch(q, st);
+            const int rc = dc_gemm_dma_route(q, r);
+            r.ln_first = 1;
+            return rc;
         }
         if (d.ln_stats && !d.ln_colsum) return DC_ERR_INVALID;
-        if (dc_gemm_p8_wanted(d, epi)) return dc_gemm_p8_launch(d, epi, st);
-        if (dc_gemm_wide_wanted(d, epi)) return dc_gemm_wide_launch(d, epi, st);
+        if (dc_gemm_p8_wanted(d, epi)) {
+            r.kernel = DC_ROUTE_GEMM_P8;
+            return DC_OK;
+        }
+        if (dc_gemm_wide_wanted(d, epi)) {
+            r.kernel = DC_ROUTE_GEMM_WIDE;
+            return DC_OK;
+        }
     }
     if (d.ln_stats && !d.ln_colsum) return DC_ERR_INVALID;
     if (d.stats_out && d.epilogue != 0) return DC_ERR_INVALID;
+    r.kernel = DC_ROUTE_GEMM_DMA;
+    auto pick = [&](int tm, int tn, int nst, int a_reg, int prod) {
+        r.variant = tm * 10000 + tn * 1000 + nst * 100 + a_reg * 10 + prod;
+        if (!prod) r.epi = 0;                                   // developer-knob shapes: the generic epilogue only
+        return DC_OK;
+    };
     const bool n160 = (d.Cout % 160 == 0) && d.epilogue == 0;
     const int bn = n160 ? 160 : 128;
     const long long big = ((M + 127) / 128) * ((d.Cout + bn - 1) / bn) * (d.splitk > 1 ? d.splitk : 1);
@@ -580,15 +600,15 @@ int dc_gemm_dma_launch(const dc_conv_desc& d, hipStream_t st)
     // other waits for its DMA); the small tiles afford 3 stages at the same residency.
     static const int force_nst = DC_KNOB("DC_GEMM_NST", 0);   // developer knobs
     static const int force_small = DC_KNOB("DC_GEMM_SMALL", 0);
-    if (force_small == 1) return n160 ? launch_gemm<2, 5, 2>(d, st) : launch_gemm<2, 4, 3>(d, st);
-    if (force_small == 2) return launch_gemm<2, 2, 3>(d, st);
-    if (force_small == 3) return launch_gemm<2, 4, 2>(d, st);
+    if (force_small == 1) return n160 ? pick(2, 5, 2, 0, 0) : pick(2, 4, 3, 0, 0);
+    if (force_small == 2) return pick(2, 2, 3, 0, 0);
+    if (force_small == 3) return pick(2, 4, 2, 0, 0);
     static const int hybrid = DC_KNOB("DC_GEMM_HYBRID", 0);   // measured: no gain over all-DMA
-    if (hybrid && big >= 256) return n160 ? launch_gemm<4, 5, 2, true>(d, st) : launch_gemm<4, 4, 2, true>(d, st);
-    if (hybrid) return n160 ? launch_gemm<2, 5, 2, true>(d, st) : launch_gemm<2, 4, 2, true>(d, st);
-    if (force_nst == 4 && big >= 256) return n160 ? launch_gemm<4, 5, 4>(d, st) : launch_gemm<4, 4, 4>(d, st);
-    if (force_nst == 3 && big >= 256) return n160 ? launch_gemm<4, 5, 3>(d, st) : launch_gemm<4, 4, 3>(d, st);
-    if (big >= 256) return n160 ? launch_gemm<4, 5, 2, false, true>(d, st) : launch_gemm<4, 4, 2, false, true>(d, st);
+    if (hybrid && big >= 256) return n160 ? pick(4, 5, 2, 1, 0) : pick(4, 4, 2, 1, 0);
+    if (hybrid) return n160 ? pick(2, 5, 2, 1, 0) : pick(2, 4, 2, 1, 0);
+    if (force_nst == 4 && big >= 256) return n160 ? pick(4, 5, 4, 0, 0) : pick(4, 4, 4, 0, 0);
+    if (force_nst == 3 && big >= 256) return n160 ? pick(4, 5, 3, 0, 0) : pick(4, 4, 3, 0, 0);
+    if (big >= 256) return n160 ? pick(4, 5, 2, 0, 1) : pick(4, 4, 2, 0, 1);
     // Grids that cannot even put one workgroup on every CU (the 16x16 / 8x8 levels of a one- or two-frame decode) are bound by
     // the serial K loop: one LDS-DMA round trip per 64-wide step.  They take a deeper ring — the whole CU's LDS for one
     // workgroup, three or four stages in flight instead of one — with the same tile shape (so the statistics / GroupNorm partial
@@ -596,8 +616,64 @@ int dc_gemm_dma_launch(const dc_conv_desc& d, hipStream_t st)
     static const int deep = DC_KNOB("DC_GEMM_DEEP", 1);        // developer A/B knob
     const long long small = ((M + 63) / 64) * ((d.Cout + bn - 1) / bn) * (d.splitk > 1 ? d.splitk : 1);
     const int KT = (d.C1 + d.C2) >> 6;
-    if (deep && small <= 256 && KT >= 6) return n160 ? launch_gemm<2, 5, 4, false, true>(d, st) : launch_gemm<2, 4, 5, false, true>(d, st);
-    return n160 ? launch_gemm<2, 5, 2, false, true>(d, st) : launch_gemm<2, 4, 3, false, true>(d, st);
+    if (deep && small <= 256 && KT >= 6) return n160 ? pick(2, 5, 4, 0, 1) : pick(2, 4, 5, 0, 1);
+    return n160 ? pick(2, 5, 2, 0, 1) : pick(2, 4, 3, 0, 1);
+}
+
+namespace {
+
+int launch_gemm_variant(const dc_conv_desc& d, int variant, hipStream_t st)
+{
+    switch (variant) {
+#define DC_DMA_VARIANT(TM, TN, NST, AR, PR) \
+    case TM * 10000 + TN * 1000 + NST * 100 + AR * 10 + PR: return launch_gemm<TM, TN, NST, (AR != 0), (PR != 0)>(d, st);
+        DC_DMA_VARIANT(4, 5, 2, 0, 1)
+        DC_DMA_VARIANT(4, 4, 2, 0, 1)
+        DC_DMA_VARIANT(2, 5, 4, 0, 1)
+        DC_DMA_VARIANT(2, 4, 5, 0, 1)
+        DC_DMA_VARIANT(2, 5, 2, 0, 1)
+        DC_DMA_VARIANT(2, 4, 3, 0, 1)
+#ifdef DC_DEV_KNOBS
+        DC_DMA_VARIANT(2, 5, 2, 0, 0)
+        DC_DMA_VARIANT(2, 4, 3, 0, 0)
+        DC_DMA_VARIANT(2, 2, 3, 0, 0)
+        DC_DMA_VARIANT(2, 4, 2, 0, 0)
+        DC_DMA_VARIANT(4, 5, 2, 1, 0)
+        DC_DMA_VARIANT(4, 4, 2, 1, 0)
+        DC_DMA_VARIANT(2, 5, 2, 1, 0)
+        DC_DMA_VARIANT(2, 4, 2, 1, 0)
+        DC_DMA_VARIANT(4, 5, 4, 0, 0)
+        DC_DMA_VARIANT(4, 4, 4, 0, 0)
+        DC_DMA_VARIANT(4, 5, 3, 0, 0)
+        DC_DMA_VARIANT(4, 4, 3, 0, 0)
+#endif
+#undef DC_DMA_VARIANT
+        default: return DC_ERR_INVALID;
+    }
+}
+
+}  // namespace
+
+int dc_gemm_dma_launch(const dc_conv_desc& d, hipStream_t st)
+{
+    dc_route r{};
+    int rc = dc_gemm_dma_route(d, r);
+    if (rc != DC_OK) return rc;
+    dc_conv_desc q = d;
+    if (r.ln_first) {
+        if (!d.ln_scratch) return DC_ERR_INVALID;
+        const long long M = (long long)d.N * d.Ho * d.Wo;
+        rc = dc_ln_finalize(d.ln_stats, d.ln_scratch, M, d.ln_parts, d.C1 + d.C2, d.ln_eps, (void*)st);
+        if (rc != DC_OK) return rc;
+        q.ln_stats = d.ln_scratch;
+        q.ln_parts = 0;
+    }
+    switch (r.kernel) {
+        case DC_ROUTE_GEMM_ROWPANEL: return dc_gemm_rowpanel_launch(q, r.epi, st);
+        case DC_ROUTE_GEMM_P8: return dc_gemm_p8_launch(q, r.epi, st);
+        case DC_ROUTE_GEMM_WIDE: return dc_gemm_wide_launch(q, r.epi, st);
+        default: return launch_gemm_variant(q, r.variant, st);
+    }
 }
 
 // gn_part_out chunks per sample of this launch (0: not available)

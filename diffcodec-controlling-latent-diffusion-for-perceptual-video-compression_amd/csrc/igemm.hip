@@ -20,6 +20,9 @@ int dc_conv3x3_tile_launch(const dc_conv_desc& d, hipStream_t st);
 // gemm_dma.hip: LDS-DMA pipelined GEMM for 1x1 convs / linears without a load-side transform
 int dc_gemm_dma_supported(const dc_conv_desc& d);
 int dc_gemm_dma_launch(const dc_conv_desc& d, hipStream_t st);
+int dc_gemm_dma_route(const dc_conv_desc& d, dc_route& r);
+int dc_conv3x3_tile_variant(const dc_conv_desc& d);
+int dc_conv3x3_tile_epi(const dc_conv_desc& d);
 int dc_gemm_dma_gn_chunks(const dc_conv_desc& d);
 int dc_conv3x3_tile_gn_chunks(const dc_conv_desc& d);
 
@@ -387,11 +390,12 @@ extern "C" long long dc_conv_igemm_ws_bytes(const dc_conv_desc* d)
     return (long long)d->N * d->Ho * d->Wo * d->Cout * 4 * d->splitk;
 }
 
-extern "C" int dc_conv_igemm_bf16(const dc_conv_desc* dp, void* stream)
+// Descriptor checks, normalisation (split-K fixpoint, row_add_stride) and kernel choice: the one routing function of
+// dc_conv_igemm_bf16 and dc_conv_route.  `d` receives the normalised descriptor the kernels are launched with.
+static int conv_route(const dc_conv_desc& in, dc_conv_desc& d, dc_route& r)
 {
-    if (!dp) return DC_ERR_INVALID;
-    dc_conv_desc d = *dp;
-    hipStream_t st = (hipStream_t)stream;
+    d = in;
+    r = dc_route{};
     const int Cin = d.C1 + d.C2;
     if (!d.x1 || !d.w || !d.out) return DC_ERR_INVALID;
     if (d.ksize != 1 && d.ksize != 3) return DC_ERR_INVALID;
@@ -415,7 +419,6 @@ extern "C" int dc_conv_igemm_bf16(const dc_conv_desc* dp, void* stream)
     if (d.row_add_stride == 0) d.row_add_stride = d.Cout;
     if (d.epilogue == 1 && (d.splitk > 1 || (d.Cout & 31) || d.residual || d.row_add || d.out_f32)) return DC_ERR_INVALID;
     if (d.splitk > 1) {
-        if (!d.splitk_ws) return DC_ERR_INVALID;
         // every split must own a non-empty K range, or its slab would stay unwritten: shrink to the fixpoint of
         // splitk = ceil(KT / ceil(KT / splitk)) (KT = 64-wide K steps, the unit all three kernels partition by)
         const int nkc = (d.C1 + d.C2) >> 6;
@@ -427,6 +430,7 @@ extern "C" int dc_conv_igemm_bf16(const dc_conv_desc* dp, void* stream)
             d.splitk = s2;
         }
     }
+    r.splitk = d.splitk;
     const long long M = (long long)d.N * d.Ho * d.Wo;
     // Tile choice: wide-N tile (160) when Cout is a multiple of 160 (all SD-1.5 UNet widths), else 128;
     // tall-M tile (128) only when that still yields >= 2 workgroups per CU.
@@ -435,13 +439,63 @@ extern "C" int dc_conv_igemm_bf16(const dc_conv_desc* dp, void* stream)
     const long long big_tiles = ((M + 127) / 128) * ((d.Cout + bn - 1) / bn) * d.splitk;
     if ((d.ln_stats || d.stats_out) && !dc_gemm_dma_supported(d)) return DC_ERR_INVALID;   // LDS-DMA GEMM epilogue only
     if (d.gn_part_out && dc_conv_gn_part_chunks(&d) == 0) return DC_ERR_INVALID;
-    int rc;
-    if (dc_gemm_dma_supported(d)) rc = dc_gemm_dma_launch(d, st);
-    else if (dc_conv3x3_tile_supported(d)) rc = dc_conv3x3_tile_launch(d, st);
-    else if (big_tiles >= 512) rc = n160 ? launch_cfg<2, 2, 4, 5>(d, st) : launch_cfg<2, 2, 4, 4>(d, st);
-    else rc = n160 ? launch_cfg<2, 2, 2, 5>(d, st) : launch_cfg<2, 2, 2, 4>(d, st);
+    if (dc_gemm_dma_supported(d)) {
+        const int rc = dc_gemm_dma_route(d, r);
+        r.splitk = d.splitk;
+        return rc;
+    }
+    if (dc_conv3x3_tile_supported(d)) {
+        r.kernel = DC_ROUTE_CONV3X3_TILE;
+        r.variant = dc_conv3x3_tile_variant(d);
+        r.epi = dc_conv3x3_tile_epi(d);
+        return DC_OK;
+    }
+    r.kernel = DC_ROUTE_IGEMM;
+    r.variant = (big_tiles >= 512 ? 40 : 20) + (n160 ? 5 : 4);
+    return DC_OK;
+}
+
+extern "C" int dc_conv_route(const dc_conv_desc* dp, int* info)
+{
+    if (!info) return DC_ERR_INVALID;
+    for (int i = 0; i < DC_ROUTE_INFO_INTS; ++i) info[i] = 0;
+    if (!dp) return DC_ERR_INVALID;
+    dc_conv_desc d;
+    dc_route r;
+    const int rc = conv_route(*dp, d, r);
+    if (rc != DC_OK) return rc;
+    info[0] = r.kernel;
+    info[1] = r.variant;
+    info[2] = r.epi;
+    info[3] = r.splitk;
+    info[4] = r.ln_first;
+    return DC_OK;
+}
+
+extern "C" int dc_conv_igemm_bf16(const dc_conv_desc* dp, void* stream)
+{
+    if (!dp) return DC_ERR_INVALID;
+    dc_conv_desc d;
+    dc_route r;
+    hipStream_t st = (hipStream_t)stream;
+    int rc = conv_route(*dp, d, r);
+    if (rc != DC_OK) return rc;
+    if (d.splitk > 1 && !d.splitk_ws) return DC_ERR_INVALID;
+    switch (r.kernel) {
+        case DC_ROUTE_CONV3X3_TILE: rc = dc_conv3x3_tile_launch(d, st); break;
+        case DC_ROUTE_IGEMM:
+            switch (r.variant) {
+                case 45: rc = launch_cfg<2, 2, 4, 5>(d, st); break;
+                case 44: rc = launch_cfg<2, 2, 4, 4>(d, st); break;
+                case 25: rc = launch_cfg<2, 2, 2, 5>(d, st); break;
+                default: rc = launch_cfg<2, 2, 2, 4>(d, st); break;
+            }
+            break;
+        default: rc = dc_gemm_dma_launch(d, st); break;        // re-derives the same dc_gemm_dma_route decision
+    }
     if (rc != DC_OK) return rc;
     if (d.splitk > 1) {
+        const long long M = (long long)d.N * d.Ho * d.Wo;
         const long long total4 = M * d.Cout / 4;
         hipLaunchKernelGGL(splitk_finish_kernel, dim3(dc_cdiv(total4, 256)), dim3(256), 0, st, d, total4);
         return dc_launch_status();

@@ -2,6 +2,7 @@
 
 Activations are NHWC bf16 tensors of shape [N,H,W,C] (a [B,L,C] token sequence is the same memory with H=1, W=L).
 No arithmetic happens in torch on this path; every function below ends in exactly one or more `lib.call`s."""
+import ctypes
 import math
 
 import torch
@@ -174,6 +175,29 @@ def ln_finalize(partials, c, eps):
     return mr
 
 
+ROUTE_NAMES = {1: "gemm_dma", 2: "gemm_wide", 3: "gemm_p8", 4: "gemm_rowpanel", 5: "conv3x3_tile", 6: "igemm"}
+
+
+class ConvRoute(tuple):
+    """(kernel, variant, epi, splitk, ln_first) of one dc_conv_desc: what dc_conv_igemm_bf16 launches for it (dc_conv_route)."""
+    __slots__ = ()
+    kernel = property(lambda s: ROUTE_NAMES[s[0]])
+    variant = property(lambda s: s[1])
+    epi = property(lambda s: s[2])
+    splitk = property(lambda s: s[3])
+    ln_first = property(lambda s: bool(s[4]))
+
+
+def conv_route(d):
+    """The dispatcher's decision for a ConvDesc, without launching (host code only: needs the library, not a GPU).  Raises
+    HipLaunchError for a descriptor the launch would refuse."""
+    info = (ctypes.c_int * 5)()
+    rc = lib.load().dc_conv_route(d, info)
+    if rc != 0:
+        raise lib.HipLaunchError(f"dc_conv_route returned {rc} (invalid argument)")
+    return ConvRoute(tuple(info))
+
+
 def rowpanel_takes(rows, rows_per_sample, cin, cout):
     """Mirror of dc_gemm_rowpanel_wanted (csrc/gemm_rowpanel.hip) for plain / residual / folded-LN 1x1 launches: the K = 320 kernel that
     keeps a 256-row panel in registers — the only GEMM of the family that can apply a GroupNorm affine on load (`gn_ab` without SiLU).
@@ -241,11 +265,6 @@ def conv(x1, pc, *, x2=None, gn_ab=None, gn_silu=False, row_add=None, residual=N
         _chk(ln_stats, F32, "ln_partials")
         assert ln_stats.dim() == 3 and ln_stats.shape[0] == m and ln_stats.shape[2] == 2
         ln_parts = int(ln_stats.shape[1])
-        # scratch for (mean, rstd): only the tile kernels need it — the row-panel kernel finalizes in its prologue (the C side mirrors
-        # `rowpanel_takes` and returns DC_ERR_INVALID if the two ever disagree)
-        takes_rp = (k == 1 and x2 is None and (gn_ab is None or not gn_silu) and pc.bias is not None and not out_f32
-                    and ln_parts <= 16 and rowpanel_takes(m, ho * wo, pc.cin, pc.cout))
-        ln_scratch = None if takes_rp else torch.empty((m, 2), device=x1.device, dtype=F32)
     if ln_stats is not None or stats_out is not None:
         splitk = 1                          # the folded LayerNorm / row statistics live in the unsplit bf16 epilogue
     if splitk is None:
@@ -280,6 +299,11 @@ def conv(x1, pc, *, x2=None, gn_ab=None, gn_silu=False, row_add=None, residual=N
                  out_scale=float(out_scale), splitk=int(splitk), gn_batch=0 if gn_ab is None else gn_ab.shape[0],
                  act=int(act), row_add_stride=int(ras), ln_stats=_ptr(ln_stats), ln_colsum=_ptr(pc.colsum if ln_stats is not None else None),
                  stats_out=_ptr(stats_out), gn_part_out=0, ln_parts=ln_parts, ln_eps=float(ln_eps), ln_scratch=_ptr(ln_scratch))
+    if ln_parts > 0 and conv_route(d).ln_first:
+        # scratch for (mean, rstd) only where the dispatcher runs the finalize pass first (the row-panel kernel finalizes in its
+        # prologue): the library's own routing decides, not a Python restatement of it
+        ln_scratch = torch.empty((m, 2), device=x1.device, dtype=F32)
+        d.ln_scratch = ln_scratch.data_ptr()
     part = None
     if gn_part and GN_EPILOGUE_STATS and not out_f32 and not pc.geglu and splitk == 1 and ln_stats is None:
         chunks = lib.load().dc_conv_gn_part_chunks(d)

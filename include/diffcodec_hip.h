@@ -127,6 +127,23 @@ typedef struct dc_conv_desc {
     float* ln_scratch;
 } dc_conv_desc;
 int dc_conv_igemm_bf16(const dc_conv_desc* desc, void* stream);
+/* The dispatcher's decision for `desc`, without launching anything: the same routing function dc_conv_igemm_bf16 runs.
+ * Returns what the launch would return for its descriptor checks (0 or DC_ERR_INVALID; operand checks that do not steer the
+ * route — splitk_ws and ln_scratch being set — are left to the launch) and fills info[DC_ROUTE_INFO_INTS]:
+ *   info[0] kernel: one of DC_ROUTE_*;
+ *   info[1] variant: gemm_dma TM*10000 + TN*1000 + stages*100 + A_REG*10 + PROD (its template); igemm TM*10 + TN;
+ *           conv3x3_tile its tile rows (2 / 4, 8 = two 8x8 images per tile); 0 for the other kernels;
+ *   info[2] epilogue mode (gemm_dma family and conv3x3_tile: the specialised epilogue; 0 = generic run-time flags);
+ *   info[3] effective split-K (after shrinking to the fixpoint where every split owns a non-empty K range);
+ *   info[4] 1 if the LayerNorm finalize runs first as its own pass into `ln_scratch` (then required), else 0. */
+#define DC_ROUTE_INFO_INTS 5
+#define DC_ROUTE_GEMM_DMA 1
+#define DC_ROUTE_GEMM_WIDE 2
+#define DC_ROUTE_GEMM_P8 3
+#define DC_ROUTE_GEMM_ROWPANEL 4
+#define DC_ROUTE_CONV3X3_TILE 5
+#define DC_ROUTE_IGEMM 6
+int dc_conv_route(const dc_conv_desc* desc, int* info);
 /* Workspace bytes needed for splitk>1 (0 otherwise). */
 long long dc_conv_igemm_ws_bytes(const dc_conv_desc* desc);
 /* Partials per output row that a 1x1 / linear launch with `stats_out` writes (one per wave column slice of the tile grid). */

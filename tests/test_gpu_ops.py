@@ -7,6 +7,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from launch_shadow import capture_routes
+
 pytestmark = pytest.mark.gpu
 
 
@@ -200,20 +202,28 @@ CONV_CASES = [
     (2, 16, 16, 128, 0, 128, 3, 2, 1, False),       # stride 2
     (1, 16, 16, 64, 0, 64, 3, 2, 0, False),         # asymmetric pad (VAE encoder)
     (1, 8, 8, 64, 0, 128, 3, 1, 1, True),           # fused nearest-2x upsample
-    (2, 16, 16, 320, 0, 320, 3, 1, 1, True),        # Upsample2D conv on the pipelined path: 8-row tiles, 160-column tiles, four-slot ring
+    (2, 16, 16, 320, 0, 320, 3, 1, 1, True),        # Upsample2D conv on the pipelined path: 4-row tiles (too few for 8-row ones), 160-column tiles, four-slot ring
     (20, 16, 24, 128, 0, 320, 3, 1, 1, True),       # the same with > 256 workgroups (two-slot ring), non-square map
     (3, 10, 8, 192, 0, 256, 3, 1, 1, True),         # 4-row tiles (Ho = 20), 128-column tiles
     (2, 8, 8, 320, 0, 320, 1, 1, 1, False),         # 1x1
-    (2, 64, 64, 320, 0, 320, 3, 1, 1, False),       # UNet 64x64 ResBlock conv (large tile path; <= 256 workgroups: four-slot weight ring)
-    (10, 64, 64, 128, 64, 320, 3, 1, 1, False),     # the same path with > 256 workgroups: two-slot ring, two workgroups per CU, skip concat
+    (2, 64, 64, 320, 0, 320, 3, 1, 1, False),       # UNet 64x64 ResBlock conv (halo-tile path, 4-row tiles; <= 256 workgroups: four-slot weight ring)
+    (10, 64, 64, 128, 64, 320, 3, 1, 1, False),     # the same path with > 256 workgroups: 8-row tiles, two-slot ring, two workgroups per CU, skip concat
     (9, 32, 16, 192, 0, 256, 3, 1, 1, False),       # 128-column tiles, 4-row tiles, batch not a power of two
     (2, 8, 8, 1280, 1280, 1280, 3, 1, 1, False),    # UNet 8x8 up-block conv (split-K path)
     # weight-stationary tile order (round 4: pixel tile fastest inside an XCD where Cout * 9 > N * H * W) on grids that are not a multiple of 8
     (3, 8, 8, 640, 0, 1280, 3, 1, 1, False),        # 8x8, odd batch: 4-row tiles, 3 x 8 N tiles
-    (6, 8, 8, 320, 0, 1280, 3, 1, 1, False),        # 8x8, two images per tile
+    (6, 8, 8, 320, 0, 1280, 3, 1, 1, False),        # 8x8, even batch, split-K 5: too few tiles for two images per tile, 4-row tiles
     (5, 16, 16, 320, 0, 1280, 3, 1, 1, False),      # 16x16: 5 x 2 pixel tiles x 8 N tiles
     (1, 16, 16, 256, 0, 640, 3, 1, 1, True),        # fused upsample (16x16 -> 32x32) in the new order
 ]
+
+
+# (kernel, variant) dc_conv_route reports for each case above: conv3x3_tile variant = tile rows (2: 4-row tiles, 4: 8-row tiles,
+# 8: two 8x8 images per tile), igemm 24 = the 64 x 128 gather-GEMM tile, gemm_dma 25201 = its 64-row tile with the deep ring
+CONV_ROUTES = [("conv3x3_tile", 2), ("conv3x3_tile", 2), ("igemm", 24), ("conv3x3_tile", 2), ("igemm", 24), ("igemm", 24),
+               ("conv3x3_tile", 2), ("conv3x3_tile", 2), ("conv3x3_tile", 2), ("conv3x3_tile", 2), ("gemm_dma", 25201),
+               ("conv3x3_tile", 2), ("conv3x3_tile", 4), ("conv3x3_tile", 2), ("conv3x3_tile", 2), ("conv3x3_tile", 2),
+               ("conv3x3_tile", 2), ("conv3x3_tile", 2), ("conv3x3_tile", 2)]
 
 
 @pytest.mark.parametrize("case", CONV_CASES)
@@ -232,7 +242,9 @@ def test_conv_igemm_plain(ops, case):
         xin = F.pad(xin, (0, 1, 0, 1))
     ref = F.conv2d(xin, wt, b, stride=stride, padding=(1 if (k == 3 and pad) else 0))
     pc = ops.PackedConv(wt, b, DEV)
-    out = ops.conv(nhwc(x1), pc, x2=None if x2 is None else nhwc(x2), stride=stride, pad=pad, upsample=up)
+    with capture_routes() as routes:
+        out = ops.conv(nhwc(x1), pc, x2=None if x2 is None else nhwc(x2), stride=stride, pad=pad, upsample=up)
+    assert [(r.kernel, r.variant) for r in routes] == [CONV_ROUTES[CONV_CASES.index(case)]], routes
     close(from_nhwc(out), ref)
 
 
@@ -460,15 +472,19 @@ def test_wide_gemm_long_k_shapes(ops, m, k, n):
     xd = x.to(DEV, torch.bfloat16)
     pc = ops.PackedConv(w, b, DEV)
     ref = F.linear(x, w, b)
-    out = ops.linear(xd, pc)
+    with capture_routes() as routes:
+        out = ops.linear(xd, pc)
+    assert [r.kernel for r in routes] == ["gemm_wide"], routes
     close(out.float().cpu(), ref)
     assert torch.equal(out, ops.linear(xd, pc))
     # residual + scale + statistics (4-D call: per-sample GroupNorm partials)
     hw = 4096 if m % 4096 == 0 else 2048
     res = bf(torch.randn(1, m, n, generator=g))
     st = torch.full((m, ops.row_stats_parts(n), 2), float("nan"), device=DEV)
-    y = ops.conv(xd.reshape(m // hw, hw // 64, 64, k), pc, residual=res.to(DEV, torch.bfloat16).reshape(m // hw, hw // 64, 64, n),
-                 out_scale=0.7, stats_out=st, gn_part=True)
+    with capture_routes() as routes:
+        y = ops.conv(xd.reshape(m // hw, hw // 64, 64, k), pc, residual=res.to(DEV, torch.bfloat16).reshape(m // hw, hw // 64, 64, n),
+                     out_scale=0.7, stats_out=st, gn_part=True)
+    assert [r.kernel for r in routes] == ["gemm_wide"], routes
     ref2 = 0.7 * ref + res
     close(y.reshape(1, m, n).float().cpu(), ref2, rtol=3e-2, atol=3e-2)
     yf = y.reshape(m, n).float().cpu()
@@ -496,7 +512,8 @@ def test_wide_gemm_long_k_shapes(ops, m, k, n):
     close(ops.conv(xa, pc, x2=xb).reshape(1, m, n).float().cpu(), ref)
 
 
-@pytest.mark.parametrize("m,k,n", [(8192, 640, 3584), (7168, 1344, 4096), (14336, 640, 1920)])
+@pytest.mark.parametrize("m,k,n", [(8192, 640, 3584), (7168, 1344, 4096), (14336, 640, 1920),
+                                   (15104, 640, 1920)])        # 59 row tiles: a short last group of the gm = 8 tile order, half-full last column tile
 def test_p8_gemm_shapes(ops, m, k, n):
     """Shapes the dispatcher hands to the 256 x 256 four-phase GEMM (gemm_p8.hip: no residual / statistics, whole 256 x 256 tiles,
     >= 448 of them, K >= 640; an even and an odd number of K tiles; a half-full last column tile): bias, folded LayerNorm, GEGLU, folded LayerNorm + GEGLU against
@@ -520,7 +537,9 @@ def test_p8_gemm_shapes(ops, m, k, n):
              (ops.PackedConv(w, b, DEV, geglu=True), None, hid * F.gelu(gate)),
              (ops.PackedConv(w, b, DEV, geglu=True, ln=(lg, lb, 1e-5)), mr, hid_ln * F.gelu(gate_ln))]
     for pc, stats, ref in cases:
-        out = ops.linear(xd, pc, ln_stats=stats)
+        with capture_routes() as routes:
+            out = ops.linear(xd, pc, ln_stats=stats)
+        assert [r.kernel for r in routes] == ["gemm_p8"], routes
         close(out.float().cpu(), ref, rtol=3e-2, atol=3e-2)
         assert torch.equal(out, ops.linear(xd, pc, ln_stats=stats))
         assert torch.equal(out[:, :256], ops.linear(head, pc, ln_stats=None if stats is None else mr_head))

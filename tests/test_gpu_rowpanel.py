@@ -15,6 +15,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from launch_shadow import capture_routes
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 M, K, CH = 65536, 320, 16384
@@ -36,6 +38,16 @@ def _rows(g, m, c, scale=1.0):
     return (torch.randn(1, m, c, generator=g) * scale).to(DEV, torch.bfloat16)
 
 
+def _on(kernel, fn, ln_first=None):
+    """fn() must issue exactly one GEMM launch, on `kernel` (dc_conv_route of its descriptor); returns fn()'s value."""
+    with capture_routes() as routes:
+        y = fn()
+    assert [r.kernel for r in routes] == [kernel], routes
+    if ln_first is not None:
+        assert routes[0].ln_first == ln_first, routes
+    return y
+
+
 def _sample_rows():
     # every wave of a panel, first / last panels, all 16 fragment rows and both row tiles
     idx = list(range(0, 256)) + list(range(M - 256, M)) + list(range(256 * 100 + 3, M, 4099))
@@ -49,8 +61,10 @@ def test_bias_mode_equals_tile_kernel_and_fp64(ops, n_out):
     w = bf(torch.randn(n_out, K, generator=g) / math.sqrt(K))
     b = torch.randn(n_out, generator=g)
     pc = ops.PackedConv(w, b, DEV)
-    big = ops.linear(x, pc)
-    small = torch.cat([ops.linear(x[:, i:i + CH], pc) for i in range(0, M, CH)], 1)
+    with capture_routes() as routes:
+        big = ops.linear(x, pc)
+        small = torch.cat([ops.linear(x[:, i:i + CH], pc) for i in range(0, M, CH)], 1)
+    assert [r.kernel for r in routes] == ["gemm_rowpanel"] + ["gemm_dma"] * (M // CH), routes
     assert torch.equal(big, small)
     rows = _sample_rows()
     ref = F.linear(x[0, rows].double().cpu(), w.double(), b.double())
@@ -68,7 +82,7 @@ def test_residual_scale_and_row_statistics(ops):
     pc = ops.PackedConv(w, b, DEV)
     parts = ops.row_stats_parts(n_out)
     st = torch.full((M, parts, 2), float("nan"), device=DEV)
-    big = ops.linear(x, pc, residual=res, out_scale=0.75, stats_out=st)
+    big = _on("gemm_rowpanel", lambda: ops.linear(x, pc, residual=res, out_scale=0.75, stats_out=st))
     sts = torch.empty((M, parts, 2), device=DEV)
     small = torch.cat([ops.linear(x[:, i:i + CH], pc, residual=res[:, i:i + CH], out_scale=0.75, stats_out=sts[i:i + CH])
                        for i in range(0, M, CH)], 1)
@@ -94,7 +108,7 @@ def test_groupnorm_partials_from_the_epilogue(ops):
     w = bf(torch.randn(c, K, 1, 1, generator=g) / math.sqrt(K))
     b = torch.randn(c, generator=g)
     pc = ops.PackedConv(w, b, DEV)
-    big = ops.conv(x, pc, residual=res, gn_part=True)
+    big = _on("gemm_rowpanel", lambda: ops.conv(x, pc, residual=res, gn_part=True))
     assert hasattr(big, "gn_part") and big.gn_part.shape[0] == hw * hw // 32      # one partial per 32-row wave panel
     gamma, beta = (1 + 0.1 * torch.randn(c, generator=g)).to(DEV), (0.1 * torch.randn(c, generator=g)).to(DEV)
     ab_big = ops.group_norm_ab(big, gamma, beta, 32, 1e-5)
@@ -114,7 +128,7 @@ def test_folded_layernorm_qkv(ops):
     gamma, beta = 1 + 0.2 * torch.randn(K, generator=g), 0.2 * torch.randn(K, generator=g)
     pc = ops.PackedConv(w, None, DEV, ln=(gamma, beta, 1e-5))
     mr = ops.ln_finalize(ops.row_stats(x), K, 1e-5)
-    big = ops.linear(x, pc, ln_stats=mr)
+    big = _on("gemm_rowpanel", lambda: ops.linear(x, pc, ln_stats=mr))
     small = torch.cat([ops.linear(x[:, i:i + CH], pc, ln_stats=mr[i:i + CH]) for i in range(0, M, CH)], 1)
     assert torch.equal(big, small)
     rows = _sample_rows()
@@ -133,7 +147,7 @@ def test_geglu_feed_forward(ops, ln):
     pc = ops.PackedConv(w, b, DEV, geglu=True, ln=lnp)
     mr = ops.ln_finalize(ops.row_stats(x), K, 1e-5) if ln else None
     kw = lambda i: dict(ln_stats=mr[i:i + CH]) if ln else {}
-    big = ops.linear(x, pc, **(dict(ln_stats=mr) if ln else {}))
+    big = _on("gemm_rowpanel", lambda: ops.linear(x, pc, **(dict(ln_stats=mr) if ln else {})))
     assert big.shape == (1, M, n_out // 2)
     small = torch.cat([ops.linear(x[:, i:i + CH], pc, **kw(i)) for i in range(0, M, CH)], 1)
     assert torch.equal(big, small)
@@ -156,7 +170,7 @@ def test_full_batch_shape_131072_rows(ops):
     w = bf(torch.randn(320, K, generator=g) / math.sqrt(K))
     b = torch.randn(320, generator=g)
     pc = ops.PackedConv(w, b, DEV)
-    big = ops.linear(x, pc)
+    big = _on("gemm_rowpanel", lambda: ops.linear(x, pc))
     small = torch.cat([ops.linear(x[:, i:i + CH], pc) for i in range(0, m, CH)], 1)
     assert torch.equal(big, small)
 
@@ -177,7 +191,7 @@ def test_layernorm_finalize_folded_into_the_consumer(ops, m):
         pc = ops.PackedConv(torch.randn(n_out, K, generator=g) / math.sqrt(K), 0.1 * torch.randn(n_out, generator=g), DEV,
                             geglu=geglu, ln=(gamma, beta, 1e-5))
         a = ops.linear(t, pc, ln_stats=ops.ln_finalize(st, K, 1e-5))
-        b = ops.linear(t, pc, ln_partials=(st, 1e-5))
+        b = _on("gemm_rowpanel" if m == M else "gemm_dma", lambda: ops.linear(t, pc, ln_partials=(st, 1e-5)), ln_first=m != M)
         assert torch.equal(a, b)
     one = ops.row_stats(t)                                                       # the single-part form (row_stats)
     pc = ops.PackedConv(torch.randn(320, K, generator=g) / math.sqrt(K), None, DEV, ln=(gamma, beta, 1e-5))
@@ -199,7 +213,7 @@ def test_groupnorm_affine_on_load_equals_the_standalone_pass(ops):
     parts = ops.row_stats_parts(c)
     st_a = torch.full((n * hw * hw, parts, 2), float("nan"), device=DEV)
     st_b = torch.empty_like(st_a)
-    fused = ops.conv(x, pc, gn_ab=ab, gn_silu=False, stats_out=st_a)
+    fused = _on("gemm_rowpanel", lambda: ops.conv(x, pc, gn_ab=ab, gn_silu=False, stats_out=st_a))
     two_pass = ops.conv(ops.gn_apply(x, ab), pc, stats_out=st_b)
     assert torch.equal(fused, two_pass)
     assert torch.equal(st_a, st_b)
@@ -228,5 +242,7 @@ def test_layernorm_finalize_folded_into_the_tile_gemms(ops, m, k):
         pc = ops.PackedConv(torch.randn(n_out, k, generator=g) / math.sqrt(k), 0.1 * torch.randn(n_out, generator=g), DEV,
                             geglu=geglu, ln=(gamma, beta, 1e-5))
         a = ops.linear(t, pc, ln_stats=ops.ln_finalize(st, k, 1e-5))
-        b = ops.linear(t, pc, ln_partials=(st, 1e-5))
+        with capture_routes() as routes:
+            b = ops.linear(t, pc, ln_partials=(st, 1e-5))
+        assert [(r.kernel in ("gemm_dma", "gemm_wide", "gemm_p8"), r.ln_first) for r in routes] == [(True, True)], routes
         assert torch.equal(a, b)

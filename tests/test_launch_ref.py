@@ -1,0 +1,350 @@
+"""CPU: the fp64 launch references of oracle/launch_ref.py equal the torch formulas, unpack every PackedConv layout, and the
+checker accepts a correct bf16 result computed in another accumulation order while rejecting realistic kernel faults."""
+import math
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from oracle import launch_ref as L
+
+BF = torch.bfloat16
+
+
+def _packed(cin, cout, k, **kw):
+    from diffcodec_amd.ops import PackedConv
+    g = torch.Generator().manual_seed(cin * 7 + cout + k)
+    w = torch.randn(cout, cin, k, k, generator=g) / math.sqrt(cin * k * k)
+    b = torch.randn(cout, generator=g) * 0.1
+    return PackedConv(w, b, "cpu", **kw), w, b
+
+
+def _wq(pc):
+    """checkpoint-order weights as stored (bf16-rounded) -> OIHW fp32"""
+    w, b = L.unpack_weight(pc)
+    k = pc.ksize
+    return w.reshape(pc.cout, k, k, pc.cin).permute(0, 3, 1, 2).float(), None if b is None else b.float()
+
+
+def _x(n, h, w, c, seed=0, mean=0.0):
+    return (torch.randn(n, h, w, c, generator=torch.Generator().manual_seed(seed)) + mean).to(BF)
+
+
+def _torch_conv(x, pc, *, x2=None, gn_ab=None, gn_silu=False, stride=1, pad=1, upsample=False):
+    xx = x.float() if x2 is None else torch.cat([x.float(), x2.float()], -1)
+    if gn_ab is not None:
+        ab = gn_ab[torch.arange(xx.shape[0]) % gn_ab.shape[0]]
+        xx = xx * ab[:, None, None, :, 0] + ab[:, None, None, :, 1]
+        if gn_silu:
+            xx = F.silu(xx)
+    t = xx.permute(0, 3, 1, 2)
+    if upsample:
+        t = F.interpolate(t, scale_factor=2, mode="nearest")
+    w, b = _wq(pc)
+    if pc.ksize == 3 and not pad:
+        t = F.pad(t, (0, 1, 0, 1))
+    y = F.conv2d(t, w, b, stride=stride, padding=1 if (pc.ksize == 3 and pad) else 0)
+    return y.permute(0, 2, 3, 1)
+
+
+def _all_rows(y):
+    return torch.arange(y.numel() // y.shape[-1])
+
+
+@pytest.mark.parametrize("k,stride,pad,up", [(1, 1, 1, False), (3, 1, 1, False), (3, 2, 1, False), (3, 2, 0, False), (3, 1, 1, True)])
+@pytest.mark.parametrize("cat,gn,silu", [(False, False, False), (True, True, True), (False, True, False)])
+def test_conv_ref_equals_torch(k, stride, pad, up, cat, gn, silu):
+    pc, _, _ = _packed(128, 32, k)
+    x1 = _x(2, 6, 10, 64 if cat else 128, 1)
+    x2 = _x(2, 6, 10, 64, 2) if cat else None
+    ab = torch.randn(2, 128, 2, generator=torch.Generator().manual_seed(3)) if gn else None
+    ref = _torch_conv(x1, pc, x2=x2, gn_ab=ab, gn_silu=silu, stride=stride, pad=pad, upsample=up)
+    rows = _all_rows(ref)
+    r, s = L.conv_ref(x1, pc, rows, x2=x2, gn_ab=ab, gn_silu=silu, stride=stride, pad=pad, upsample=up)
+    assert torch.allclose(r.float(), ref.reshape(-1, 32), atol=1e-4, rtol=1e-4)
+    assert (s >= 0).all()
+
+
+def test_conv_ref_epilogue_fusions():
+    pc, _, _ = _packed(64, 48, 1)
+    x = _x(3, 4, 4, 64, 4)
+    ra = torch.randn(3, 48, generator=torch.Generator().manual_seed(5))
+    res = _x(3, 4, 4, 48, 6)
+    for act, fn in ((0, lambda z: z), (1, F.silu), (2, lambda z: z * torch.sigmoid(1.702 * z))):
+        z = _torch_conv(x, pc) + ra[:, None, None, :]
+        ref = fn(z) * 0.7 + res.float()
+        r, _ = L.conv_ref(x, pc, _all_rows(ref), row_add=ra, residual=res, out_scale=0.7, act=act)
+        assert torch.allclose(r.float(), ref.reshape(-1, 48), atol=1e-4, rtol=1e-4), act
+
+
+def test_geglu_and_folded_layernorm_unpack():
+    from diffcodec_amd.ops import PackedConv
+    g = torch.Generator().manual_seed(9)
+    w, b = torch.randn(128, 64, generator=g) / 8, torch.randn(128, generator=g)
+    gamma, beta = 1 + 0.1 * torch.randn(64, generator=g), 0.1 * torch.randn(64, generator=g)
+    x = _x(1, 1, 40, 64, 10, mean=1.5)
+    # GEGLU: packed rows interleaved 16 | 16, the reference undoes it
+    pc = PackedConv(w, b, "cpu", geglu=True)
+    wq, bq = _wq(pc)
+    hg = F.linear(x.float().reshape(-1, 64), wq[:, :, 0, 0], bq)
+    ref = hg[:, :64] * F.gelu(hg[:, 64:])
+    r, _ = L.conv_ref(x, pc, torch.arange(40))
+    assert torch.allclose(r.float(), ref, atol=1e-4, rtol=1e-4)
+    # folded LayerNorm (+ GEGLU): Linear(LN(x)) with the stored W', b'
+    pc = PackedConv(w, b, "cpu", geglu=True, ln=(gamma, beta, 1e-5))
+    wq, bq = _wq(pc)
+    xl = F.layer_norm(x.double().reshape(-1, 64), (64,), eps=1e-5)
+    hg = xl @ wq[:, :, 0, 0].double().T + bq.double()
+    ref = hg[:, :64] * F.gelu(hg[:, 64:])
+    r, _ = L.conv_ref(x, pc, torch.arange(40))
+    assert torch.allclose(r, ref, atol=1e-9, rtol=1e-9)
+    # and W' = W diag(gamma), b' = b + W beta up to the bf16 rounding of W'
+    pc = PackedConv(w, b, "cpu", ln=(gamma, beta, 1e-5))
+    wq, bq = _wq(pc)
+    assert torch.allclose(wq[:, :, 0, 0], w * gamma, rtol=2 ** -8, atol=1e-6)
+    assert torch.allclose(bq, b + w @ beta, atol=1e-5)
+
+
+@pytest.mark.parametrize("cin,cout,kw", [(4, 320, {}), (320, 4, {}), (320, 4, {"mfma_small_cout": True}), (128, 8, {})])
+def test_every_packed_layout_unpacks(cin, cout, kw):
+    pc, w, b = _packed(cin, cout, 3, **kw)
+    assert pc.kind == {(4, 320): "small_cin", (128, 8): "small_cout"}.get((cin, cout), "small_cout" if not kw else "igemm")
+    wq, bq = _wq(pc)
+    assert torch.equal(wq, w.to(BF).float()) and torch.allclose(bq, b)
+    x = _x(1, 5, 7, cin, 11)
+    ref = _torch_conv(x, pc)
+    r, _ = L.conv_ref(x, pc, _all_rows(ref))
+    assert torch.allclose(r.float(), ref.reshape(-1, cout), atol=1e-4, rtol=1e-4)
+
+
+def test_attention_refs_equal_explicit_softmax():
+    g = torch.Generator().manual_seed(12)
+    qkv = torch.randn(2, 24, 3 * 64, generator=g).to(BF)
+    q, k, v = qkv[..., :64], qkv[..., 64:128], qkv[..., 128:]
+    rows = torch.arange(48)
+    for causal in (False, True):
+        r, s = L.attention_ref(q, k, v, 4, rows, causal=causal)
+        qq, kk, vv = (t.float().reshape(2, 24, 4, 16).transpose(1, 2) for t in (q, k, v))
+        lg = qq @ kk.transpose(-1, -2) / 4.0
+        if causal:
+            lg = lg.masked_fill(torch.ones(24, 24, dtype=torch.bool).triu(1), -math.inf)
+        ref = (torch.softmax(lg, -1) @ vv).transpose(1, 2).reshape(48, 64)
+        assert torch.allclose(r.float(), ref, atol=1e-5)
+
+
+def test_norm_refs_equal_torch():
+    g = torch.Generator().manual_seed(13)
+    x, x2 = _x(2, 4, 4, 64, 14, mean=0.5), _x(2, 4, 4, 32, 15)
+    gamma, beta = torch.randn(96, generator=g), torch.randn(96, generator=g)
+    ab, st = L.group_norm_ab_ref(x, gamma, beta, 32, 1e-6, x2=x2)
+    xx = torch.cat([x.float(), x2.float()], -1).permute(0, 3, 1, 2)
+    ref = F.group_norm(xx.double(), 32, gamma.double(), beta.double(), 1e-6).permute(0, 2, 3, 1)
+    y = xx.double().permute(0, 2, 3, 1) * ab[:, None, None, :, 0] + ab[:, None, None, :, 1]
+    assert torch.allclose(y, ref, atol=1e-9)
+    assert L.check_group_norm_ab(ab.float(), ab, st)["ok"]
+    bad = ab.clone()
+    bad[1, 40:43, 1] += 0.02 * ab[1, 40:43, 0]                      # one group's shift off by 2 % of a standard deviation
+    assert not L.check_group_norm_ab(bad.float(), ab, st)["ok"]
+    rows = torch.arange(32)
+    r, _ = L.gn_apply_ref(x, ab.float(), rows, silu=True, x2=x2)
+    assert torch.allclose(r, F.silu(ref.reshape(32, 96)), atol=1e-6)
+    gm, bt = gamma[:64], beta[:64]
+    r, _ = L.layer_norm_ref(x, gm, bt, 1e-5, rows)
+    assert torch.allclose(r, F.layer_norm(x.double().reshape(32, 64), (64,), gm.double(), bt.double(), 1e-5), atol=1e-9)
+    fg, fb = _x(1, 4, 4, 64, 16), _x(1, 4, 4, 64, 17)
+    r, _ = L.fdn_modulate_ref(x, ab[:, :64].float(), fg, fb, rows)
+    ref = (x.double() * ab[:, None, None, :64, 0] + ab[:, None, None, :64, 1]) * (1 + fg.double()) + fb.double()
+    assert torch.allclose(r, ref.reshape(32, 64), atol=1e-6)
+    st, _ = L.row_stats_ref(x, rows)
+    xr = x.double().reshape(32, 64)
+    assert torch.allclose(st[:, 0], torch.stack([xr.sum(1), (xr * xr).sum(1)], 1))
+    mr, _ = L.ln_finalize_ref(st.float(), 64, 1e-5, rows)
+    assert torch.allclose(mr[:, 0], xr.mean(1), atol=1e-6)
+    assert torch.allclose(mr[:, 1], 1 / torch.sqrt(xr.var(1, unbiased=False) + 1e-5), rtol=1e-5)
+
+
+def test_elementwise_refs():
+    g = torch.Generator().manual_seed(18)
+    s = torch.randn(8, 40, generator=g)
+    p, _ = L.softmax_rows_ref(s, 0.3, torch.arange(8))
+    assert torch.allclose(p, torch.softmax(s.double() * 0.3, 1))
+    x = torch.randn(3, 5, 7, generator=g).to(BF)
+    t, _ = L.transpose_ref(x, torch.arange(21))
+    assert torch.equal(t, x.transpose(1, 2).reshape(21, 5).double())
+    x = _x(2, 8, 8, 32, 19)
+    r, _ = L.freeu_backbone_ref(x, 1.4, torch.arange(128))
+    assert torch.equal(r[:, 16:], x.reshape(-1, 32)[:, 16:].double()) and torch.allclose(r[:, :16], 1.4 * x.reshape(-1, 32)[:, :16].double())
+    r, _ = L.freeu_lowfreq_ref(x, 0.9, torch.arange(128))
+    xf = x.double().permute(0, 3, 1, 2)
+    X = torch.fft.fftshift(torch.fft.fftn(xf, dim=(-2, -1)), dim=(-2, -1))
+    m = torch.ones(8, 8, dtype=torch.float64)
+    m[3:5, 3:5] = 0.9                                           # diffusers fourier_filter, threshold 1
+    ref = torch.fft.ifftn(torch.fft.ifftshift(X * m, dim=(-2, -1)), dim=(-2, -1)).real.permute(0, 2, 3, 1).reshape(-1, 32)
+    assert torch.allclose(r, ref, atol=1e-9)
+    r, _ = L.timestep_embedding_ref(951.0, 2, 320)
+    f = torch.exp(-math.log(10000) * torch.arange(160, dtype=torch.float64) / 160)
+    assert torch.allclose(r[1], torch.cat([torch.cos(951 * f), torch.sin(951 * f)]))
+
+
+# ------------------------------------------------------------------------------------------ the checker catches faults
+M_T, N_T, K_T = 1024, 64, 256            # four 256-row tiles, one 64-wide N tile per 16-column fragment group, four 64-wide K chunks
+
+
+def _gemm_case():
+    from diffcodec_amd.ops import PackedConv
+    g = torch.Generator().manual_seed(21)
+    w = torch.randn(N_T, K_T, generator=g) / 16
+    b = torch.randn(N_T, generator=g)
+    pc = PackedConv(w, b, "cpu")
+    x = torch.randn(1, 1, M_T, K_T, generator=g).to(BF)
+    wq, bq = L.unpack_weight(pc)
+    return pc, x, wq[:, 0].float(), bq.float()
+
+
+def _verdict(y, pc, x, **kw):
+    rows = L.sample_rows(M_T)
+    r, s = L.conv_ref(x, pc, rows, **kw)
+    return L.check(y.reshape(-1, y.shape[-1])[rows], r, s, y.dtype)
+
+
+def _fp32_gemm(x, w, order=1):
+    """fp32 accumulation over 64-wide K chunks, in a given chunk order (a different kernel's summation order)"""
+    xs = x.float().reshape(-1, K_T)
+    acc = torch.zeros(xs.shape[0], w.shape[0])
+    chunks = list(range(0, K_T, 64))[::order]
+    for c in chunks:
+        acc = acc + xs[:, c:c + 64] @ w[:, c:c + 64].T
+    return acc
+
+
+def test_checker_accepts_another_accumulation_order():
+    pc, x, w, b = _gemm_case()
+    for order in (1, -1):
+        y = (_fp32_gemm(x, w, order) + b).to(BF)
+        v = _verdict(y, pc, x)
+        assert v["ok"], v
+        assert v["ratio"] < 0.75            # one bf16 rounding: at most half an ulp, e_out is one
+
+
+FAULTS = ["k_chunk_missing", "fragment_transposed", "rows_swapped", "tile_zero", "tile_duplicate", "bias_missing_n_tile"]
+
+
+@pytest.mark.parametrize("fault", FAULTS)
+def test_checker_rejects_gemm_faults(fault):
+    pc, x, w, b = _gemm_case()
+    acc = _fp32_gemm(x, w)
+    t = 2                                   # the faulty 256-row tile
+    lo, hi = t * 256, (t + 1) * 256
+    if fault == "k_chunk_missing":
+        acc[lo:hi] -= x.float().reshape(-1, K_T)[lo:hi, 64:128] @ w[:, 64:128].T
+    y = acc + b
+    if fault == "fragment_transposed":
+        y[lo:lo + 16, 16:32] = y[lo:lo + 16, 16:32].T.clone()
+    elif fault == "rows_swapped":
+        ra, rb = lo + 5, lo + 64 + 37 * t % 64          # two rows of the tile (one of them a sampled row)
+        y[[ra, rb]] = y[[rb, ra]]
+    elif fault == "tile_zero":
+        y[lo:hi] = 0
+    elif fault == "tile_duplicate":
+        y[lo:hi] = y[lo - 256:lo].clone()
+    elif fault == "bias_missing_n_tile":
+        y[:, 32:48] -= b[32:48]
+    v = _verdict(y.to(BF), pc, x)
+    assert not v["ok"], (fault, v)
+
+
+def test_checker_rejects_epilogue_faults():
+    pc, x, w, b = _gemm_case()
+    res = torch.randn(1, 1, M_T, N_T, generator=torch.Generator().manual_seed(22)).to(BF)
+    z = _fp32_gemm(x, w) + b
+    good = (z * 0.5 + res.reshape(-1, N_T).float()).to(BF)
+    assert _verdict(good, pc, x, residual=res, out_scale=0.5)["ok"]
+    twice = (z * 0.5 + 2 * res.reshape(-1, N_T).float()).to(BF)
+    assert not _verdict(twice, pc, x, residual=res, out_scale=0.5)["ok"]
+    scaled = ((z + res.reshape(-1, N_T).float()) * 0.5).to(BF)
+    assert not _verdict(scaled, pc, x, residual=res, out_scale=0.5)["ok"]
+
+
+def test_checker_rejects_geglu_halves_swapped_and_stale_layernorm_stats():
+    from diffcodec_amd.ops import PackedConv
+    g = torch.Generator().manual_seed(23)
+    w, b = torch.randn(128, 256, generator=g) / 16, torch.randn(128, generator=g)
+    x = (torch.randn(1, 1, 512, 256, generator=g) * (1 + torch.arange(512.0)[:, None] / 64) + torch.randn(512, 1, generator=g)).to(BF)
+    pc = PackedConv(w, b, "cpu", geglu=True)
+    wq, bq = L.unpack_weight(pc)
+    hg = x.double().reshape(-1, 256) @ wq[:, 0].T + bq
+    rows = L.sample_rows(512)
+    r, s = L.conv_ref(x, pc, rows)
+    good = (hg[:, :64] * F.gelu(hg[:, 64:])).to(BF)
+    swapped = (hg[:, 64:] * F.gelu(hg[:, :64])).to(BF)
+    assert L.check(good[rows], r, s, BF)["ok"]
+    assert not L.check(swapped[rows], r, s, BF)["ok"]
+    gamma, beta = 1 + 0.1 * torch.randn(256, generator=g), 0.1 * torch.randn(256, generator=g)
+    pc = PackedConv(w[:64], b[:64], "cpu", ln=(gamma, beta, 1e-5))
+    wq, bq = L.unpack_weight(pc)
+    xr = x.double().reshape(-1, 256)
+    mean, var = xr.mean(1, keepdim=True), xr.var(1, unbiased=False, keepdim=True)
+    fold = lambda m, v: ((xr - m) / torch.sqrt(v + 1e-5)) @ wq[:, 0].T + bq
+    r, s = L.conv_ref(x, pc, rows)
+    assert L.check(fold(mean, var).to(BF)[rows], r, s, BF)["ok"]
+    stale = fold(torch.roll(mean, 1, 0), torch.roll(var, 1, 0)).to(BF)          # every row fed the previous row's statistics
+    assert not L.check(stale[rows], r, s, BF)["ok"]
+
+
+def test_checker_rejects_a_skipped_key_block():
+    g = torch.Generator().manual_seed(24)
+    q, k, v = (torch.randn(1, 256, 64, generator=g).to(BF) for _ in range(3))
+    rows = torch.arange(256)
+    r, s = L.attention_ref(q, k, v, 2, rows)
+    good = r.to(BF)
+    assert L.check(good, r, s, BF)["ok"]
+    kk = k.clone()
+    sel = torch.ones(256, dtype=torch.bool)
+    sel[64:128] = False                                           # head 1 skips its second 64-key block
+    qq, kh, vh = q[0, :, 32:].double(), k[0, sel, 32:].double(), v[0, sel, 32:].double()
+    bad = r.clone()
+    bad[:, 32:] = torch.softmax(qq @ kh.T / math.sqrt(32), -1) @ vh
+    assert not L.check(bad.to(BF), r, s, BF)["ok"]
+
+
+# ------------------------------------------------------------------------------------------ the row sampler
+def test_sampler_touches_every_tile_residue_border_and_boundary():
+    M = 88 * 64 * 64
+    rows = L.sample_rows(M, spatial=(88, 64, 64))
+    assert rows[0] == 0 and rows[-1] == M - 1 and (rows[:256] == torch.arange(256)).all()
+    assert set((rows // 256).tolist()) == set(range(M // 256))                    # every 256-row block (so every M tile)
+    for tile in (64, 128, 256):
+        assert set((rows // tile).tolist()) == set(range(M // tile))
+    assert set((rows % 64).tolist()) == set(range(64))
+    for n in range(88):
+        s = set(rows[(rows // 4096) == n].tolist())
+        base = n * 4096
+        oy, ox = (0, 63) if n % 2 == 0 else (63, 0)
+        assert all(base + oy * 64 + i in s for i in range(64)) and all(base + i * 64 + ox in s for i in range(64))
+    # the VAE's last up-block of a 44-frame call: 44 x 512 x 512 rows of 256 bf16 channels (5.8 GB)
+    M, rb = 44 * 512 * 512, 256 * 2
+    rows = set(L.sample_rows(M, row_bytes=[rb]).tolist())
+    for lim in (2 ** 31, 2 ** 32):
+        r = lim // rb
+        assert all(i in rows for i in range(r - 128, r + 128))
+
+
+@pytest.mark.parametrize("stride,silu", [(1, True), (2, False), (2, True)])
+def test_conv3x3_nchw_f32_ref_equals_torch(stride, silu):
+    g = torch.Generator().manual_seed(30 + stride)
+    full = torch.randn(2, 24, 9, 11, generator=g)
+    x = full[:, 4:20]                                            # a channel-slice view, as the extractors pass
+    w, b = torch.randn(8, 16, 3, 3, generator=g) / 12, torch.randn(8, generator=g)
+    ref = F.conv2d(x.double(), w.double(), b.double(), stride=stride, padding=1)
+    if silu:
+        ref = F.silu(ref)
+    n, co, ho, wo = ref.shape
+    rows = L.sample_rows(n * ho * wo, spatial=(n, ho, wo))
+    r, s = L.conv3x3_nchw_f32_ref(x, w, b, rows, stride=stride, silu=silu)
+    assert torch.allclose(r, ref.permute(0, 2, 3, 1).reshape(-1, co)[rows], atol=1e-12)
+    y = F.conv2d(x, w, b, stride=stride, padding=1)
+    y = (F.silu(y) if silu else y).permute(0, 2, 3, 1).reshape(-1, co)[rows]
+    assert L.check(y, r, s, torch.float32)["ok"]                # torch's own fp32 conv: another accumulation order
+    bad = y.clone()
+    bad[3, 2] *= 1 + 2 ** -12                                    # a bf16-class error is far outside an fp32 launch's bound
+    assert not L.check(bad, r, s, torch.float32)["ok"]
