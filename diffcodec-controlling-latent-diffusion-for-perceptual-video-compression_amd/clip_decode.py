@@ -87,6 +87,13 @@ class DirectorySource:
         from .io_utils import load_controls_and_flows
         return load_controls_and_flows(*self.paths(frame, prev, nxt), size=self.size, device=self.device)
 
+    def ground_truth(self, frame):
+        """The original frame <root>/<video>/images/frame_%04d.png as uint8 [H,W,3] on `device`, loaded like the anchors
+        (BICUBIC resize to `size`, also Pillow's default behind validation.py:120's `.resize((512, 512))`)."""
+        from .io_utils import _load_rgb_u8
+        path = os.path.join(self.root, self.video, "images", f"frame_{frame:04d}.png")
+        return torch.from_numpy(_load_rgb_u8(path, self.size)).to(self.device)
+
 
 class SyntheticSource:
     """Seeded synthetic controls of the shapes the reference feeds `pipe(...)`; frame f of every rank
@@ -222,10 +229,8 @@ def gather_units(local_u8, units, rank=None, world=None, mode="unit", dst=0):
     return out
 
 
-def blend_frames(unit_u8, units, height, width, overlap=64):
-    """uint8 unit images [n,th,tw,3] of COMPLETE frames -> {frame: uint8 [H,W,3]} (device blend kernel when the tensor
-    lives on the GPU, `tiling.merge_ramp` on the host otherwise; both blend the 8-bit tiles in fp32 with the same op
-    order, so the two are bit-identical)."""
+def _blend_frame_tensors(unit_u8, units, height, width, overlap=64):
+    """blend_frames before the host copy: {frame: uint8 [H,W,3] tensor on the device of `unit_u8`} (decode_clip scores these)."""
     from . import ops, tiling
     if unit_u8.dtype != torch.uint8:
         raise ValueError("blend_frames takes uint8 unit images (units_to_u8)")
@@ -239,20 +244,68 @@ def blend_frames(unit_u8, units, height, width, overlap=64):
         coords = [w for _, _, w in lst]
         tiles = unit_u8[idx]
         if len(lst) == 1 and coords[0] == (0, height, 0, width):
-            frames[f] = tiles[0].cpu().numpy()
+            frames[f] = tiles[0]
         elif tiles.is_cuda:
             frames[f] = ops.blend_tiles_ramp(tiles.permute(0, 3, 1, 2).float().contiguous(), coords, (height, width), overlap,
-                                             scale=1.0).cpu().numpy()
+                                             scale=1.0)
         else:
-            frames[f] = tiling.merge_ramp([t.numpy() for t in tiles], coords, (height, width), order="hwc", feather=overlap)
+            frames[f] = torch.from_numpy(tiling.merge_ramp([t.numpy() for t in tiles], coords, (height, width), order="hwc",
+                                                           feather=overlap))
     return frames
+
+
+def blend_frames(unit_u8, units, height, width, overlap=64):
+    """uint8 unit images [n,th,tw,3] of COMPLETE frames -> {frame: uint8 [H,W,3]} (device blend kernel when the tensor
+    lives on the GPU, `tiling.merge_ramp` on the host otherwise; both blend the 8-bit tiles in fp32 with the same op
+    order, so the two are bit-identical)."""
+    return {f: t.cpu().numpy() for f, t in _blend_frame_tensors(unit_u8, units, height, width, overlap).items()}
+
+
+def score_frames(frames, source):
+    """{frame: uint8 [H,W,3] tensor} -> {frame: {"psnr": dB, "ms_ssim": value}} against `source.ground_truth(frame)`, with L = 255
+    (test_utils.py:23-24, :55; validation.py:147-150 on x / 255 gives the same values), on the device of the frames."""
+    from . import metrics
+    scores = {}
+    for f, pred in sorted(frames.items()):
+        gt = source.ground_truth(f).to(pred.device)
+        if gt.shape != pred.shape:
+            raise ValueError(f"ground truth of frame {f} has shape {tuple(gt.shape)}, the decoded frame {tuple(pred.shape)}")
+        x, y = pred.unsqueeze(0), gt.unsqueeze(0)
+        scores[f] = dict(psnr=float(metrics.psnr(x, y, data_range=255.0)[0]), ms_ssim=float(metrics.ms_ssim(x, y, data_range=255)))
+    return scores
+
+
+def gather_scores(scores, units, rank, world, dst=0):
+    """Every rank's {frame: {"psnr", "ms_ssim"}} -> the union on `dst` (None elsewhere): ONE `dist.gather` of a float64
+    [inter frames, 3] tensor (scored flag, PSNR, MS-SSIM) per rank; no pixels travel."""
+    import torch.distributed as dist
+    frames = sorted({u.frame for u in units})
+    row = {f: i for i, f in enumerate(frames)}
+    dev = "cpu" if dist.get_backend() == "gloo" else torch.device("cuda", torch.cuda.current_device())
+    send = torch.zeros((len(frames), 3), dtype=torch.float64)
+    for f, s in scores.items():
+        send[row[f]] = torch.tensor([1.0, s["psnr"], s["ms_ssim"]], dtype=torch.float64)
+    send = send.to(dev)
+    bufs = [torch.empty_like(send) for _ in range(world)] if rank == dst else None
+    dist.gather(send, bufs, dst=dst)
+    if rank != dst:
+        return None
+    out = {}
+    for b in bufs:
+        for f, (have, p, m) in zip(frames, b.cpu().tolist()):
+            if have:
+                out[f] = dict(psnr=p, ms_ssim=m)
+    return dict(sorted(out.items()))
 
 
 @torch.no_grad()
 def decode_clip(pipe, source, num_frames, gop_size, height, width, prompt_embeds, negative_prompt_embeds=None, *, tile=512,
-                overlap=64, batch=16, seed=0, rank=None, world=None, shard_mode="unit", gather=True, **pipe_kwargs):
+                overlap=64, batch=16, seed=0, rank=None, world=None, shard_mode="unit", gather=True, score=False, **pipe_kwargs):
     """Whole pipeline for one clip on this rank.  Returns dict(units=all units, mine=this rank's, images=this rank's fp32 unit
-    images, frames={frame: uint8 HxWx3} on the gathering rank (or for locally complete frames when gather=False))."""
+    images, frames={frame: uint8 HxWx3} on the gathering rank (or for locally complete frames when gather=False)).
+    score=True adds scores={frame: {"psnr": dB, "ms_ssim": value}}: each blended frame against `source.ground_truth(frame)` on
+    the device, from the uint8 frames `frames` holds (score_frames).  With gather=False and world > 1 every rank scores its
+    complete frames and one gather of the scores (not the pixels) gives rank 0 all of them; other ranks keep their own."""
     if rank is None or world is None:
         ini = torch.distributed.is_available() and torch.distributed.is_initialized()
         rank = torch.distributed.get_rank() if ini else 0
@@ -265,10 +318,19 @@ def decode_clip(pipe, source, num_frames, gop_size, height, width, prompt_embeds
                           frame_size=(height, width), unit_hw=unit_hw, **pipe_kwargs)
     u8 = units_to_u8(images)
     frames = None
+    scores = None
+
+    def blend(unit_u8, us):
+        nonlocal scores
+        dev = _blend_frame_tensors(unit_u8, us, height, width, overlap)
+        if score:
+            scores = score_frames(dev, source)
+        return {f: t.cpu().numpy() for f, t in dev.items()}
+
     if gather and world > 1:
         allimg = gather_units(u8, units, rank, world, shard_mode, dst=0)
         if rank == 0:
-            frames = blend_frames(allimg, units, height, width, overlap)
+            frames = blend(allimg, units)
     else:
         per_frame = {}
         for u in units:
@@ -278,5 +340,12 @@ def decode_clip(pipe, source, num_frames, gop_size, height, width, prompt_embeds
             have[u.frame] = have.get(u.frame, 0) + 1
         complete = [k for k, u in enumerate(mine) if have[u.frame] == per_frame[u.frame]]
         if complete:
-            frames = blend_frames(u8[complete], [mine[k] for k in complete], height, width, overlap)
-    return dict(units=units, mine=mine, images=images, frames=frames)
+            frames = blend(u8[complete], [mine[k] for k in complete])
+        if score and world > 1 and torch.distributed.is_available() and torch.distributed.is_initialized():
+            merged = gather_scores(scores or {}, units, rank, world, dst=0)
+            if rank == 0:
+                scores = merged
+    out = dict(units=units, mine=mine, images=images, frames=frames)
+    if score:
+        out["scores"] = scores if scores is not None else {}
+    return out

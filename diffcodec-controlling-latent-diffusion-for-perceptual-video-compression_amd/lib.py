@@ -4,12 +4,12 @@ The product path has no CPU fallback: if the shared object is missing or a launc
 module raises.  (Loading the library and resolving symbols needs no GPU; launching does.)"""
 import ctypes
 import os
-from ctypes import POINTER, c_float, c_int, c_longlong, c_void_p
+from ctypes import POINTER, c_double, c_float, c_int, c_longlong, c_void_p
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libdiffcodec_hip.so")
 
-vp, i32, i64, f32 = c_void_p, c_int, c_longlong, c_float
+vp, i32, i64, f32, f64 = c_void_p, c_int, c_longlong, c_float, c_double
 
 
 class ConvDesc(ctypes.Structure):
@@ -76,6 +76,11 @@ SIGNATURES = {
     "dc_flow_hw2_resize_scale_f32": [vp, i32, i32, vp, i32, i32, vp],
     "dc_pack_sixch_u8_f32": [vp, vp, vp, i32, i32, vp],
     "dc_blend_tiles_ramp_u8": [vp, vp, i32, i32, i32, i32, vp, i32, vp, i32, i32, f32, vp],
+    "dc_ssim_ws_bytes": [i32, i32, i32, i32, i32, i32],
+    "dc_ms_ssim": [vp, vp, i32, POINTER(i64), i32, i32, i32, i32, POINTER(f32), i32, POINTER(f32), i32, f32, f32, f32, vp, vp, vp],
+    "dc_ssim": [vp, vp, i32, POINTER(i64), i32, i32, i32, i32, POINTER(f32), i32, f32, f32, f32, i32, vp, vp, vp],
+    "dc_psnr_ws_bytes": [i32],
+    "dc_psnr": [vp, vp, i32, POINTER(i64), i32, i32, i32, i32, f64, vp, vp, vp],
 }
 
 _lib = None
@@ -98,7 +103,7 @@ def load():
     for name, args in SIGNATURES.items():
         fn = getattr(lib, name)          # AttributeError if the symbol is missing
         fn.argtypes = args
-        fn.restype = c_longlong if name in ("dc_conv_igemm_ws_bytes", "dc_splat_ws_bytes") else c_int
+        fn.restype = c_longlong if name.endswith("_ws_bytes") else c_int
     lib.dc_gn_stats_chunks.restype = c_int
     _lib = lib
     return lib

@@ -265,6 +265,29 @@ int dc_pack_sixch_u8_f32(const uint8_t* img0_hw3, const uint8_t* img1_hw3, float
 int dc_blend_tiles_ramp_u8(const float* tiles_nchw, const int* coords_dev, int T, int C, int th, int tw,
                            const float* ramp_dev, int feather, uint8_t* out_hwc, int H, int W, float scale, void* stream);
 
+/* ------------------------------------------------------------------ frame quality metrics (validation.py:120-155, test_utils.py:23-55) */
+/* Operands: two logical [N][C][H][W] images, uint8 (x_u8 = 1: converted to fp32 on load) or fp32 (x_u8 = 0), read through element
+ * strides: strides[0..3] = X's (n, c, h, w) strides, strides[4..7] = Y's (host array), so NHWC frames and permuted views need no copy.
+ * Semantics of pytorch_msssim 1.0 (ms_ssim / ssim: Gaussian window applied as a valid separable correlation, C1 = (K1 L)^2,
+ * C2 = (K2 L)^2, avg_pool2d(2, padding = (H % 2, W % 2)) between scales), computed in fp32 with fp64 sums in a fixed order:
+ * bitwise reproducible, no float atomics.  win: host array of win_size (odd, <= 15) taps; weights: host array of `levels`
+ * (<= 8) exponents.  ws: scratch of dc_ssim_ws_bytes(...) bytes (any contents).  out (device, fp64) [N*C + N + 1]: the value per
+ * (n, c), its mean over c per n, the mean over (n, c).  Every scale must keep H, W >= win_size; dc_ssim_ws_bytes returns -1
+ * for a shape / window / level count the kernels do not take. */
+long long dc_ssim_ws_bytes(int N, int C, int H, int W, int win_size, int levels);
+int dc_ms_ssim(const void* x, const void* y, int x_u8, const long long* strides, int N, int C, int H, int W, const float* win,
+               int win_size, const float* weights, int levels, float K1, float K2, float data_range, void* ws, double* out,
+               void* stream);
+/* single-scale SSIM (levels = 1 in dc_ssim_ws_bytes); nonnegative = 1 applies relu to the per-(n, c) value (nonnegative_ssim) */
+int dc_ssim(const void* x, const void* y, int x_u8, const long long* strides, int N, int C, int H, int W, const float* win,
+            int win_size, float K1, float K2, float data_range, int nonnegative, void* ws, double* out, void* stream);
+/* PSNR per image: out (device, fp64) [N] = 10 log10(L^2 / mse) over the C*H*W elements of each image, +inf when mse = 0.  The
+ * squared differences are summed exactly in 64-bit integers for uint8, in fp64 in a fixed order for fp32.
+ * ws: dc_psnr_ws_bytes(N) bytes. */
+long long dc_psnr_ws_bytes(int N);
+int dc_psnr(const void* x, const void* y, int x_u8, const long long* strides, int N, int C, int H, int W, double data_range,
+            void* ws, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
