@@ -13,6 +13,7 @@
 #include "dc_common.h"
 #include "../../include/diffcodec_hip.h"
 #include <cstdlib>
+#include <type_traits>
 
 // Developer-only phase stamps (tools/attn_stamp.py builds this file with -DDC_STAMP into a scratch .so): per-wave s_memtime sums of
 // the QK^T + row-max phase, the exp + PV phase and the staging + barrier phase of the long-context loop.
@@ -689,41 +690,71 @@ int launch_qb_r(const AttnArgs& a, hipStream_t st)
     return dc_launch_status();
 }
 
-template <int D, int QB, bool SHORT>
-int launch_qb(const AttnArgs& a, hipStream_t st)
+// The form choice of dc_attention_bf16: (QB, SHORT, RAGGED, PP) of the attn_kernel instance it launches for a shape.  The
+// launcher and dc_attention_route both read it.
+struct AttnForm {
+    int qb;
+    bool shrt, ragged, pp;
+};
+
+AttnForm attn_form(int D, int B, int heads, int Nq, int Nk)
 {
-    if (SHORT || (a.Nk % KV_TILE) != 0) return launch_qb_r<D, QB, SHORT, true>(a, st);
-    return launch_qb_r<D, QB, SHORT, false>(a, st);
+    // two query blocks per wave only for the small heads (register budget) and only when that still leaves >= 2 workgroups per CU
+    static const int force_qb = DC_KNOB("DC_ATTN_QB", 0);      // developer knob
+    static const int no_short = DC_KNOB("DC_ATTN_NO_SHORT", 0);   // developer knob (A/B)
+    static const int force_pp = DC_KNOB("DC_ATTN_PP", -1);     // developer A/B knob (DC_ATTN_PP=0/1)
+    // short context (text cross-attention): keys resident, several query blocks per workgroup — when enough workgroups remain
+    const bool short_ctx = !no_short && Nk <= 2 * KV_TILE;
+    // the key-masking code exists only where the last key tile is ragged (always in the short form)
+    const bool ragged = (Nk % KV_TILE) != 0;
+    if (D <= 48) {                    // d = 80 spills at two blocks per wave (measured slower)
+        const long long wgs2 = (long long)B * heads * ((Nq + 255) / 256);
+        if (force_qb == 2 || (force_qb == 0 && wgs2 >= 512)) {
+            // short context: one query block per wave when that still fills the chip (measured at 32 x 8 x 4096 x 77, d = 40: 63 us
+            // against 70-73 us for two blocks per wave — the keys are resident either way, and the smaller workgroup tail wins)
+            if (short_ctx && force_qb == 0 && (long long)B * heads * ((Nq + 127) / 128) / SHORT_PASSES >= 512) return {1, true, true, false};
+            if (short_ctx && wgs2 / SHORT_PASSES >= 512) return {2, true, true, false};
+            // long context with at least one 8-wave workgroup per CU: the ping-pong form
+            const long long wgs_pp = (long long)B * heads * ((Nq + 511) / 512);
+            if (!short_ctx && (force_pp == 1 || (force_pp < 0 && wgs_pp >= 256 && Nk >= 4 * KV_TILE))) return {2, false, ragged, true};
+            return {2, false, ragged, false};
+        }
+    }
+    const long long wgs1 = (long long)B * heads * ((Nq + 127) / 128);
+    if (short_ctx && wgs1 / SHORT_PASSES >= 512) return {1, true, true, false};
+    return {1, false, ragged, false};
 }
 
 template <int D>
 int launch(const AttnArgs& a, hipStream_t st)
 {
-    // two query blocks per wave only for the small heads (register budget) and only when that still leaves >= 2 workgroups per CU
-    static const int force_qb = DC_KNOB("DC_ATTN_QB", 0);      // developer knob
-    static const int no_short = DC_KNOB("DC_ATTN_NO_SHORT", 0);   // developer knob (A/B)
-    // short context (text cross-attention): keys resident, several query blocks per workgroup — when enough workgroups remain
-    const bool short_ctx = !no_short && a.Nk <= 2 * KV_TILE;
-    if constexpr (D <= 48) {          // d = 80 spills at two blocks per wave (measured slower)
-        const long long wgs2 = (long long)a.B * a.heads * ((a.Nq + 255) / 256);
-        if (force_qb == 2 || (force_qb == 0 && wgs2 >= 512)) {
-            // short context: one query block per wave when that still fills the chip (measured at 32 x 8 x 4096 x 77, d = 40: 63 us
-            // against 70-73 us for two blocks per wave — the keys are resident either way, and the smaller workgroup tail wins)
-            if (short_ctx && force_qb == 0 && (long long)a.B * a.heads * ((a.Nq + 127) / 128) / SHORT_PASSES >= 512) return launch_qb<D, 1, true>(a, st);
-            if (short_ctx && wgs2 / SHORT_PASSES >= 512) return launch_qb<D, 2, true>(a, st);
-            // long context with at least one 8-wave workgroup per CU: the ping-pong form (DC_ATTN_PP=0/1: developer A/B knob)
-            static const int force_pp = DC_KNOB("DC_ATTN_PP", -1);
-            const long long wgs_pp = (long long)a.B * a.heads * ((a.Nq + 511) / 512);
-            if (!short_ctx && (force_pp == 1 || (force_pp < 0 && wgs_pp >= 256 && a.Nk >= 4 * KV_TILE))) {
-                if ((a.Nk % KV_TILE) != 0) return launch_qb_r<D, 2, false, true, true>(a, st);
-                return launch_qb_r<D, 2, false, false, true>(a, st);
-            }
-            return launch_qb<D, 2, false>(a, st);
+    const AttnForm f = attn_form(D, a.B, a.heads, a.Nq, a.Nk);
+    if constexpr (D <= 48) {
+        if (f.qb == 2) {
+            if (f.pp) return f.ragged ? launch_qb_r<D, 2, false, true, true>(a, st) : launch_qb_r<D, 2, false, false, true>(a, st);
+            if (f.shrt) return launch_qb_r<D, 2, true, true>(a, st);
+            return f.ragged ? launch_qb_r<D, 2, false, true>(a, st) : launch_qb_r<D, 2, false, false>(a, st);
         }
     }
-    const long long wgs1 = (long long)a.B * a.heads * ((a.Nq + 127) / 128);
-    if (short_ctx && wgs1 / SHORT_PASSES >= 512) return launch_qb<D, 1, true>(a, st);
-    return launch_qb<D, 1, false>(a, st);
+    if (f.shrt) return launch_qb_r<D, 1, true, true>(a, st);
+    return f.ragged ? launch_qb_r<D, 1, false, true>(a, st) : launch_qb_r<D, 1, false, false>(a, st);
+}
+
+// The head dims attn_kernel is built for: the one list both the launch and the route query dispatch through.
+template <class F>
+int with_head_dim(int D, F&& f)
+{
+    switch (D) {
+        case 8: return f(std::integral_constant<int, 8>{});
+        case 16: return f(std::integral_constant<int, 16>{});
+        case 32: return f(std::integral_constant<int, 32>{});
+        case 40: return f(std::integral_constant<int, 40>{});
+        case 64: return f(std::integral_constant<int, 64>{});
+        case 80: return f(std::integral_constant<int, 80>{});
+        case 128: return f(std::integral_constant<int, 128>{});
+        case 160: return f(std::integral_constant<int, 160>{});
+        default: return DC_ERR_INVALID;
+    }
 }
 
 // Row softmax fp32 -> bf16 (one workgroup per row; cols <= 65536).
@@ -760,17 +791,22 @@ extern "C" int dc_attention_bf16(const void* q, const void* k, const void* v, vo
     AttnArgs a{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)out, B, heads, Nq, Nk,
                q_stride, k_stride, v_stride, o_stride, scale * 1.4426950408889634f, DC_KNOB("DC_ATTN_XCD", 1)};
     hipStream_t st = (hipStream_t)stream;
-    switch (D) {
-        case 8: return launch<8>(a, st);
-        case 16: return launch<16>(a, st);
-        case 32: return launch<32>(a, st);
-        case 40: return launch<40>(a, st);
-        case 64: return launch<64>(a, st);
-        case 80: return launch<80>(a, st);
-        case 128: return launch<128>(a, st);
-        case 160: return launch<160>(a, st);
-        default: return DC_ERR_INVALID;
-    }
+    return with_head_dim(D, [&](auto dc) { return launch<decltype(dc)::value>(a, st); });
+}
+
+extern "C" int dc_attention_route(int B, int heads, int Nq, int Nk, int D, int* info)
+{
+    if (!info) return DC_ERR_INVALID;
+    for (int i = 0; i < DC_ATTN_ROUTE_INFO_INTS; ++i) info[i] = 0;
+    if (B <= 0 || heads <= 0 || Nq <= 0 || Nk <= 0) return DC_ERR_INVALID;
+    if (with_head_dim(D, [](auto) { return (int)DC_OK; }) != DC_OK) return DC_ERR_INVALID;
+    const AttnForm f = attn_form(D, B, heads, Nq, Nk);
+    info[0] = D;
+    info[1] = f.qb;
+    info[2] = f.shrt;
+    info[3] = f.ragged;
+    info[4] = f.pp;
+    return DC_OK;
 }
 
 extern "C" int dc_softmax_rows_f32_to_bf16(const float* s, void* p, long long rows, int cols, float scale, void* stream)

@@ -462,6 +462,26 @@ def attention(q, k, v, heads, scale=None, out=None):
     return out
 
 
+class AttentionRoute(tuple):
+    """(D, QB, SHORT, RAGGED, PP): the attn_kernel<D, QB, SHORT, RAGGED, PP> instance dc_attention_bf16 launches for a shape."""
+    __slots__ = ()
+    d = property(lambda s: s[0])
+    qb = property(lambda s: s[1])
+    short = property(lambda s: bool(s[2]))
+    ragged = property(lambda s: bool(s[3]))
+    pp = property(lambda s: bool(s[4]))
+
+
+def attention_route(b, heads, nq, nk, d):
+    """The form `attention` launches for B x heads x Nq x Nk at head dim d, without launching (host code only: needs the library,
+    not a GPU).  Raises HipLaunchError for a shape the launch would refuse."""
+    info = (ctypes.c_int * 5)()
+    rc = lib.load().dc_attention_route(int(b), int(heads), int(nq), int(nk), int(d), info)
+    if rc != 0:
+        raise lib.HipLaunchError(f"dc_attention_route returned {rc} (invalid argument)")
+    return AttentionRoute(tuple(info))
+
+
 def attention_causal(q, k, v, heads, scale=None):
     """Causal self-attention over a short context (CLIP text, T <= 128): same operand convention as `attention`."""
     b, t, c = q.shape

@@ -199,6 +199,12 @@ int dc_layernorm_bf16(const void* x, const float* gamma, const float* beta, void
 int dc_attention_bf16(const void* q, const void* k, const void* v, void* out, int B, int heads, int Nq, int Nk, int D,
                       long long q_stride, long long k_stride, long long v_stride, long long o_stride, float scale,
                       void* stream);
+/* The form dc_attention_bf16 launches for a shape, without launching anything (host code; reads the same developer knobs).
+ * Returns 0, or DC_ERR_INVALID for a shape the launch would refuse, and fills info[DC_ATTN_ROUTE_INFO_INTS] with the template
+ * arguments of the attn_kernel<D, QB, SHORT, RAGGED, PP> instance: head dim, 32-query blocks per wave, short-context form (both
+ * key tiles resident), ragged last key tile (key masking compiled in), ping-pong form. */
+#define DC_ATTN_ROUTE_INFO_INTS 5
+int dc_attention_route(int B, int heads, int Nq, int Nk, int D, int* info);
 /* Causal softmax(Q K^T * scale) V over a short context (T <= 128, D <= 128): CLIPTextModel self-attention behind
  * `encode_prompt` (pipeline.py:223-236).  Same operand layout as dc_attention_bf16; key j is visible to query i iff j <= i. */
 int dc_attention_causal_small_bf16(const void* q, const void* k, const void* v, void* out, int B, int heads, int T, int D,

@@ -1,0 +1,579 @@
+"""Edge-case tables of the conv / linear, attention and normalisation launches, their instance keys, and guarded buffers.
+
+Plain module (imported by tests/test_edge_coverage.py on the CPU and tests/test_gpu_edges.py on the GPU, as launch_shadow.py is):
+
+* `Guarded`: a tensor view inside a larger allocation whose guard elements (before, after, and in the gap between rows of a
+  pitched view) hold a NaN with a distinctive payload.  An output view is pre-filled with the same pattern, so an element the
+  kernel never writes stays non-finite (L.check treats it as infinitely wrong); `bad()` lists every guard element that no longer
+  holds the pattern, compared as integers.
+* `conv_key` / `attention_key`: the kernel instance a launch runs, from the dispatcher's own route query (dc_conv_route,
+  dc_attention_route) refined by the descriptor flags that pick a different template inside the launchers.
+* `CONV_CASES`, `ATTN_CASES`, `NORM_CASES`: the tables.  Every conv / attention case declares the instance it targets;
+  tests/test_edge_coverage.py proves that every instance the dispatcher can reach has a case and that every case routes where it
+  says."""
+import math
+from dataclasses import dataclass
+
+import torch
+
+GUARD = 256                                   # guard elements on each side of a view
+NAN_BITS = {torch.bfloat16: 0x7FA5, torch.float32: 0x7FA5A5A5}
+_INT = {torch.bfloat16: torch.int16, torch.float32: torch.int32}
+
+
+# ------------------------------------------------------------------------------------------ guarded buffers
+class Guarded:
+    """`view` = contiguous `shape` (or rows of `pitch` elements, the last dim using the first shape[-1] of them) inside one
+    allocation of GUARD + rows * pitch + GUARD elements, everything filled with the NaN pattern.  `fill(t)` copies data into the
+    view (operands); outputs are left holding the pattern."""
+
+    def __init__(self, shape, dtype, device, pitch=None, guard=GUARD):
+        self.shape, self.dtype = tuple(shape), dtype
+        cols = self.shape[-1]
+        rows = math.prod(self.shape[:-1])
+        self.pitch = cols if pitch is None else pitch
+        assert self.pitch >= cols
+        self.guard = guard
+        n = guard + rows * self.pitch + guard
+        self.base = torch.empty(n, dtype=dtype, device=device)
+        self.base.view(_INT[dtype]).fill_(_signed(NAN_BITS[dtype], dtype))
+        # batch stride implied by the rows (a [B, N, C] view with row pitch p has batch stride N * p)
+        strides = []
+        acc = self.pitch
+        for d in reversed(self.shape[:-1]):
+            strides.append(acc)
+            acc *= d
+        strides = tuple(reversed(strides)) + (1,)
+        self.view = torch.as_strided(self.base, self.shape, strides, guard)
+        self.mask = torch.ones(n, dtype=torch.bool, device=device)             # True: a guard element
+        idx = torch.as_strided(torch.arange(n, device=device), self.shape, strides, guard)
+        self.mask[idx.reshape(-1)] = False
+
+    def fill(self, t):
+        self.view.copy_(t)
+        return self.view
+
+    def bad(self):
+        """-> list of (where, element index) of guard elements that no longer hold the pattern: 'before', 'after' or 'gap'."""
+        bits = self.base.view(_INT[self.dtype])
+        wrong = (bits != _signed(NAN_BITS[self.dtype], self.dtype)) & self.mask
+        out = []
+        for i in torch.nonzero(wrong).reshape(-1)[:8].tolist():
+            out.append(("before" if i < self.guard else "after" if i >= self.base.numel() - self.guard else "gap", i - self.guard))
+        return out
+
+    def assert_intact(self, name):
+        b = self.bad()
+        assert not b, f"{name}: guard elements overwritten (where, offset from the view's first element): {b}"
+
+    def unwritten(self):
+        """number of view elements that still hold the exact pattern (an output element the kernel never wrote)"""
+        return int((self.view.contiguous().view(_INT[self.dtype]) == _signed(NAN_BITS[self.dtype], self.dtype)).sum())
+
+
+def _signed(bits, dtype):
+    w = 16 if dtype == torch.bfloat16 else 32
+    return bits - (1 << w) if bits >= 1 << (w - 1) else bits
+
+
+# ------------------------------------------------------------------------------------------ conv / linear instances
+@dataclass(frozen=True)
+class ConvCase:
+    """One ops.conv launch.  ln: None | 'pairs' (finalized (mean, rstd)) | number of raw partials per row (ln_partials)."""
+    key: tuple
+    n: int
+    h: int
+    w: int
+    c1: int
+    cout: int
+    k: int = 1
+    c2: int = 0
+    stride: int = 1
+    pad: int = 1
+    up: bool = False
+    gn: bool = False
+    gn_silu: bool = False
+    row_add: bool = False
+    residual: bool = False
+    act: int = 0
+    out_f32: bool = False
+    out_scale: float = 1.0
+    geglu: bool = False
+    ln: object = None
+    stats_out: bool = False
+    gn_part: bool = False
+    splitk: int = 1
+    note: str = ""
+
+    @property
+    def ho(self):
+        if self.k == 1:
+            return self.h
+        hin = 2 * self.h if self.up else self.h
+        return (hin + (2 if self.pad else 1) - 3) // self.stride + 1
+
+    @property
+    def wo(self):
+        if self.k == 1:
+            return self.w
+        win = 2 * self.w if self.up else self.w
+        return (win + (2 if self.pad else 1) - 3) // self.stride + 1
+
+    @property
+    def m(self):
+        return self.n * self.ho * self.wo
+
+    def label(self):
+        f = [n for n in ("gn", "gn_silu", "row_add", "residual", "out_f32", "geglu", "stats_out", "gn_part", "up") if getattr(self, n)]
+        f += [f"act={self.act}"] if self.act else []
+        f += [f"ln={self.ln}"] if self.ln is not None else []
+        f += [f"out_scale={self.out_scale}"] if self.out_scale != 1.0 else []
+        f += [f"splitk={self.splitk}"] if self.splitk != 1 else []
+        return (f"{self.n}x{self.h}x{self.w}x({self.c1}+{self.c2})->{self.cout} k{self.k}s{self.stride}p{self.pad} "
+                f"M={self.m} [{','.join(f)}]")
+
+
+def case_desc(c):
+    """The dc_conv_desc ops.conv builds for case `c` (dummy non-null pointers: the route query reads flags, not memory)."""
+    from diffcodec_amd import lib
+    from diffcodec_amd.lib import ConvDesc
+    P = 16
+    ln_parts = c.ln if isinstance(c.ln, int) else 0
+    splitk = 1 if (c.ln is not None or c.stats_out) else c.splitk
+    d = ConvDesc(x1=P, x2=P if c.c2 else 0, w=P, bias=P, gn_ab=P if c.gn else 0, row_add=P if c.row_add else 0,
+                 residual=P if c.residual else 0, out=P, splitk_ws=P if splitk > 1 else 0, N=c.n, H=c.h, W=c.w, C1=c.c1, C2=c.c2,
+                 Cout=c.cout, ksize=c.k, stride=c.stride, pad=int(c.pad), upsample=int(c.up), Ho=c.ho, Wo=c.wo,
+                 gn_silu=int(c.gn_silu), epilogue=1 if c.geglu else 0, out_f32=int(c.out_f32), out_scale=float(c.out_scale),
+                 splitk=int(splitk), gn_batch=c.n if c.gn else 0, act=int(c.act), row_add_stride=0,
+                 ln_stats=P if c.ln is not None else 0, ln_colsum=P if c.ln is not None else 0, stats_out=P if c.stats_out else 0,
+                 gn_part_out=0, ln_parts=ln_parts, ln_eps=1e-5 if ln_parts else 0.0, ln_scratch=0)
+    if c.gn_part and not c.out_f32 and not c.geglu and splitk == 1 and c.ln is None:
+        if lib.load().dc_conv_gn_part_chunks(d) > 0:
+            d.gn_part_out = P
+    return d
+
+
+def conv_key(d, route=None):
+    """Instance key of a dc_conv_desc: (kernel, variant, epi, split-K > 1, ln_first) from dc_conv_route, refined by the flags that
+    select another template in the launchers:
+      conv3x3_tile  GroupNorm on load, fused upsample, narrow map (Wo < 16), and the (TN, NSTB, FAST) template arguments
+                    dc_conv3x3_tile_launch picks (`_tile_template`);
+      gemm_rowpanel GroupNorm partials out (GN template flag);
+      gemm_wide     statistics template ST (stats_out | gn_part_out) of the epi 1 / 2 kernels, and TN (160- or 128-column tile);
+      igemm         3x3 gather, GroupNorm on load."""
+    from diffcodec_amd import ops
+    r = ops.conv_route(d) if route is None else route
+    key = (r.kernel, r.variant, r.epi, r.splitk > 1, r.ln_first)
+    if r.kernel == "conv3x3_tile":
+        tn, nst, fast = _tile_template(d, r.variant, r.splitk)
+        key += (("gn", bool(d.gn_ab)), ("up", bool(d.upsample)), ("narrow", d.Wo < 16), ("tn", tn), ("nst", nst), ("fast", fast))
+    elif r.kernel == "gemm_rowpanel":
+        key += (("gn_part", bool(d.gn_part_out)),)
+    elif r.kernel == "gemm_wide":
+        key += (("st", (1 if d.stats_out else 0) | (2 if d.gn_part_out else 0) if r.epi in (1, 2) else 0),
+                ("tn", 5 if r.epi < 4 and d.Cout % 160 == 0 else 4))
+    elif r.kernel == "igemm":
+        key += (("k3", d.ksize == 3), ("gn", bool(d.gn_ab)))
+    return key
+
+
+def _tile_template(d, variant, splitk):
+    """(TN, NSTB, FAST) of the launch_tile<TM, TN, NSTB, FAST, UPS, SH> instance dc_conv3x3_tile_launch (conv3x3_tile.hip) takes for
+    a descriptor of tile variant `variant` (TM = 2 for variant 2, else 4; UPS / SH = fused upsample / narrow map without GroupNorm)."""
+    tn = 5 if d.Cout % 160 == 0 else 4
+    if not d.upsample and d.Wo >= 16 and d.Cout % 8 == 0:             # plain maps: half-step pipeline
+        th, bn = (8 if variant == 4 else 4), (160 if tn == 5 else 128)
+        wgs = d.N * (d.Ho // th) * (d.Wo // 16) * -(-d.Cout // bn) * splitk
+        if d.Cout <= 32:
+            return 1, 2, True
+        return tn, (4 if wgs <= 256 else 2), True
+    if d.Cout % 8 == 0 and not d.gn_ab and ((d.upsample and d.Wo >= 16) or (d.Wo == 8 and not d.upsample)):
+        return tn, 2, True
+    if d.Cout <= 32 and variant != 8:
+        return 1, 3, False
+    if variant in (4, 8):
+        return (5, 2, False) if tn == 5 else (4, 3, False)
+    return tn, 3, False
+
+
+def key_str(key):
+    return "/".join(f"{k[0]}={int(k[1]) if isinstance(k[1], bool) else k[1]}" if isinstance(k, tuple) else str(k) for k in key)
+
+
+def enumerate_conv_keys():
+    """Every instance key dc_conv_route yields over a descriptor grid that spans each routing flag: 1x1 shapes in the regime of
+    each GEMM kernel x every epilogue / statistics / LayerNorm / split-K option, and 3x3 shapes (tile-aligned, narrow 8x8, odd,
+    strided, upsampled, Cout <= 32) x GroupNorm on load, concat, epilogue and split-K options.  -> {key: example descriptor label}"""
+    from diffcodec_amd import lib
+    keys = {}
+
+    def add(c):
+        d = case_desc(c)
+        try:
+            k = conv_key(d)
+        except lib.HipLaunchError:
+            return
+        keys.setdefault(k, c.label())
+
+    # 1x1 / linear regimes: small M (64-row deep ring), mid M (128-row tiles), the wide / p8 grids, the row-panel K = 320 panels
+    shapes11 = [(1, 1, 77, 640, 640), (1, 1, 333, 320, 1280), (1, 1, 4096, 640, 640), (1, 1, 4096, 1280, 1280),
+                (1, 1, 16384, 640, 1920), (1, 1, 15104, 640, 1920), (1, 1, 8192, 1280, 1280), (1, 1, 8192, 1280, 1024), (1, 1, 8192, 1280, 5120), (1, 1, 65536, 320, 320),
+                (1, 1, 65536, 320, 1280), (4, 16, 16, 1280, 1280), (16, 64, 64, 320, 320), (1, 1, 64, 64, 48)]
+    for (n, h, w, cin, cout) in shapes11:
+        for geglu in (False, True):
+            if geglu and cout % 32:
+                continue
+            for ln in (None, "pairs", 4, 20):
+                for res, ra, act, f32, so, gp, gn, sk in _epi_grid(geglu):
+                    add(ConvCase(None, n, h, w, cin, (2 * cout if geglu else cout), geglu=geglu, ln=ln, residual=res, row_add=ra,
+                                 act=act, out_f32=f32, stats_out=so, gn_part=gp, gn=gn, splitk=sk))
+    # 3x3 maps: 8-row / 4-row tiles, two 8x8 images per tile, narrow 8x8, odd (gather), strided, upsampled
+    shapes33 = [(2, 16, 16, 64, 64), (3, 16, 32, 320, 320), (40, 12, 32, 320, 320), (40, 12, 32, 128, 144), (40, 32, 32, 320, 320),
+                (80, 32, 32, 128, 128), (1, 8, 8, 320, 320), (2, 8, 8, 128, 128), (512, 8, 8, 320, 320), (1024, 8, 8, 128, 128),
+                (1, 13, 9, 64, 48), (2, 16, 16, 320, 4), (2, 8, 8, 128, 16), (2, 16, 16, 128, 16), (3, 12, 32, 128, 144)]
+    for (n, h, w, cin, cout) in shapes33:
+        for up in (False, True):
+            for stride, pad in ((1, 1), (2, 1), (2, 0)):
+                if up and stride != 1:
+                    continue
+                for gn, silu in ((False, False), (True, False), (True, True)):
+                    for res, act, f32, sk in ((False, 0, False, 1), (True, 0, False, 1), (False, 1, False, 1), (False, 0, True, 1),
+                                              (False, 0, False, 2)):
+                        for c2 in (0, 64):
+                            add(ConvCase(None, n, h, w, cin - c2, cout, k=3, c2=c2, stride=stride, pad=pad, up=up, gn=gn,
+                                         gn_silu=silu, residual=res, act=act, out_f32=f32, splitk=sk, gn_part=True))
+                            add(ConvCase(None, n, h, w, cin - c2, cout, k=3, c2=c2, stride=stride, pad=pad, up=up, gn=gn,
+                                         gn_silu=silu, residual=res, act=act, out_f32=f32, splitk=sk))
+    return keys
+
+
+def _epi_grid(geglu):
+    """(residual, row_add, act, out_f32, stats_out, gn_part, gn, splitk) options of a 1x1 launch"""
+    out = []
+    for res in (False, True):
+        for ra in (False, True):
+            for act in (0, 1):
+                for f32 in (False, True):
+                    for so in (False, True):
+                        for gp in (False, True):
+                            for gn in (False, True):
+                                for sk in (1, 3):
+                                    out.append((res, ra, act, f32, so, gp, gn, sk))
+    return out
+
+
+
+
+def _k(kernel, variant, epi, split=False, ln_first=False, **extra):
+    key = (kernel, variant, epi, split, ln_first)
+    if kernel == "conv3x3_tile":
+        key += tuple((n, extra[n]) for n in ("gn", "up", "narrow", "tn", "nst", "fast"))
+    elif kernel == "gemm_rowpanel":
+        key += (("gn_part", extra.get("gn_part", False)),)
+    elif kernel == "gemm_wide":
+        key += (("st", extra.get("st", 0)), ("tn", extra.get("tn", 5)))
+    elif kernel == "igemm":
+        key += (("k3", extra.get("k3", False)), ("gn", extra.get("gn", False)))
+    return key
+
+
+# Epilogue flag sets of the 1x1 family and the specialised epilogue mode each one declares (epi_mode in gemm_dma.hip: 1 plain,
+# 2 residual, 3 folded LayerNorm, 4 GEGLU, 5 GEGLU + LayerNorm, 0 the generic run-time flags); 'lf' = the LayerNorm finalize runs
+# first (raw partials on a kernel whose waves do not own whole rows), 'sk' = split-K.
+_PLAIN = [(dict(), 1, {}), (dict(residual=True, out_scale=0.5), 2, {}), (dict(ln="pairs"), 3, {}), (dict(ln=4), 3, dict(lf=1)),
+          (dict(out_f32=True, out_scale=0.25), 0, {}), (dict(row_add=True, act=1), 0, {}), (dict(act=2, residual=True), 0, {}),
+          (dict(stats_out=True, ln=4), 0, dict(lf=1)), (dict(splitk=3), 0, dict(sk=1))]
+_GEGLU = [(dict(geglu=True), 4, {}), (dict(geglu=True, ln="pairs"), 5, {}), (dict(geglu=True, ln=4), 5, dict(lf=1)),
+          (dict(geglu=True, act=1), 0, {}), (dict(geglu=True, act=1, ln=20), 0, dict(lf=1))]
+
+
+def _family(kernel, variant, shape, sets, skip=(), **extra):
+    n, h, w, cin, cout = shape
+    out = []
+    for i, (flags, epi, o) in enumerate(sets):
+        if i in skip:
+            continue
+        c_out = 2 * cout if flags.get("geglu") else cout
+        out.append(ConvCase(_k(kernel, variant, epi, bool(o.get("sk")), bool(o.get("lf")), **extra), n, h, w, cin, c_out, **flags))
+    return out
+
+
+def _tile(variant, shape, tn, ring=2, fast=True, gn_tpl=None, split_ring=None, narrow=False, gn_opts=(False, True), up=False,
+          splits=True, c2=0, **kw):
+    """conv3x3_tile cases of one map shape: the plain / residual / generic epilogues, with and without GroupNorm on load, split-K.
+    Declared template: (tn, ring, fast) without GroupNorm, gn_tpl (default the same) with it; split_ring = the ring of the split-K
+    launch when its larger grid changes it."""
+    n, h, w, cin, cout = shape
+    out = []
+    for gn in gn_opts:
+        t_tn, t_ring, t_fast = (gn_tpl or (tn, ring, fast)) if gn else (tn, ring, fast)
+        ex = dict(gn=gn, up=up, narrow=narrow, tn=t_tn, nst=t_ring, fast=t_fast)
+        base = dict(k=3, up=up, gn=gn, gn_silu=gn, c2=c2, **kw)
+        out.append(ConvCase(_k("conv3x3_tile", variant, 1, **ex), n, h, w, cin - c2, cout, gn_part=True, **base))
+        out.append(ConvCase(_k("conv3x3_tile", variant, 2, **ex), n, h, w, cin - c2, cout, residual=True, **base))
+        out.append(ConvCase(_k("conv3x3_tile", variant, 0, **ex), n, h, w, cin - c2, cout, act=1, out_scale=0.5, **base))
+        if splits:
+            exs = dict(ex, nst=split_ring if (split_ring is not None and t_fast and not up and not narrow) else t_ring)
+            out.append(ConvCase(_k("conv3x3_tile", variant, 0, True, **exs), n, h, w, cin - c2, cout, splitk=2, **base))
+    return out
+
+
+CONV_CASES = (
+    # ---------------------------------------------------------------- gemm_dma: the LDS-DMA GEMM's four production tiles
+    # 64-row tiles, 2 stages (K = 320: too short for the deep ring), Cout 1280 = 8 x 160; M = 333: 5 full + 1 ragged row tile
+    _family("gemm_dma", 25201, (1, 1, 333, 320, 1280), _PLAIN)
+    # 64-row tiles, deep 4-stage ring (K = 640, one workgroup per CU): M = 77 (the text context), 4 x 160 columns
+    + _family("gemm_dma", 25401, (1, 1, 77, 640, 640), _PLAIN)
+    # 128-row tiles: M = 4099 (ragged last tile), N = 1280
+    + _family("gemm_dma", 45201, (1, 1, 4099, 1280, 1280), _PLAIN)
+    # 64-row 128-column tile (Cout not a multiple of 160): Cout = 48 (one ragged N tile), K = 64 (a single K step), M = 65
+    + _family("gemm_dma", 24301, (1, 1, 65, 64, 48), _PLAIN, skip=(8,))
+    + _family("gemm_dma", 24301, (1, 1, 333, 320, 1280), _GEGLU)
+    + _family("gemm_dma", 24501, (1, 1, 77, 640, 640), _GEGLU)
+    + _family("gemm_dma", 44201, (1, 1, 4097, 640, 640), _GEGLU)
+    + [ConvCase(_k("gemm_dma", 45201, 0, True), 3, 1, 1365, 640, 640, splitk=7, note="split 7 over 10 K steps -> fixpoint 5"),
+       ConvCase(_k("gemm_dma", 24301, 1), 1, 1, 65, 64, 144, note="Cout = 144: one full and one ragged 128-column tile"),
+       ConvCase(_k("gemm_dma", 25401, 1), 1, 1, 77, 320, 640, c2=320, note="x2 concat"),
+       ConvCase(_k("gemm_dma", 45201, 1), 3, 1, 1367, 640, 1280, c2=640, note="x2 concat, odd N")]
+    # ---------------------------------------------------------------- gemm_wide: 256-row tiles, K in [640, 2560], >= 192 tiles
+    + [ConvCase(_k("gemm_wide", 0, 1, st=s), 1, 1, 16384, 640, 1920, stats_out=bool(s & 1), gn_part=bool(s & 2)) for s in (1, 3)]
+    + [ConvCase(_k("gemm_wide", 0, 1, st=2), 64, 16, 16, 640, 1920, gn_part=True)]
+    + [ConvCase(_k("gemm_wide", 0, 2, st=s), 64, 16, 16, 640, 1920, residual=True, stats_out=bool(s & 1), gn_part=bool(s & 2))
+       for s in (0, 1, 2, 3)]
+    + [ConvCase(_k("gemm_wide", 0, 1, tn=4), 1, 1, 8192, 1280, 1024, note="128-column tiles"),
+       ConvCase(_k("gemm_wide", 0, 2, tn=4), 1, 1, 8192, 1280, 1024, residual=True),
+       ConvCase(_k("gemm_wide", 0, 3, tn=4), 1, 1, 8192, 1280, 1024, ln="pairs"),
+       ConvCase(_k("gemm_wide", 0, 3, ln_first=True, tn=4), 1, 1, 8192, 1280, 1024, ln=4),
+       ConvCase(_k("gemm_dma", 44201, 0, True), 1, 1, 8193, 1280, 1024, splitk=3),
+       ConvCase(_k("igemm", 44, 0, True, gn=True), 1, 1, 8193, 1280, 1024, gn=True, splitk=3)]
+    + [ConvCase(_k("gemm_wide", 0, e, st=st, tn=4), 32, 16, 16, 1280, 1024, residual=e == 2, stats_out=bool(st & 1),
+                gn_part=bool(st & 2)) for e in (1, 2) for st in (1, 2, 3)]
+    + [ConvCase(_k("gemm_wide", 0, 1), 1, 1, 8192, 1280, 1280, note="too few tiles for the 256 x 256 kernel"),
+       ConvCase(_k("gemm_wide", 0, 3), 1, 1, 8192, 1280, 1280, ln="pairs"),
+       ConvCase(_k("gemm_wide", 0, 3, ln_first=True), 1, 1, 8192, 1280, 1280, ln=4)]
+    + [ConvCase(_k("gemm_wide", 0, 4, tn=4), 1, 1, 4096, 1280, 2 * 1280, geglu=True),
+       ConvCase(_k("gemm_wide", 0, 5, tn=4), 1, 1, 4096, 1280, 2 * 1280, geglu=True, ln="pairs"),
+       ConvCase(_k("gemm_wide", 0, 5, ln_first=True, tn=4), 1, 1, 4096, 1280, 2 * 1280, geglu=True, ln=20)]
+    # ---------------------------------------------------------------- gemm_p8: 256 x 256 tiles; 15104 = 59 row tiles (not a
+    # multiple of gm = 8) with a half-full last column tile (1920 = 7.5 x 256)
+    + [ConvCase(_k("gemm_p8", 0, 1), 1, 1, 15104, 640, 1920, note="round-4 advice shape"),
+       ConvCase(_k("gemm_p8", 0, 3), 1, 1, 15104, 640, 1920, ln="pairs"),
+       ConvCase(_k("gemm_p8", 0, 3, ln_first=True), 1, 1, 15104, 640, 1920, ln=20),
+       ConvCase(_k("gemm_p8", 0, 4), 1, 1, 15104, 640, 2 * 1920, geglu=True),
+       ConvCase(_k("gemm_p8", 0, 5), 1, 1, 15104, 640, 2 * 1920, geglu=True, ln="pairs"),
+       ConvCase(_k("gemm_p8", 0, 5, ln_first=True), 1, 1, 15104, 640, 2 * 1920, geglu=True, ln=4)]
+    # ---------------------------------------------------------------- gemm_rowpanel: K = 320, M >= 65536, 256-row panels
+    + [ConvCase(_k("gemm_rowpanel", 0, 1), 1, 1, 65536, 320, 320),
+       ConvCase(_k("gemm_rowpanel", 0, 1, gn_part=True), 16, 64, 64 + 4, 320, 320, gn_part=True, note="M = 65536 + 256 x 17"),
+       ConvCase(_k("gemm_rowpanel", 0, 1), 16, 64, 64, 320, 320, gn=True, note="GroupNorm affine on load"),
+       ConvCase(_k("gemm_rowpanel", 0, 2), 1, 1, 65536 + 256, 320, 640, residual=True, out_scale=0.5),
+       ConvCase(_k("gemm_rowpanel", 0, 2, gn_part=True), 16, 64, 64, 320, 320, residual=True, gn_part=True),
+       ConvCase(_k("gemm_rowpanel", 0, 3), 1, 1, 65536, 320, 320, ln="pairs"),
+       ConvCase(_k("gemm_rowpanel", 0, 3), 1, 1, 65536 + 256, 320, 320, ln=16, note="raw partials = DC_LN_PARTS_MAX"),
+       ConvCase(_k("gemm_rowpanel", 0, 3, ln_first=True), 1, 1, 65536, 320, 320, ln=20, note="raw partials > DC_LN_PARTS_MAX"),
+       ConvCase(_k("gemm_rowpanel", 0, 4), 1, 1, 65536, 320, 2 * 640, geglu=True),
+       ConvCase(_k("gemm_rowpanel", 0, 5), 1, 1, 65536 + 256, 320, 2 * 640, geglu=True, ln=4),
+       ConvCase(_k("gemm_rowpanel", 0, 5, ln_first=True), 1, 1, 65536, 320, 2 * 640, geglu=True, ln=20)]
+    # ---------------------------------------------------------------- igemm: the gather GEMM (strided / odd 3x3 maps, GN on load)
+    + [ConvCase(_k("igemm", 24, 0, k3=True), 3, 13, 9, 64, 48, k=3, note="odd map, Cout 48"),
+       ConvCase(_k("igemm", 24, 0, k3=True), 3, 15, 17, 128, 144, k=3, stride=2, pad=1, note="stride 2, pad 1, odd map"),
+       ConvCase(_k("igemm", 24, 0, k3=True), 1, 15, 17, 64, 64, k=3, stride=2, pad=0, note="stride 2, pad 0 (F.pad right / bottom)"),
+       ConvCase(_k("igemm", 24, 0, k3=True), 2, 7, 5, 64, 128, k=3, up=True, note="upsample of an odd map"),
+       ConvCase(_k("igemm", 24, 0, k3=True), 2, 13, 9, 64, 48, k=3, c2=128, residual=True, note="x2 concat C1 != C2"),
+       ConvCase(_k("igemm", 24, 0, k3=True, gn=True), 3, 13, 9, 128, 48, k=3, gn=True, gn_silu=True, act=2),
+       ConvCase(_k("igemm", 24, 0, True, k3=True), 1, 13, 9, 1280, 128, k=3, splitk=7, note="KT = 180, split 7 -> 7"),
+       ConvCase(_k("igemm", 24, 0, True, k3=True), 1, 13, 9, 1280, 128, k=3, splitk=19, note="KT = 180, split 19 -> 18"),
+       ConvCase(_k("igemm", 24, 0, True, k3=True, gn=True), 2, 13, 9, 320, 48, k=3, gn=True, splitk=4, out_f32=True),
+       ConvCase(_k("igemm", 25, 0, k3=True), 16, 32, 32, 320, 320, k=3, stride=2, pad=1),
+       ConvCase(_k("igemm", 25, 0, k3=True, gn=True), 16, 32, 32, 320, 320, k=3, stride=2, pad=0, gn=True),
+       ConvCase(_k("igemm", 25, 0, True, k3=True), 16, 32, 32, 320, 320, k=3, stride=2, splitk=2),
+       ConvCase(_k("igemm", 25, 0, True, k3=True, gn=True), 16, 32, 32, 320, 320, k=3, stride=2, gn=True, splitk=2),
+       ConvCase(_k("igemm", 24, 0, gn=True), 1, 1, 77, 640, 2 * 640, geglu=True, gn=True),
+       ConvCase(_k("igemm", 25, 0, gn=True), 1, 1, 77, 640, 640, gn=True, gn_silu=True, row_add=True),
+       ConvCase(_k("igemm", 25, 0, True, gn=True), 1, 1, 77, 640, 640, gn=True, splitk=3),
+       ConvCase(_k("igemm", 44, 0, gn=True), 1, 1, 4096, 1280, 2 * 1280, geglu=True, gn=True),
+       ConvCase(_k("igemm", 45, 0, gn=True), 1, 1, 16384, 640, 1920, gn=True, residual=True),
+       ConvCase(_k("igemm", 45, 0, True, gn=True), 1, 1, 4097, 1280, 1280, gn=True, splitk=3)]
+    # ---------------------------------------------------------------- conv3x3_tile: the halo-tile kernel
+    + _tile(2, (3, 12, 32, 128, 144), 4, ring=4)                         # 4-row tiles, Cout 144: ragged 128-column tile, odd N
+    + _tile(2, (3, 16, 32, 320, 320), 5, ring=4)                         # 160-column tiles, deep ring (<= 256 workgroups)
+    + _tile(2, (41, 12, 32, 320, 320), 5, ring=2)                        # 160-column tiles, > 256 workgroups, odd N
+    + _tile(2, (41, 12, 32, 128, 144), 4, ring=2)
+    + _tile(2, (1, 8, 8, 320, 320), 5, narrow=True, gn_tpl=(5, 3, False))   # narrow 8x8 map, one image
+    + _tile(2, (3, 16, 8, 128, 48), 4, narrow=True, gn_tpl=(4, 3, False))   # narrow 16 x 8 map
+    + _tile(2, (2, 8, 8, 128, 16), 4, narrow=True, gn_tpl=(1, 3, False))   # (the narrow and upsample forms keep 128-column tiles)
+    + _tile(2, (3, 4, 16, 128, 16), 1)
+    + _tile(2, (3, 4, 16, 320, 4), 1, ring=3, fast=False, splits=False)
+    + _tile(2, (2, 4, 8, 128, 64), 4, up=True, gn_tpl=(4, 3, False))     # upsample 4x8 -> 8x16
+    + _tile(2, (2, 4, 8, 320, 320), 5, up=True, gn_tpl=(5, 3, False))
+    + _tile(2, (2, 4, 8, 128, 16), 4, up=True, gn_tpl=(1, 3, False))
+    + _tile(2, (3, 2, 8, 320, 4), 1, ring=3, fast=False, up=True, splits=False)
+    + _tile(4, (22, 32, 48, 128, 144), 4, c2=64)                         # 8-row tiles, x2 concat, ragged N tile
+    + _tile(4, (22, 32, 48, 320, 320), 5)                                # 8-row tiles, 160-column tiles
+    + _tile(4, (22, 16, 24, 128, 144), 4, up=True, gn_tpl=(4, 3, False))  # 8-row tiles with the fused upsample
+    + _tile(4, (22, 16, 24, 320, 320), 5, up=True, gn_tpl=(5, 2, False))
+    + _tile(8, (1026, 8, 8, 128, 128), 4, narrow=True, gn_opts=(False,))  # two 8x8 images per tile, 128-column tiles
+    + _tile(8, (514, 8, 8, 128, 320), 5, narrow=True, gn_opts=(False,))   # two 8x8 images per tile
+)
+
+
+# ------------------------------------------------------------------------------------------ attention instances
+HEAD_DIMS = (8, 16, 32, 40, 64, 80, 128, 160)
+
+
+def attention_key(b, heads, nq, nk, d):
+    """(D, QB, SHORT, RAGGED, PP) of the attn_kernel instance dc_attention_bf16 launches (dc_attention_route)"""
+    from diffcodec_amd import ops
+    return tuple(int(v) for v in ops.attention_route(b, heads, nq, nk, d))
+
+
+def enumerate_attention_keys():
+    """Every instance dc_attention_route yields over a grid of B x heads (grids below, at and far above the form thresholds),
+    query counts and key counts (1 .. 4096: single key, one tile +- 1, the short-context limit, ragged and whole long tiles)."""
+    keys = {}
+    for d in HEAD_DIMS:
+        for bh in ((1, 1), (2, 5), (9, 7), (8, 8), (16, 8), (32, 8), (64, 8)):
+            for nq in (1, 100, 1000, 2304, 4100, 8192):
+                for nk in (1, 63, 64, 65, 77, 128, 129, 192, 255, 256, 1000, 4096):
+                    keys.setdefault(attention_key(*bh, nq, nk, d), (*bh, nq, nk, d))
+    return keys
+
+
+@dataclass(frozen=True)
+class AttnCase:
+    key: tuple
+    b: int
+    heads: int
+    nq: int
+    nk: int
+    note: str = ""
+
+    @property
+    def d(self):
+        return self.key[0]
+
+    def label(self):
+        return f"B={self.b} heads={self.heads} Nq={self.nq} Nk={self.nk} d={self.d}"
+
+
+def _attn_cases():
+    out = []
+    for d in HEAD_DIMS:
+        small = d <= 48
+        # long form, one query block per wave (small grids): whole and ragged key tiles, Nk in {1, 63, 65, 64}
+        out += [AttnCase((d, 1, 0, 0, 0), 2, 5, 333, 192), AttnCase((d, 1, 0, 1, 0), 2, 5, 333, 1000),
+                AttnCase((d, 1, 0, 1, 0), 1, 3, 130, 1), AttnCase((d, 1, 0, 1, 0), 1, 3, 130, 63),
+                AttnCase((d, 1, 0, 1, 0), 1, 3, 97, 65), AttnCase((d, 1, 0, 0, 0), 1, 3, 97, 64)]
+        # short context (keys resident, 4 query blocks per workgroup): B x heads x ceil(Nq / 128) / 4 >= 512, one-half and
+        # two-half last tiles (77, 96, 97, 128)
+        out += [AttnCase((d, 1, 1, 1, 0), 9, 7, 4100, nk) for nk in (77, 97)]
+        out += [AttnCase((d, 1, 1, 1, 0), 16, 8, 2050, nk) for nk in (96, 128)]
+        if small:
+            # two query blocks per wave: grids of >= 512 workgroups of 256 queries (Nq = 2300: a ragged last block); short contexts with too few workgroups for
+            # the short form (Nk = 1, 63, 65) and long contexts below the ping-pong threshold (Nk < 256)
+            out += [AttnCase((d, 2, 0, 1, 0), 9, 7, 2300, nk) for nk in (1, 63, 65)]
+            out += [AttnCase((d, 2, 0, 0, 0), 9, 7, 2300, 64), AttnCase((d, 2, 0, 0, 0), 9, 7, 2300, 192),
+                    AttnCase((d, 2, 0, 1, 0), 9, 7, 2300, 200)]
+            # ping-pong (8 waves, 512 queries per workgroup): >= 256 workgroups and Nk >= 256
+            out += [AttnCase((d, 2, 0, 0, 1), 9, 7, 2100, 256), AttnCase((d, 2, 0, 1, 1), 9, 7, 2100, 1000),
+                    AttnCase((d, 2, 0, 1, 1), 5, 8, 3333, 300)]
+    return out
+
+
+ATTN_CASES = _attn_cases()
+
+
+def attention_query_span(key):
+    """queries per workgroup of an instance: 128 (4 waves) or 256 (8 waves, ping-pong) x QB, x 4 passes in the short form"""
+    d, qb, short, ragged, pp = key
+    return (256 if pp else 128) * qb * (4 if short else 1)
+
+
+def attention_inputs(family, b, heads, nq, nk, d, gen):
+    """fp32 (q, k, v) of an attention input family:
+      random  q, k, v ~ N(0, 1);
+      flat    q = 0: every real key gets the same weight and the output is the mean of V = 1 + 0.25 N(0, 1), so a masking or
+              normalisation error shifts the whole row;
+      peaked  the queries of head h share one direction u_h (plus 0.1 noise); the winner key of head h is c_w u_h, the others
+              0.5 N(0, 1): the winner leads by a c_w scale = 25 after the softmax scale, |score| stays below ~30 (the bf16
+              rounding of the prescaled queries cannot reorder keys).  Winner: first tile for heads h % 3 == 0, key Nk - 1 for head 1,
+              inside the last (ragged) tile for the others — the running max, the rescale across tiles and the last-tile mask."""
+    c = heads * d
+    if family == "random":
+        return torch.randn(b, nq, c, generator=gen), torch.randn(b, nk, c, generator=gen), torch.randn(b, nk, c, generator=gen)
+    if family == "flat":
+        return torch.zeros(b, nq, c), torch.randn(b, nk, c, generator=gen), 1 + 0.25 * torch.randn(b, nk, c, generator=gen)
+    assert family == "peaked", family
+    u = torch.randn(heads, d, generator=gen)
+    u = u / u.norm(dim=1, keepdim=True)
+    a = 8.0
+    cw = 25.0 * math.sqrt(d) / a
+    q = (a * u[None, None] + 0.1 * torch.randn(b, nq, heads, d, generator=gen)).reshape(b, nq, c)
+    k = 0.5 * torch.randn(b, nk, heads, d, generator=gen)
+    for h, j in enumerate(peaked_winners(heads, nk)):
+        k[:, j, h] = cw * u[h]
+    return q, k.reshape(b, nk, c), torch.randn(b, nk, c, generator=gen)
+
+
+def peaked_winners(heads, nk):
+    """key index of each head's winner in the peaked family"""
+    last0 = (nk - 1) // 64 * 64
+    return [min(3, nk - 1) if h % 3 == 0 else nk - 1 if h == 1 else last0 + (h * 7) % (nk - last0) for h in range(heads)]
+
+
+# ------------------------------------------------------------------------------------------ normalisation cases
+# group_norm_ab / gn_apply: (N, H, W, C1, C2, groups): HW not a multiple of the statistics chunking (15 x 8, 7 x 9, 1), N in {1, 3},
+# a group straddling the x1 / x2 boundary (320 + 640 channels: 30 per group, group 10 = channels 300..329)
+GN_CASES = [(1, 15, 8, 320, 0, 32), (3, 7, 9, 64, 0, 32), (1, 1, 1, 64, 0, 32), (3, 15, 8, 320, 640, 32), (1, 7, 9, 320, 640, 32),
+            (3, 33, 17, 128, 0, 32)]
+LN_CASES = [(77, c) for c in (8, 512, 520, 768, 1024, 1032, 2048)] + [(4097, 320)]          # (M, C): M % 4 != 0
+ROW_STATS_CASES = [(77, 64), (77, 320), (333, 1280), (5, 2048)]
+LN_FINALIZE_CASES = [(77, 1, 320), (77, 4, 640), (333, 16, 1280), (5, 20, 1280)]              # (M, parts, C)
+SOFTMAX_CASES = [(5, c) for c in (1, 77, 255, 257, 4097)]                                      # (rows, cols)
+
+
+# ------------------------------------------------------------------------------------------ direct (VALU) convs
+@dataclass(frozen=True)
+class SmallCase:
+    """dc_conv_small_cin_bf16 (Cin <= 16: conv_in4_kernel for Cin = 4, 3x3 s1 p1, Cout % 8 == 0, W % 4 == 0 — 4-pixel strips —
+    the generic per-pixel kernel otherwise) and dc_conv_small_cout_bf16 (COUT = 3 / 4 / 8 templates, 4 pixels per workgroup,
+    GroupNorm (+ SiLU) on load, fp32 output)."""
+    kind: str
+    n: int
+    h: int
+    w: int
+    cin: int
+    cout: int
+    k: int = 3
+    stride: int = 1
+    pad: int = 1
+    gn: bool = False
+    out_f32: bool = False
+
+    @property
+    def ho(self):
+        return self.h if self.k == 1 else (self.h + (2 if self.pad else 1) - 3) // self.stride + 1
+
+    @property
+    def wo(self):
+        return self.w if self.k == 1 else (self.w + (2 if self.pad else 1) - 3) // self.stride + 1
+
+    @property
+    def strip_kernel(self):
+        return self.kind == "small_cin" and self.cin == 4 and self.k == 3 and self.stride == 1 and self.pad == 1 and \
+            self.cout % 8 == 0 and self.w % 4 == 0
+
+    def label(self):
+        f = ["gn"] * self.gn + ["out_f32"] * self.out_f32
+        return f"{self.kind} {self.n}x{self.h}x{self.w}x{self.cin}->{self.cout} k{self.k}s{self.stride}p{self.pad} [{','.join(f)}]"
+
+
+SMALL_CASES = [
+    SmallCase("small_cin", 2, 9, 32, 4, 320),                   # conv_in: 4-pixel strips, W % 4 == 0, odd H
+    SmallCase("small_cin", 3, 7, 30, 4, 320),                   # W % 4 != 0: the per-pixel kernel
+    SmallCase("small_cin", 1, 7, 13, 4, 20),                    # Cout % 8 != 0
+    SmallCase("small_cin", 2, 15, 17, 4, 32, stride=2),         # stride 2 on an odd map
+    SmallCase("small_cin", 1, 9, 11, 16, 24, k=1),              # 1x1, Cin 16
+    SmallCase("small_cin", 2, 8, 12, 3, 16, stride=2, pad=1),   # Cin 3
+] + [SmallCase("small_cout", n, 7, 9, 64, co, k=k, gn=gn, out_f32=f32)  # M = 63 or 189: a partial last 4-pixel workgroup
+     for co in (3, 4, 8) for (n, k, gn, f32) in ((1, 3, False, False), (3, 3, True, False), (1, 1, False, True), (3, 3, True, True))]

@@ -1,0 +1,236 @@
+"""CPU: the edge-case tables of tests/edge_cases.py cover every kernel instance the dispatchers can reach, every case routes to the
+instance it declares, and the checks the GPU edge tests rely on (guarded buffers, the flat and peaked attention input families held
+to oracle/launch_ref.py) reject the faults they are there to catch."""
+import json
+import math
+import os
+import re
+
+import pytest
+import torch
+
+import edge_cases as E
+from oracle import launch_ref as L
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+F64 = torch.float64
+
+
+@pytest.fixture(scope="module")
+def lib():
+    import __graft_entry__ as g
+    from diffcodec_amd import lib as l
+    if not os.path.exists(l.LIB_PATH):
+        g.build()
+    return l
+
+
+# ------------------------------------------------------------------------------------------ conv / linear routes
+@pytest.fixture(scope="module")
+def conv_keys(lib):
+    return E.enumerate_conv_keys()
+
+
+def uncovered(keys, cases):
+    have = {c.key for c in cases}
+    return sorted(E.key_str(k) if isinstance(k[0], str) else str(k) for k in keys if k not in have)
+
+
+def test_conv_grid_spans_the_production_routes(conv_keys):
+    """every (route, epi, split-K) triple the decodes launch (tests/golden/shadow_routes.json) is the projection of an enumerated key"""
+    proj = {(k[0], k[2], k[3]) for k in conv_keys}
+    shadow = json.load(open(os.path.join(ROOT, "tests", "golden", "shadow_routes.json")))
+    for batch, routes in shadow.items():
+        for kernel, epi, split in routes:
+            assert (kernel, epi, split) in proj, (batch, kernel, epi, split)
+
+
+def test_every_conv_case_targets_an_enumerated_instance(conv_keys):
+    """the grid spans every flag the table uses: no case reaches an instance the enumeration misses"""
+    extra = sorted({E.key_str(c.key) for c in E.CONV_CASES if c.key not in conv_keys})
+    assert not extra, "table instances the descriptor grid does not reach:\n" + "\n".join(extra)
+
+
+def test_every_conv_instance_has_a_case(conv_keys):
+    missing = uncovered(conv_keys, E.CONV_CASES)
+    assert not missing, "conv instances without an edge case:\n" + "\n".join(missing)
+
+
+@pytest.mark.parametrize("i", range(len(E.CONV_CASES)), ids=[c.label() for c in E.CONV_CASES])
+def test_conv_case_routes_where_it_declares(lib, i):
+    c = E.CONV_CASES[i]
+    got = E.conv_key(E.case_desc(c))
+    assert got == c.key, f"{c.label()}: declared {E.key_str(c.key)}, routes to {E.key_str(got)}"
+
+
+def test_removing_a_sole_conv_case_names_its_instance(conv_keys):
+    """the coverage check is sharp: dropping any case that is the only one of its instance fails and names that instance"""
+    count = {}
+    for c in E.CONV_CASES:
+        count[c.key] = count.get(c.key, 0) + 1
+    sole = [i for i, c in enumerate(E.CONV_CASES) if count[c.key] == 1 and c.key in conv_keys]
+    assert sole
+    for i in sole:
+        cases = E.CONV_CASES[:i] + E.CONV_CASES[i + 1:]
+        assert uncovered(conv_keys, cases) == [E.key_str(E.CONV_CASES[i].key)]
+
+
+# ------------------------------------------------------------------------------------------ attention routes
+@pytest.fixture(scope="module")
+def attn_keys(lib):
+    return E.enumerate_attention_keys()
+
+
+def test_every_attention_instance_has_a_case(attn_keys):
+    assert len(attn_keys) >= 40
+    missing = uncovered(attn_keys, E.ATTN_CASES)
+    assert not missing, "attention instances without an edge case:\n" + "\n".join(missing)
+
+
+@pytest.mark.parametrize("i", range(len(E.ATTN_CASES)), ids=[c.label() for c in E.ATTN_CASES])
+def test_attention_case_routes_where_it_declares(lib, i):
+    c = E.ATTN_CASES[i]
+    assert E.attention_key(c.b, c.heads, c.nq, c.nk, c.d) == c.key, c.label()
+
+
+def test_attention_cases_have_a_query_tail():
+    """every case leaves a partial last query block (Nq not a multiple of its instance's workgroup query span)"""
+    for c in E.ATTN_CASES:
+        assert c.nq % E.attention_query_span(c.key) != 0, c.label()
+
+
+def test_small_conv_table_spans_both_kernels():
+    """dc_conv_small_cin_bf16: the 4-pixel-strip kernel and the per-pixel one, W % 4 != 0, Cout % 8 != 0, stride 2;
+    dc_conv_small_cout_bf16: every COUT template with and without GroupNorm on load and fp32 output, M % 4 != 0"""
+    cin = [c for c in E.SMALL_CASES if c.kind == "small_cin"]
+    assert {c.strip_kernel for c in cin} == {True, False}
+    assert any(c.w % 4 for c in cin) and any(c.cout % 8 for c in cin) and any(c.stride == 2 for c in cin)
+    cout = {(c.cout, c.gn, c.out_f32) for c in E.SMALL_CASES if c.kind == "small_cout"}
+    assert cout >= {(co, gn, f32) for co in (3, 4, 8) for gn in (False, True) for f32 in (False, True)}
+    assert all((c.n * c.ho * c.wo) % 4 for c in E.SMALL_CASES if c.kind == "small_cout")
+
+
+def test_removing_a_sole_attention_case_names_its_instance(attn_keys):
+    count = {}
+    for c in E.ATTN_CASES:
+        count[c.key] = count.get(c.key, 0) + 1
+    for i, c in enumerate(E.ATTN_CASES):
+        if count[c.key] == 1:
+            assert uncovered(attn_keys, E.ATTN_CASES[:i] + E.ATTN_CASES[i + 1:]) == [str(c.key)]
+
+
+def test_attention_route_refuses_what_the_launch_refuses(lib):
+    from diffcodec_amd import ops
+    for bad in ((0, 8, 64, 64, 40), (1, 8, 64, 0, 40), (1, 8, 64, 64, 48), (1, 0, 64, 64, 40)):
+        with pytest.raises(lib.HipLaunchError):
+            ops.attention_route(*bad)
+
+
+# the attention launches of one denoising step (UNet + ControlNet transformer blocks at 64x64 / 32x32 / 16x16 / 8x8 latents; self
+# attention over the map, cross attention over the 77-token text context), at the model batches of the 16-frame (32) and 1-frame (2) legs
+def _decode_attention_shapes(batch):
+    shapes = set()
+    for hw, c in ((4096, 320), (1024, 640), (256, 1280), (64, 1280)):
+        d = c // 8
+        shapes.add((batch, 8, hw, hw, d))
+        shapes.add((batch, 8, hw, 77, d))
+    return shapes
+
+
+@pytest.mark.parametrize("frames,batch", [(16, 32), (1, 2)])
+def test_attention_routes_match_the_profiled_instances(lib, frames, batch):
+    """hardware witness: the instances the route returns for a decode's attention shapes are the attn_kernel<...> instances a
+    profile of that decode on the MI355X recorded (profiles/r04_kernel_stats_frames{16,1}.txt)"""
+    prof = open(os.path.join(ROOT, "profiles", f"r04_kernel_stats_frames{frames}.txt")).read()
+    seen = set()
+    for m in re.finditer(r"attn_kernel<(\d+), (\d+), (true|false), (true|false), (true|false)>", prof):
+        d, qb = int(m.group(1)), int(m.group(2))
+        seen.add((d, qb) + tuple(int(x == "true") for x in m.group(3, 4, 5)))
+    routed = {E.attention_key(*s) for s in _decode_attention_shapes(batch)}
+    assert routed == seen, (sorted(routed), sorted(seen))
+
+
+# ------------------------------------------------------------------------------------------ guarded buffers
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+def test_guard_flags_writes_outside_the_view_and_unwritten_rows(dtype):
+    g = E.Guarded((3, 5, 24), dtype, "cpu", pitch=32)
+    g.fill(torch.randn(3, 5, 24))
+    assert g.bad() == [] and g.unwritten() == 0
+    flat = g.base
+    for where, idx in (("after", g.guard + 3 * 5 * 32), ("before", g.guard - 1), ("gap", g.guard + 2 * 32 + 24)):
+        h = E.Guarded((3, 5, 24), dtype, "cpu", pitch=32)
+        h.fill(torch.randn(3, 5, 24))
+        h.base[idx] = 1.0
+        assert h.bad() and h.bad()[0][0] == where, (where, h.bad())
+        with pytest.raises(AssertionError):
+            h.assert_intact("out")
+    # an output row the kernel never writes stays NaN: L.check rejects it, and the pattern count names it
+    o = E.Guarded((4, 8), dtype, "cpu")
+    ref = torch.randn(4, 8, dtype=F64)
+    o.view[:3] = ref[:3].to(dtype)
+    assert o.unwritten() == 8
+    assert not L.check(o.view, ref, ref.abs(), dtype)["ok"]
+    o.view[3] = ref[3].to(dtype)
+    assert L.check(o.view, ref, ref.abs(), dtype)["ok"] and o.bad() == []
+    assert flat.numel() == 2 * E.GUARD + 3 * 5 * 32
+
+
+# ------------------------------------------------------------------------------------------ attention input families
+def _attention_masked_wrong(q, k, v, heads, pad_to):
+    """fp64 output of a kernel whose padded keys (up to `pad_to`, re-reading the last key) score 0 instead of -inf"""
+    b, nq, c = q.shape
+    d = c // heads
+    nk = k.shape[1]
+    idx = torch.clamp(torch.arange(pad_to), max=nk - 1)
+    qq = q.to(F64).reshape(b, nq, heads, d).transpose(1, 2)
+    kk = k.to(F64)[:, idx].reshape(b, pad_to, heads, d).transpose(1, 2)
+    vv = v.to(F64)[:, idx].reshape(b, pad_to, heads, d).transpose(1, 2)
+    s = qq @ kk.transpose(2, 3) * d ** -0.5
+    s[..., nk:] = 0.0
+    return (torch.softmax(s, -1) @ vv).transpose(1, 2).reshape(b * nq, c)
+
+
+@pytest.mark.parametrize("nk", [65, 1000])
+def test_flat_family_rejects_padded_keys_scoring_zero(nk):
+    """the flat inputs of the GPU edge tests: padded keys of the ragged last tile that score 0 instead of -inf fail L.check"""
+    q, k, v = (t.to(torch.bfloat16) for t in E.attention_inputs("flat", 2, 2, 16, nk, 40, torch.Generator().manual_seed(0)))
+    rows = torch.arange(2 * 16)
+    r, s = L.attention_ref(q, k, v, 2, rows)
+    assert L.check(r.to(torch.bfloat16), r, s, torch.bfloat16)["ok"]
+    wrong = _attention_masked_wrong(q, k, v, 2, (nk + 63) // 64 * 64).to(torch.bfloat16)
+    v_ = L.check(wrong, r, s, torch.bfloat16)
+    assert not v_["ok"], v_
+
+
+def _attention_no_rescale(q, k, v, heads, tile=64):
+    """online softmax whose running max moves but whose earlier accumulations are never rescaled (the stale-max fault)"""
+    b, nq, c = q.shape
+    d = c // heads
+    nk = k.shape[1]
+    qq = q.to(F64).reshape(b, nq, heads, d).transpose(1, 2)
+    kk = k.to(F64).reshape(b, nk, heads, d).transpose(1, 2)
+    vv = v.to(F64).reshape(b, nk, heads, d).transpose(1, 2)
+    s = qq @ kk.transpose(2, 3) * d ** -0.5
+    m = torch.full(s.shape[:-1] + (1,), -math.inf, dtype=F64)
+    acc = torch.zeros(b, heads, nq, d, dtype=F64)
+    l = torch.zeros_like(m)
+    for t0 in range(0, nk, tile):
+        st = s[..., t0:t0 + tile]
+        m = torch.maximum(m, st.amax(-1, keepdim=True))
+        p = torch.exp(st - m)
+        acc = acc + p @ vv[:, :, t0:t0 + tile]
+        l = l + p.sum(-1, keepdim=True)
+    return (acc / l).transpose(1, 2).reshape(b * nq, c)
+
+
+@pytest.mark.parametrize("nk", [200, 1000])
+def test_peaked_family_rejects_a_stale_running_max(nk):
+    """the peaked inputs of the GPU edge tests: a running max that moves without rescaling the earlier tiles fails L.check"""
+    heads = 4
+    assert any(j >= 64 for j in E.peaked_winners(heads, nk))           # some winner lies past the first tile
+    q, k, v = (t.to(torch.bfloat16) for t in E.attention_inputs("peaked", 1, heads, 8, nk, 40, torch.Generator().manual_seed(0)))
+    rows = torch.arange(8)
+    r, s = L.attention_ref(q, k, v, heads, rows)
+    assert L.check(r.to(torch.bfloat16), r, s, torch.bfloat16)["ok"]
+    wrong = _attention_no_rescale(q, k, v, heads).to(torch.bfloat16)
+    assert not L.check(wrong, r, s, torch.bfloat16)["ok"]

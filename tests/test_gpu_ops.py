@@ -8,6 +8,7 @@ import torch
 import torch.nn.functional as F
 
 from launch_shadow import capture_routes
+from oracle import launch_ref as L
 
 pytestmark = pytest.mark.gpu
 
@@ -246,6 +247,17 @@ def test_conv_igemm_plain(ops, case):
         out = ops.conv(nhwc(x1), pc, x2=None if x2 is None else nhwc(x2), stride=stride, pad=pad, upsample=up)
     assert [(r.kernel, r.variant) for r in routes] == [CONV_ROUTES[CONV_CASES.index(case)]], routes
     close(from_nhwc(out), ref)
+    _strict(out, lambda rows: L.conv_ref(nhwc(x1), pc, rows, x2=None if x2 is None else nhwc(x2), stride=stride, pad=pad, upsample=up),
+            spatial=(out.shape[0], out.shape[1], out.shape[2]) if k == 3 else None)
+
+
+def _strict(y, ref_fn, spatial=None):
+    """the launch's output held to its fp64 reference (oracle/launch_ref.py) on the sampled rows, beside the torch comparison"""
+    c = y.shape[-1]
+    rows = L.sample_rows(y.numel() // c, spatial=spatial)
+    r, s = ref_fn(rows)
+    v = L.check(y.reshape(-1, c)[rows.to(y.device)], r, s, y.dtype)
+    assert v["ok"], v
 
 
 def test_conv_igemm_asymmetric_operands(ops):
@@ -562,8 +574,10 @@ def test_attention(ops, b, heads, nq, nk, d):
     v = bf(torch.randn(b, nk, c, generator=g))
     qh, kh, vh = (t.view(b, -1, heads, d).transpose(1, 2) for t in (q, k, v))
     ref = F.scaled_dot_product_attention(qh, kh, vh).transpose(1, 2).reshape(b, nq, c)
-    out = ops.attention(q.to(DEV, torch.bfloat16), k.to(DEV, torch.bfloat16), v.to(DEV, torch.bfloat16), heads)
+    qd, kd, vd = (t.to(DEV, torch.bfloat16) for t in (q, k, v))
+    out = ops.attention(qd, kd, vd, heads)
     close(out.float().cpu(), ref, rtol=2e-2, atol=1e-2)
+    _strict(out, lambda rows: L.attention_ref(qd, kd, vd, heads, rows))
 
 
 def test_attention_forced_rescale_and_strided_views(ops):
@@ -578,8 +592,10 @@ def test_attention_forced_rescale_and_strided_views(ops):
     qh, kh, vh = (t.reshape(b, -1, heads, d).transpose(1, 2) for t in (q, k, v))
     ref = F.scaled_dot_product_attention(qh, kh, vh).transpose(1, 2).reshape(b, n, c)
     kvd = kv.to(DEV, torch.bfloat16)
-    out = ops.attention(q.to(DEV, torch.bfloat16), kvd[..., :c], kvd[..., c:], heads)
+    qd = q.to(DEV, torch.bfloat16)
+    out = ops.attention(qd, kvd[..., :c], kvd[..., c:], heads)
     close(out.float().cpu(), ref, rtol=2e-2, atol=1e-2)
+    _strict(out, lambda rows: L.attention_ref(qd, kvd[..., :c], kvd[..., c:], heads, rows))
 
 
 @pytest.mark.parametrize("b,heads,nq,nk,d", [(32, 8, 4096, 4096, 40),   # the 64x64 self-attention of the decode loop at model batch 32
@@ -603,6 +619,7 @@ def test_attention_ping_pong_form(ops, b, heads, nq, nk, d):
         qh, kh, vh = (t[bi:bi + 1].view(1, -1, heads, d).transpose(1, 2) for t in (q, k, v))
         ref = F.scaled_dot_product_attention(qh, kh, vh).transpose(1, 2).reshape(1, nq, c)
         close(out[bi:bi + 1].float().cpu(), ref, rtol=2e-2, atol=1e-2)
+    _strict(out, lambda rows: L.attention_ref(qd, kd, vd, heads, rows))
 
 
 @pytest.mark.parametrize("b,heads,nq,nk,d", [(36, 8, 1024, 512, 16), (64, 8, 512, 256, 8), (16, 8, 4096, 4096, 40), (4, 8, 4096, 4096, 40),
