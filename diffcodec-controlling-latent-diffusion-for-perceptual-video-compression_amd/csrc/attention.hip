@@ -31,9 +31,6 @@ extern "C" int dc_attn_stamp_read(void* dst, int n) { return (int)hipMemcpyFromS
 namespace {
 
 constexpr int KV_TILE = 64;                  // keys per iteration (two 32-key MFMA tiles)
-#ifndef DC_ATTN_PRESCALE
-#define DC_ATTN_PRESCALE 1                   // developer A/B switch for the accumulator-initialised softmax (see process_tile)
-#endif
 // Offset-in-the-GEMM online softmax (head dims with a spare zero-padded column: d = 40, 8): the queries are pre-multiplied by
 // scale*log2(e) once per block (fp32 multiply, one bf16 rounding), column D of every K row is 1.0 in LDS and element D of the
 // query fragment holds minus the running offset — so the QK^T MFMA chain itself leaves t = log2e*scale*s - offset, ready for
@@ -43,21 +40,6 @@ constexpr int KV_TILE = 64;                  // keys per iteration (two 32-key M
 // subtract-and-rescale pass is the exception, not the rule.  The d = 40 kernel is VALU-issue-bound (64 exps + 32 converts +
 // 16 max3 per 28 MFMAs and tile): the 32 packed FMAs this removes were ~13 % of its VALU time.
 constexpr float RESCALE_THR = 4.0f;
-#ifndef DC_ATTN_SOFTMAX_PRIO
-#define DC_ATTN_SOFTMAX_PRIO 2               // wave priority during the exp / convert block (0 = off: developer A/B)
-#endif
-#ifndef DC_ATTN_STORE_FENCE
-#define DC_ATTN_STORE_FENCE 2                // developer A/B switch: scheduling fences in front of the ping-pong form's staging stores (0 | 1 = V | 2 = V and K)
-#endif
-#ifndef DC_ATTN_QK_FIRST
-#define DC_ATTN_QK_FIRST 1                   // ping-pong form: QK^T(t) before PV(t-1) inside the MFMA block (0: the round-3 order, developer A/B)
-#endif
-#ifndef DC_ATTN_V_EARLY
-#define DC_ATTN_V_EARLY 0                    // developer A/B switch: 0 = group 1 of the ping-pong form stages V at the end of its MFMA block
-#endif
-#ifndef DC_ATTN_EARLY_STAGE
-#define DC_ATTN_EARLY_STAGE 1                // developer A/B switch: 0 = the next tile is written to LDS after the PV MFMAs
-#endif
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
 // V stays row-major [key][d] in LDS (one ds_write_b128 per staged vector); the PV MFMA's A operand (V^T: 4 consecutive
@@ -73,6 +55,8 @@ struct AttnArgs {
     int B, heads, Nq, Nk;
     long long qs, ks, vs, os;
     float scale_log2e;
+    // Always 1.  Dropping this argument and its never-taken branch leaves every loop instruction as it is but shortens the prologue,
+    // which moves the loops: the d = 40 ping-pong form then measured 0.9 % slower (same box, 12 of 12 alternating pairs).
     int xcd_remap;
 };
 
@@ -115,7 +99,7 @@ __global__ __launch_bounds__(PP ? 512 : 256, (D <= 80 ? 2 : 1)) void attn_kernel
     // the running-max correction.  Saves one v_add_f32 per probability.
     // spare QK^T column available for the offset; not for the short-context form (two tiles per block: the first-tile anchor
     // pass costs more than the two tiles of FMAs it saves — measured 74 vs 68 us at 4096 x 77, d = 40)
-    constexpr bool QOFF = DC_ATTN_PRESCALE && (D % 16) != 0 && !SHORT;
+    constexpr bool QOFF = (D % 16) != 0 && !SHORT;
     constexpr int QOFF_KS = D / 16, QOFF_LH = (D % 16) / 8, QOFF_E = (D % 16) % 8;
     constexpr bool ONES = (D % 32) != 0;
     constexpr int ONES_T = D / 32, ONES_R = ((D % 32) & 3) + 4 * ((D % 32) >> 3);
@@ -135,10 +119,7 @@ __global__ __launch_bounds__(PP ? 512 : 256, (D <= 80 ? 2 : 1)) void attn_kernel
     // K/V (PMC, round 3: 4.5x the algorithmic bytes = 8 x K/V + Q + O).  Each XCD now walks a contiguous range of (head, block)
     // pairs: the blocks of one head run on one XCD, back to back, and share its L2 copy of K/V.
     int bid = blockIdx.x;
-    if (a.xcd_remap) {
-        const int nblk = gridDim.x, xq = nblk >> 3, xr = nblk & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + idx;
-    }
+    if (a.xcd_remap) bid = dc_xcd_remap(bid, gridDim.x);
     const int bh = bid / qblocks;
     const int qb = bid - bh * qblocks;
     const int b = bh / a.heads, h = bh - b * a.heads;
@@ -321,7 +302,7 @@ __global__ __launch_bounds__(PP ? 512 : 256, (D <= 80 ? 2 : 1)) void attn_kernel
         // the issue arbitration: at equal priority the (older) wave whose next instruction is an MFMA waiting for the matrix pipe
         // holds the SIMD's issue slot, and the two waves' times add (tools/micro/mfma_valu_overlap.hip: v_exp beside MFMA 3.31 ms
         // at equal priority = the sum, 1.97 ms = the max with the VALU wave at s_setprio 2; plain v_fma never overlaps).
-        if (DC_ATTN_SOFTMAX_PRIO) __builtin_amdgcn_s_setprio(DC_ATTN_SOFTMAX_PRIO);
+        __builtin_amdgcn_s_setprio(2);
 #pragma unroll
         for (int u = 0; u < QB; ++u) {
             const float mloc = mloc_s[u];
@@ -389,7 +370,7 @@ __global__ __launch_bounds__(PP ? 512 : 256, (D <= 80 ? 2 : 1)) void attn_kernel
             if (!ONES) l_run[u] += lsum;
         }
 
-        if (DC_ATTN_SOFTMAX_PRIO) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(0);
     };
     // ---- O^T += V^T . P^T ; A-operand element jj of lane-half lh is key 16*s2 + 8*(jj>>2) + 4*lh + (jj&3)
     // transposing read: lane (16-lane group g4, j16) addresses key row (j16>>2), d columns 4*(j16&3).. of its block
@@ -429,7 +410,7 @@ __global__ __launch_bounds__(PP ? 512 : 256, (D <= 80 ? 2 : 1)) void attn_kernel
 #endif
         // the next tile's K/V (in registers since the top of this tile) go to the other LDS buffer HERE, so the writes drain under
         // the PV MFMAs instead of in front of the barrier
-        if (DC_ATTN_EARLY_STAGE && stage_next) store_lds((t & 1) ^ 1);
+        if (stage_next) store_lds((t & 1) ^ 1);
         pv_part(t & 1);
     };
 
@@ -536,15 +517,11 @@ __global__ __launch_bounds__(PP ? 512 : 256, (D <= 80 ? 2 : 1)) void attn_kernel
         if (grp == 1) __syncthreads();                         // group 1 runs one slot behind
         // tile 0 (peeled: no PV yet, and the softmax anchors its offset)
         if (grp == 0 && 1 < T) pp_issue(1);                    // K(1): written at the end of this tile's softmax
-        if (DC_ATTN_V_EARLY && grp == 1) {
-            pp_store(1);                                       // V(0), in registers since the prologue
-            if (DC_ATTN_V_EARLY == 1 && 1 < T) pp_issue(1);    // V(1): written at the START of the next MFMA block
-        }
         qk_part(0);
         rowmax_part(0);
-        if (!DC_ATTN_V_EARLY && grp == 1) pp_store(1);         // V(0), in registers since the prologue
+        if (grp == 1) pp_store(1);                             // V(0), in registers since the prologue
         __syncthreads();
-        if (DC_ATTN_V_EARLY != 1 && grp == 1 && 1 < T) pp_issue(1);   // V(1)
+        if (grp == 1 && 1 < T) pp_issue(1);                    // V(1)
         softmax_part(0, true);
         if (grp == 0 && 1 < T) pp_store(1);                    // K(1)
         __syncthreads();
@@ -552,33 +529,20 @@ __global__ __launch_bounds__(PP ? 512 : 256, (D <= 80 ? 2 : 1)) void attn_kernel
             // MFMA block of tile t
             DC_NOW(st_a);
             if (grp == 0 && t + 1 < T) pp_issue(t + 1);
-            // group 1 writes V(t) (fetched during the whole previous tile) and fetches V(t+1) at the START of its MFMA block: the LDS
-            // write and its wait drain under the block's 28 MFMAs instead of standing between the row maxima and the barrier (stamps,
-            // round 4: group 1's MFMA block took 1,900 cycles against group 0's 1,490, and group 0 idled 1,360 cycles per tile at the
-            // end barrier).  Pair t+1's buffer was last read one full tile ago, so the write may come anywhere in this block.
-            if (DC_ATTN_V_EARLY && grp == 1) {
-                pp_store((t + 1) & 1);                         // V(t)
-                if (DC_ATTN_V_EARLY == 1 && t + 1 < T) pp_issue(t + 1);
-            }
-#if DC_ATTN_QK_FIRST
-            // scores first: their row maxima (a dependent v_max3 chain behind the last QK^T MFMA) then issue in the shadow of the 16 PV
-            // MFMAs instead of as a tail in front of the barrier; 236 VGPRs, no spill (round 4, same-box A/B: 950 -> 930-939 us)
+            // scores first, QK^T(t) before PV(t-1): their row maxima (a dependent v_max3 chain behind the last QK^T MFMA) then issue in
+            // the shadow of the 16 PV MFMAs instead of as a tail in front of the barrier; 236 VGPRs, no spill (round 4, same-box A/B
+            // against the round-3 order PV first: 950 -> 930-939 us)
             qk_part(t & 1);
             pv_part(t & 1);
             rowmax_part(t);
-#else
-            pv_part(t & 1);                                    // V(t-1), probabilities of tile t-1
-            __builtin_amdgcn_sched_barrier(0);                 // PV before QK^T: the probabilities die before the new scores are born
-            qk_part(t & 1);
-            rowmax_part(t);
-#endif
-            // the staging stores stay where they are written: without the fence hipcc hoists the `s_waitcnt vmcnt(0)` + ds_write of V(t)
-            // up among the block's MFMAs, where the wait stalls the matrix pipe (stamps, round 4: group 1's MFMA block 1,900 -> 1,570 cycles)
-            if (DC_ATTN_STORE_FENCE >= 1) __builtin_amdgcn_sched_barrier(0);
+            // group 1 stages V(t) (fetched during the whole previous tile) at the END of its MFMA block, and the staging stores stay
+            // where they are written: without the fence hipcc hoists the `s_waitcnt vmcnt(0)` + ds_write of V(t) up among the block's
+            // MFMAs, where the wait stalls the matrix pipe (stamps, round 4: group 1's MFMA block 1,900 -> 1,570 cycles)
+            __builtin_amdgcn_sched_barrier(0);
 #ifdef DC_STAMP
             DC_NOW(st_v);
 #endif
-            if (!DC_ATTN_V_EARLY && grp == 1) pp_store((t + 1) & 1);               // V(t)
+            if (grp == 1) pp_store((t + 1) & 1);               // V(t)
 #ifdef DC_STAMP
             __builtin_amdgcn_sched_barrier(0);
             DC_NOW(st_b);
@@ -587,9 +551,9 @@ __global__ __launch_bounds__(PP ? 512 : 256, (D <= 80 ? 2 : 1)) void attn_kernel
             __syncthreads();
             // softmax block of tile t
             DC_NOW(st_c);
-            if (DC_ATTN_V_EARLY != 1 && grp == 1 && t + 1 < T) pp_issue(t + 1);
+            if (grp == 1 && t + 1 < T) pp_issue(t + 1);
             softmax_part(t, false);
-            if (DC_ATTN_STORE_FENCE >= 2) __builtin_amdgcn_sched_barrier(0);   // K(t+1) is written AFTER the exponentials (hipcc puts its vmcnt(0) in front of them)
+            __builtin_amdgcn_sched_barrier(0);                 // K(t+1) is written AFTER the exponentials (hipcc puts its vmcnt(0) in front of them)
             if (grp == 0 && t + 1 < T) pp_store((t + 1) & 1);  // K(t+1)
 #ifdef DC_STAMP
             __builtin_amdgcn_sched_barrier(0);
@@ -631,7 +595,6 @@ __global__ __launch_bounds__(PP ? 512 : 256, (D <= 80 ? 2 : 1)) void attn_kernel
             __builtin_amdgcn_sched_barrier(0);
             DC_NOW(st_d);
 #endif
-            if (!DC_ATTN_EARLY_STAGE && more) store_lds((t & 1) ^ 1);
             __syncthreads();
 #ifdef DC_STAMP
             DC_NOW(st_e);
@@ -700,23 +663,20 @@ struct AttnForm {
 AttnForm attn_form(int D, int B, int heads, int Nq, int Nk)
 {
     // two query blocks per wave only for the small heads (register budget) and only when that still leaves >= 2 workgroups per CU
-    static const int force_qb = DC_KNOB("DC_ATTN_QB", 0);      // developer knob
-    static const int no_short = DC_KNOB("DC_ATTN_NO_SHORT", 0);   // developer knob (A/B)
-    static const int force_pp = DC_KNOB("DC_ATTN_PP", -1);     // developer A/B knob (DC_ATTN_PP=0/1)
     // short context (text cross-attention): keys resident, several query blocks per workgroup — when enough workgroups remain
-    const bool short_ctx = !no_short && Nk <= 2 * KV_TILE;
+    const bool short_ctx = Nk <= 2 * KV_TILE;
     // the key-masking code exists only where the last key tile is ragged (always in the short form)
     const bool ragged = (Nk % KV_TILE) != 0;
     if (D <= 48) {                    // d = 80 spills at two blocks per wave (measured slower)
         const long long wgs2 = (long long)B * heads * ((Nq + 255) / 256);
-        if (force_qb == 2 || (force_qb == 0 && wgs2 >= 512)) {
+        if (wgs2 >= 512) {
             // short context: one query block per wave when that still fills the chip (measured at 32 x 8 x 4096 x 77, d = 40: 63 us
             // against 70-73 us for two blocks per wave — the keys are resident either way, and the smaller workgroup tail wins)
-            if (short_ctx && force_qb == 0 && (long long)B * heads * ((Nq + 127) / 128) / SHORT_PASSES >= 512) return {1, true, true, false};
+            if (short_ctx && (long long)B * heads * ((Nq + 127) / 128) / SHORT_PASSES >= 512) return {1, true, true, false};
             if (short_ctx && wgs2 / SHORT_PASSES >= 512) return {2, true, true, false};
             // long context with at least one 8-wave workgroup per CU: the ping-pong form
             const long long wgs_pp = (long long)B * heads * ((Nq + 511) / 512);
-            if (!short_ctx && (force_pp == 1 || (force_pp < 0 && wgs_pp >= 256 && Nk >= 4 * KV_TILE))) return {2, false, ragged, true};
+            if (!short_ctx && wgs_pp >= 256 && Nk >= 4 * KV_TILE) return {2, false, ragged, true};
             return {2, false, ragged, false};
         }
     }
@@ -789,7 +749,7 @@ extern "C" int dc_attention_bf16(const void* q, const void* k, const void* v, vo
     if (!q || !k || !v || !out || B <= 0 || heads <= 0 || Nq <= 0 || Nk <= 0) return DC_ERR_INVALID;
     if ((q_stride | k_stride | v_stride | o_stride) & 7) return DC_ERR_INVALID;     // 16-byte aligned rows
     AttnArgs a{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)out, B, heads, Nq, Nk,
-               q_stride, k_stride, v_stride, o_stride, scale * 1.4426950408889634f, DC_KNOB("DC_ATTN_XCD", 1)};
+               q_stride, k_stride, v_stride, o_stride, scale * 1.4426950408889634f, 1};
     hipStream_t st = (hipStream_t)stream;
     return with_head_dim(D, [&](auto dc) { return launch<decltype(dc)::value>(a, st); });
 }

@@ -22,19 +22,6 @@
 #include <cstdlib>
 #include <utility>
 
-#ifndef DC_EPI_SPECIALIZE
-#define DC_EPI_SPECIALIZE 1     // developer A/B switch: 0 = every launch takes the generic run-time-flag epilogue
-#endif
-#ifndef DC_CONV_FAST
-#define DC_CONV_FAST 1          // developer A/B switch: 0 = plain maps also take the XOR-swizzled, whole-step K loop
-#endif
-#ifndef DC_SH_HP
-#define DC_SH_HP 160            // halo pixel pitch of the narrow-map (8-wide) pipelined form (developer A/B: 144 / 176 / 192)
-#endif
-#ifndef DC_CONV_PIPE
-#define DC_CONV_PIPE 1          // developer A/B switch for the scheduled K-step (see `mfma_frags`)
-#endif
-
 // Developer-only phase stamps (tools/conv_stamp.py builds this file with -DDC_STAMP into a scratch .so): s_memtime sums of
 // the K loop's barrier waits, its fragment-read + MFMA phases and the halo swaps, plus entry / loop / exit times, written to
 // the (otherwise unused) split-K workspace.  Never defined in the product build.
@@ -94,7 +81,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_tile_kernel(const dc_conv_desc
     constexpr int HALO_MAX = UPS ? (TH / 2 + 2) * 10 : SH ? (TM == 4 ? 200 : ((TH << 1) + 2) * 10) : ((TM == 4 && !FAST) ? 200 : (TH + 2) * 18);   // TM == 4 also serves two stacked 8x8 images (2 x 10 x 10)
     constexpr int NHU = (HALO_MAX * 8 + 255) / 256;   // 16-byte halo units per thread
     constexpr int NB = BN / 32;                       // weight-tile DMA wave-instructions per wave per stage
-    constexpr int HP = FAST ? (SH ? DC_SH_HP : 160) : 128;   // halo pixel-row pitch (bytes)
+    constexpr int HP = FAST ? 160 : 128;              // halo pixel-row pitch (bytes; the narrow-map form too, tried against 144 / 176 / 192)
     constexpr int H_BYTES = HALO_MAX * HP;
     constexpr int B_BYTES = BN * 128;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -119,11 +106,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_tile_kernel(const dc_conv_desc
     const int n_tiles = (d.Cout + BN - 1) / BN;
     const int m_tiles = dual ? d.N / 2 : d.N * tiles_y * tiles_x;
     const int nblk = n_tiles * m_tiles;
-    int bid = blockIdx.x;
-    {   // XCD-aware remap: blocks b, b+8, ... share an XCD (and its L2); give each XCD a contiguous tile range
-        const int xq = nblk >> 3, xr = nblk & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + idx;
-    }
+    const int bid = dc_xcd_remap(blockIdx.x, nblk);
     // Which index runs fastest inside an XCD's contiguous range decides what its L2 shares: n fastest (the default) keeps one pixel
     // tile's halo resident while its N tiles stream the weights; m fastest keeps one WEIGHT tile resident while the pixel tiles walk
     // past it — the right order where the weights are the bigger operand (the 8x8 / 16x16 levels: 29.5 MB of weights against 5-21 MB
@@ -229,11 +212,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_tile_kernel(const dc_conv_desc
         }
     };
     const int last_step = (c_end - c_begin) * 9 - 1;
-#ifndef DC_EXP_NO_DMA
-#define DC_EXP_NO_DMA 0         // developer experiment (wrong results): 1 = weight stages are issued in the prologue only — the
-#endif                          // K loop then runs without any DMA traffic or latency: an upper bound for pipelining changes
     auto issue_b = [&](int step, int slot) {          // step = (cc - c_begin) * 9 + tap ; past-the-end re-reads the last
-        if (DC_EXP_NO_DMA && step >= NSTB - 1) return;
         step = step < last_step ? step : last_step;
         const int cc = c_begin + step / 9, tap = step % 9;
         const long long off = ((long long)tap * Cin + cc * 64) * 2;
@@ -244,7 +223,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_tile_kernel(const dc_conv_desc
     };
 
     auto issue_b_at = [&](int cc, int tap, int slot) {   // the same with (slice, tap) known: no division in the unrolled K loop
-        if (DC_EXP_NO_DMA) return;
         const bool past = cc >= c_end;
         cc = past ? c_end - 1 : cc;
         tap = past ? 8 : tap;
@@ -301,9 +279,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_tile_kernel(const dc_conv_desc
         }
     };
     auto mfma_frags = [&]() {
-#ifdef DC_EXP_PRIO
-        __builtin_amdgcn_s_setprio(DC_EXP_PRIO);
-#endif
 #pragma unroll
         for (int s = 0; s < 2; ++s)
 #pragma unroll
@@ -311,20 +286,15 @@ __global__ __launch_bounds__(256, 2) void conv3x3_tile_kernel(const dc_conv_desc
 #pragma unroll
                 for (int tm = 0; tm < TM; ++tm)
                     acc[tn][tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[s][tn], xf[s][tm], acc[tn][tm], 0, 0, 0);
-#ifdef DC_EXP_PRIO
-        __builtin_amdgcn_s_setprio(0);
-#endif
-        if (DC_CONV_PIPE) {
-            constexpr int NMF = 2 * TN * TM;
-            constexpr int PER = NMF / (NB + 1) > 0 ? NMF / (NB + 1) : 1;
-            __builtin_amdgcn_sched_group_barrier(0x100, 2 * (TN + TM), 0);          // every fragment read first
+        constexpr int NMF = 2 * TN * TM;
+        constexpr int PER = NMF / (NB + 1) > 0 ? NMF / (NB + 1) : 1;
+        __builtin_amdgcn_sched_group_barrier(0x100, 2 * (TN + TM), 0);              // every fragment read first
 #pragma unroll
-            for (int i = 0; i < NB; ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, PER, 0);                // a few MFMAs ...
-                __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);                  // ... then one LDS-DMA piece
-            }
-            __builtin_amdgcn_sched_group_barrier(0x008, NMF - NB * PER, 0);
+        for (int i = 0; i < NB; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, PER, 0);                    // a few MFMAs ...
+            __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);                      // ... then one LDS-DMA piece
         }
+        __builtin_amdgcn_sched_group_barrier(0x008, NMF - NB * PER, 0);
     };
 
     unsigned long long ts0 = 0, ts1 = 0, ts2 = 0, ts3 = 0, ta = 0, tb = 0, tc = 0, s_sync = 0, s_work = 0, s_halo = 0;
@@ -469,7 +439,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_tile_kernel(const dc_conv_desc
         const bool more_c = cc + 1 < c_end;
         for (int tap = 0; tap < 9; ++tap, ++step) {
             DC_NOW(ta);
-            dc_ring_sync<DC_EXP_NO_DMA ? 0 : NB * (NSTB - 2)>(); // this wave's pieces of weight stage `step` have landed and its reads of
+            dc_ring_sync<NB * (NSTB - 2)>();                     // this wave's pieces of weight stage `step` have landed and its reads of
                                                                  // step-1 have returned; after the barrier everyone's have: halo image
                                                                  // visible, slot step-1 free
             DC_NOW(tb);
@@ -643,7 +613,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_tile_kernel(const dc_conv_desc
 // Specialised epilogue mode of a halo-tile launch (0 = generic run-time flags, 1 = plain, 2 = residual).
 int dc_conv3x3_tile_epi(const dc_conv_desc& d)
 {
-    return (!DC_EPI_SPECIALIZE || d.splitk > 1 || d.out_f32 || d.act) ? 0 : (d.residual ? 2 : 1);
+    return (d.splitk > 1 || d.out_f32 || d.act) ? 0 : (d.residual ? 2 : 1);
 }
 
 namespace {
@@ -657,15 +627,10 @@ int launch_tile(const dc_conv_desc& d, hipStream_t st)
     const int nblk = (dual ? d.N / 2 : d.N * (d.Ho / (TH << sh)) * (d.Wo / (16 >> sh))) * dc_cdiv(d.Cout, BN);
     constexpr int HALO_ROWS = UPS ? (TH / 2 + 2) * 10 : SH ? (TM == 4 ? 200 : ((TH << 1) + 2) * 10) : ((TM == 4 && !FAST) ? 200 : (TH + 2) * 18);
     const dim3 grid(nblk, d.splitk > 1 ? d.splitk : 1);
-#ifdef DC_EXP_ONE_WG            // developer experiment: pad the allocation so one workgroup owns the CU
-    const size_t lds = 96 * 1024;
-#else
-    const size_t lds = HALO_ROWS * (FAST ? (SH ? DC_SH_HP : 160) : 128) + NSTB * BN * 128;
-#endif
+    const size_t lds = HALO_ROWS * (FAST ? 160 : 128) + NSTB * BN * 128;
     const int epi = dc_conv3x3_tile_epi(d);
     // tile order inside an XCD's range (see the kernel): pixel tiles fastest when the weight tensor is larger than the activations
-    static const int force_order = DC_KNOB("DC_CONV_ORDER", -1);   // developer A/B knob: 0 = n fastest, 1 = m fastest
-    const int order = force_order >= 0 ? force_order : ((long long)d.Cout * 9 > (long long)d.N * d.H * d.W ? 1 : 0);
+    const int order = (long long)d.Cout * 9 > (long long)d.N * d.H * d.W ? 1 : 0;
 #define DC_TILE_LAUNCH1(GN, EPI)                                                                                \
     do {                                                                                                        \
         auto kern = conv3x3_tile_kernel<TM, TN, GN, NSTB, EPI, FAST, (UPS && !GN), (SH && !GN)>;                                                    \
@@ -702,13 +667,12 @@ int dc_conv3x3_tile_supported(const dc_conv_desc& d)
 
 // Tile-shape decision shared by the launcher and the statistics-chunk query: 4 = 8-row tiles (TM = 4), 2 = 4-row tiles,
 // 8 = two whole 8x8 images per tile (TM = 4, dual).
-// N tile: 160 columns when Cout is a multiple of 160 (all SD-1.5 UNet widths).  DC_CONV_BN128=1 (developer A/B knob) takes the
-// 128-column tile instead wherever Cout is also a multiple of 128 (640, 1280): it affords a 3-stage weight ring at two
-// workgroups per CU where the 160-column tile has room for two stages only.
+// N tile: 160 columns whenever Cout is a multiple of 160 (all SD-1.5 UNet widths), also where Cout is a multiple of 128 as well
+// (640, 1280) and the 128-column tile would afford a 3-stage weight ring at two workgroups per CU (the 160-column tile has room
+// for two stages only).
 static bool use_n160(const dc_conv_desc& d)
 {
-    static const int force128 = DC_KNOB("DC_CONV_BN128", 0);
-    return d.Cout % 160 == 0 && !(force128 && d.Cout % 128 == 0);
+    return d.Cout % 160 == 0;
 }
 
 static int tile_variant(const dc_conv_desc& d)
@@ -743,26 +707,25 @@ int dc_conv3x3_tile_launch(const dc_conv_desc& d, hipStream_t st)
 {
     const bool n160 = use_n160(d);
     const int v = tile_variant(d);
-    if (DC_CONV_FAST && !d.upsample && d.Wo >= 16 && (d.Cout & 7) == 0) {            // plain maps: half-step pipeline (see the kernel comment)
+    if (!d.upsample && d.Wo >= 16 && (d.Cout & 7) == 0) {            // plain maps: half-step pipeline (see the kernel comment)
         // at most one workgroup per CU (one- or two-frame decodes): a four-slot weight ring, three taps of weights in flight
-        static const int deep = DC_KNOB("DC_CONV_DEEP", 1);      // developer A/B knob
         const int th = v == 4 ? 8 : 4, bn = n160 ? 160 : 128;
         const long long wgs = (long long)d.N * (d.Ho / th) * (d.Wo / 16) * dc_cdiv(d.Cout, bn) * (d.splitk > 1 ? d.splitk : 1);
         // Cout <= 32 (UNet conv_out 320 -> 4, VAE conv_out 128 -> 3 + 1): one 32-column N tile instead of a mostly empty 128-column
         // one — a fifth of the MFMA work per pixel tile (the launch is then paced by the GroupNorm+SiLU of its halo, done once)
         if (d.Cout <= 32) return v == 4 ? launch_tile<4, 1, 2, true>(d, st) : launch_tile<2, 1, 2, true>(d, st);
-        if (deep && wgs <= 256) {
+        if (wgs <= 256) {
             if (v == 4) return n160 ? launch_tile<4, 5, 4, true>(d, st) : launch_tile<4, 4, 4, true>(d, st);
             return n160 ? launch_tile<2, 5, 4, true>(d, st) : launch_tile<2, 4, 4, true>(d, st);
         }
         if (v == 4) return n160 ? launch_tile<4, 5, 2, true>(d, st) : launch_tile<4, 4, 2, true>(d, st);
         return n160 ? launch_tile<2, 5, 2, true>(d, st) : launch_tile<2, 4, 2, true>(d, st);
     }
-    if (DC_CONV_FAST && d.upsample && !d.gn_ab && d.Wo >= 16 && (d.Cout & 7) == 0) {       // Upsample2D convs: the same pipeline
+    if (d.upsample && !d.gn_ab && d.Wo >= 16 && (d.Cout & 7) == 0) {       // Upsample2D convs: the same pipeline
         if (v == 4) return n160 ? launch_tile<4, 5, 2, true, true>(d, st) : launch_tile<4, 4, 2, true, true>(d, st);
         return n160 ? launch_tile<2, 5, 2, true, true>(d, st) : launch_tile<2, 4, 2, true, true>(d, st);
     }
-    if (DC_CONV_FAST && d.Wo == 8 && !d.upsample && !d.gn_ab && (d.Cout & 7) == 0) {        // 8x8 maps: the same pipeline
+    if (d.Wo == 8 && !d.upsample && !d.gn_ab && (d.Cout & 7) == 0) {        // 8x8 maps: the same pipeline
         if (v == 8) return n160 ? launch_tile<4, 5, 2, true, false, true>(d, st) : launch_tile<4, 4, 2, true, false, true>(d, st);
         return n160 ? launch_tile<2, 5, 2, true, false, true>(d, st) : launch_tile<2, 4, 2, true, false, true>(d, st);
     }

@@ -167,11 +167,9 @@ int launch_fm(const float* x, long long xbs, const float* w, const float* bias, 
 
 // The MFMA form takes a layer when the GEMM dimensions are whole tiles: Cin a multiple of the 8-channel chunk (>= 16), Cout a
 // multiple of 32, stride 1 | 2 with exact halving, and an output map that splits into 128-pixel (8x8 maps: 64-pixel) tiles.
-// DC_F32CONV_MFMA (developer builds): 0 = never.
 int dc_conv_f32_mfma_wanted(int Cin, int H, int W, int Cout, int stride)
 {
-    static const int mode = DC_KNOB("DC_F32CONV_MFMA", 1);
-    if (!mode || (stride != 1 && stride != 2) || Cin < 16 || Cin % FM_CK || Cout % 32) return 0;
+    if ((stride != 1 && stride != 2) || Cin < 16 || Cin % FM_CK || Cout % 32) return 0;
     if (stride == 2 && ((H | W) & 1)) return 0;
     const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
     const int pt = Ho * Wo >= 128 ? 128 : 64;

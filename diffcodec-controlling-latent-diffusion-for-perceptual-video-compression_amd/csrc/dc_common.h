@@ -29,15 +29,13 @@ struct dc_route {
     int ln_first;   // the LayerNorm finalize pass runs first, into ln_scratch
 };
 
-// Developer A/B switches of the launchers (tile shape, ring depth, kernel selection).  The product library is built WITHOUT
-// DC_DEV_KNOBS, so every DC_KNOB folds to its default and no dispatch decision depends on the environment; scratch builds of
-// tools/ (-DDC_DEV_KNOBS) read the variable once.
-#ifdef DC_DEV_KNOBS
-#include <cstdlib>
-#define DC_KNOB(name, dflt) (getenv(name) ? atoi(getenv(name)) : (dflt))
-#else
-#define DC_KNOB(name, dflt) (dflt)
-#endif
+// XCD-aware block order: the hardware deals workgroups round-robin over the 8 XCDs (blocks b, b + 8, ... share one XCD and its
+// L2), so logical block `bid` of `nblk` is remapped to give each XCD one contiguous range of tiles.
+__host__ __device__ inline int dc_xcd_remap(int bid, int nblk)
+{
+    const int xq = nblk >> 3, xr = nblk & 7, xcd = bid & 7, idx = bid >> 3;
+    return (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + idx;
+}
 
 __device__ __forceinline__ float dc_bf2f(bf16_t v) { return (float)v; }
 __device__ __forceinline__ bf16_t dc_f2bf(float v) { return (bf16_t)v; }   // v_cvt_pk_bf16_f32: RNE, NaN-preserving
@@ -64,17 +62,10 @@ __device__ __forceinline__ float dc_erf_fast(float x)
     const float r = __builtin_fmaf(-(p * t), e, 1.0f);
     return copysignf(r, x);
 }
-#ifndef DC_GELU_VARIANT
-#define DC_GELU_VARIANT 0       // developer experiments only (tools/bench_gemm.py A/B): 1 = identity (upper bound of what a cheaper
-#endif                          // GELU could buy), never built into the product library
 __device__ __forceinline__ float dc_gelu_erf(float x)
 {
 #pragma clang fp contract(off)
-#if DC_GELU_VARIANT == 1
-    return x;
-#else
     return 0.5f * x * (1.0f + dc_erf_fast(x * 0.70710678118654752440f));
-#endif
 }
 
 // Epilogue arithmetic shared by the GEMM / conv kernels, with the fused multiply-adds WRITTEN OUT.  Left to -ffp-contract, hipcc

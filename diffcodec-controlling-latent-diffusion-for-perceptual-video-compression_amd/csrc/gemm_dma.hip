@@ -30,13 +30,6 @@
 #define DC_STAMP_AT(i)
 #endif
 
-#ifndef DC_EPI_SPECIALIZE
-#define DC_EPI_SPECIALIZE 1     // developer A/B switch: 0 = every launch takes the generic run-time-flag epilogue
-#endif
-#ifndef DC_GEMM_PIPE
-#define DC_GEMM_PIPE 1          // developer A/B switch for the scheduled K-step (see `compute`)
-#endif
-
 namespace {
 
 typedef const void __attribute__((address_space(1))) * gptr_t;
@@ -48,10 +41,6 @@ __device__ __forceinline__ void wait_vmcnt()
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-// A_REG: the activation tile goes through registers (global_load_dwordx4 -> ds_write_b128) and only the weight tile by
-// LDS-DMA.  An LDS-DMA wave-instruction costs ~100 issue cycles against ~10 for a register load + 13 for its ds_write,
-// and with both operands on DMA (9 pieces per wave per K-step) the K-loop is DMA-issue-bound (900 vs 640 MFMA cycles);
-// the hybrid issues 5.  Requires NST == 2.
 // EPI: epilogue specialisation chosen by the launcher from the descriptor.  With every fusion a run-time flag, the unrolled
 // (tm, tn) epilogue was 6,300 instructions in 336 basic blocks — a branch (and often a wait) per flag per 4 outputs — and took
 // 10.7k cycles per workgroup against 9k for the whole K loop at K = 320 (phase stamps, tools/gemm_stamp.py).  The common
@@ -59,10 +48,9 @@ __device__ __forceinline__ void wait_vmcnt()
 //   0 generic (run-time flags: row_add, act, fp32 out, split-K, any mix)      1 bias        2 bias + scale + residual
 //   3 folded LayerNorm + bias                                               4 GEGLU       5 folded LayerNorm + GEGLU
 // stats_out / gn_part_out stay run-time in modes 1-2: one workgroup-uniform test outside the loops.
-template <int TM, int TN, int NST, bool A_REG, int EPI>
+template <int TM, int TN, int NST, int EPI>
 __global__ __launch_bounds__(256, 2) void gemm_dma_kernel(const dc_conv_desc d)
 {
-    constexpr bool PIPE = DC_GEMM_PIPE;
     constexpr bool GENERIC = EPI == 0;
     const bool e_geglu = GENERIC ? d.epilogue == 1 : EPI >= 4;
     const bool e_ln = GENERIC ? d.ln_stats != nullptr : (EPI == 3 || EPI == 5);
@@ -75,11 +63,8 @@ __global__ __launch_bounds__(256, 2) void gemm_dma_kernel(const dc_conv_desc d)
     constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
     constexpr int ROWS = BM + BN;
     constexpr int STAGE = ROWS * 128;
-    constexpr int NGW = (A_REG ? BN : ROWS) / 32;     // DMA wave-instructions per wave per stage (8 rows each)
-    constexpr int G0 = A_REG ? BM / 8 : 0;            // first DMA piece (pieces below it are the register-staged A rows)
-    constexpr int PA = BM / 32;
+    constexpr int NGW = ROWS / 32;                    // DMA wave-instructions per wave per stage (8 rows each)
     static_assert(ROWS % 32 == 0 && BN % 32 == 0, "rows per stage must split over 4 waves x 8-row pieces");
-    static_assert(!A_REG || NST == 2, "hybrid staging is double-buffered");
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -95,11 +80,7 @@ __global__ __launch_bounds__(256, 2) void gemm_dma_kernel(const dc_conv_desc d)
     const int n_tiles = (d.Cout + BN - 1) / BN;
     const int m_tiles = (M + BM - 1) / BM;
     const int nblk = n_tiles * m_tiles;
-    int bid = blockIdx.x;
-    {
-        const int xq = nblk >> 3, xr = nblk & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + idx;
-    }
+    const int bid = dc_xcd_remap(blockIdx.x, nblk);
     const int tile_n = bid % n_tiles, tile_m = bid / n_tiles;
     const int m0 = tile_m * BM, n0 = tile_n * BN;
 
@@ -120,7 +101,7 @@ __global__ __launch_bounds__(256, 2) void gemm_dma_kernel(const dc_conv_desc d)
     const int c1_steps = d.C1 >> 6;
 #pragma unroll
     for (int i = 0; i < NGW; ++i) {
-        const int g = G0 + wave + 4 * i;
+        const int g = wave + 4 * i;
         const int row = g * 8 + (lane >> 3);
         const int chunk = (lane & 7) ^ (row & 7);
         ldsoff[i] = g * 1024;
@@ -136,11 +117,7 @@ __global__ __launch_bounds__(256, 2) void gemm_dma_kernel(const dc_conv_desc d)
             src2[i] = nullptr;
         }
     }
-#ifndef DC_EXP_NO_DMA
-#define DC_EXP_NO_DMA 0         // developer experiment (wrong results): 1 = stages are issued in the prologue only
-#endif
     auto issue_stage = [&](int kt, int slot) {
-        if (DC_EXP_NO_DMA && kt >= kt_begin + NST - 1) return;
         kt = kt < kt_end ? kt : kt_end - 1;           // past-the-end stages re-read the last one (keeps vmcnt counts constant)
         char* base = smem + slot * STAGE;
         if (kt < c1_steps) {                          // first K range (the only one without a channel concat): no per-piece select
@@ -151,39 +128,9 @@ __global__ __launch_bounds__(256, 2) void gemm_dma_kernel(const dc_conv_desc d)
         }
 #pragma unroll
         for (int i = 0; i < NGW; ++i) {
-            const bool is_a = (G0 + wave + 4 * i) * 8 < BM;                    // wave-uniform
+            const bool is_a = (wave + 4 * i) * 8 < BM;                    // wave-uniform
             const char* p = is_a ? src2[i] + (long long)(kt - c1_steps) * 128 : src1[i] + (long long)kt * 128;
             __builtin_amdgcn_global_load_lds((gptr_t)p, (lptr_t)(base + ldsoff[i]), 16, 0, 0);
-        }
-    };
-
-    // register-staged A rows (A_REG): thread -> chunk q of rows r0 + 32 i
-    const int aq = tid & 7, ar0 = tid >> 3;
-    const char* a1[PA];
-    const char* a2[PA];
-    u32x4 ra[PA];
-    if (A_REG) {
-#pragma unroll
-        for (int i = 0; i < PA; ++i) {
-            int m = m0 + ar0 + 32 * i;
-            m = m < M ? m : M - 1;
-            a1[i] = (const char*)d.x1 + ((long long)m * d.C1 + aq * 8) * 2;
-            a2[i] = d.x2 ? (const char*)d.x2 + ((long long)m * d.C2 + aq * 8) * 2 : nullptr;
-        }
-    }
-    auto load_a = [&](int kt) {
-#pragma unroll
-        for (int i = 0; i < PA; ++i) {
-            const char* p = kt >= c1_steps ? a2[i] + (long long)(kt - c1_steps) * 128 : a1[i] + (long long)kt * 128;
-            ra[i] = *(const u32x4*)p;
-        }
-    };
-    auto store_a = [&](int slot) {
-        char* sA = smem + slot * STAGE;
-#pragma unroll
-        for (int i = 0; i < PA; ++i) {
-            const int r = ar0 + 32 * i;
-            *(u32x4*)(sA + r * 128 + ((aq ^ (r & 7)) << 4)) = ra[i];
         }
     };
 
@@ -213,7 +160,7 @@ __global__ __launch_bounds__(256, 2) void gemm_dma_kernel(const dc_conv_desc d)
             for (int tn = 0; tn < TN; ++tn) wf[s][tn] = *(const bf16x8*)(sB + ((wn * TN + tn) * 16 + fr) * 128 + swz);
         }
     };
-    auto mfma_frags = [&](bool with_dma) {
+    auto mfma_frags = [&]() {
 #pragma unroll
         for (int s = 0; s < 2; ++s)
 #pragma unroll
@@ -221,23 +168,15 @@ __global__ __launch_bounds__(256, 2) void gemm_dma_kernel(const dc_conv_desc d)
 #pragma unroll
                 for (int tm = 0; tm < TM; ++tm)
                     acc[tn][tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[s][tn], xf[s][tm], acc[tn][tm], 0, 0, 0);
-        if (PIPE) {
-            constexpr int NMF = 2 * TN * TM;
-            constexpr int PER = NMF / (NGW + 1) > 0 ? NMF / (NGW + 1) : 1;
-            __builtin_amdgcn_sched_group_barrier(0x100, 2 * (TN + TM), 0);          // every fragment read first
-            if (with_dma) {
+        constexpr int NMF = 2 * TN * TM;
+        constexpr int PER = NMF / (NGW + 1) > 0 ? NMF / (NGW + 1) : 1;
+        __builtin_amdgcn_sched_group_barrier(0x100, 2 * (TN + TM), 0);              // every fragment read first
 #pragma unroll
-                for (int i = 0; i < NGW; ++i) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, PER, 0);            // a few MFMAs ...
-                    __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);              // ... then one LDS-DMA piece
-                }
-                __builtin_amdgcn_sched_group_barrier(0x008, NMF - NGW * PER, 0);
-            }
+        for (int i = 0; i < NGW; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, PER, 0);                    // a few MFMAs ...
+            __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);                      // ... then one LDS-DMA piece
         }
-    };
-    auto compute = [&](int slot) {
-        load_frags(slot);
-        mfma_frags(false);
+        __builtin_amdgcn_sched_group_barrier(0x008, NMF - NGW * PER, 0);
     };
 
     // bias for this lane's output channels: fetched now so its latency hides under the K loop
@@ -269,37 +208,17 @@ __global__ __launch_bounds__(256, 2) void gemm_dma_kernel(const dc_conv_desc d)
     }
 
     // ---- pipeline
-    if (A_REG) {
-        issue_stage(kt_begin, 0);
-        load_a(kt_begin);
-        store_a(0);
-        wait_vmcnt<0>();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        for (int k = 0; k < nk; ++k) {
-            const bool more = k + 1 < nk;
-            if (more) {
-                issue_stage(kt_begin + k + 1, (k + 1) & 1);      // slot (k+1)&1 was last read in step k-1: free since the barrier
-                load_a(kt_begin + k + 1);
-            }
-            compute(k & 1);
-            if (more) store_a((k + 1) & 1);
-            dc_ring_sync<0>();                                  // this wave's weight pieces of stage k+1 have landed, its A rows are
-                                                                // written and its reads of stage k have returned
-        }
-    } else {
 #pragma unroll
-        for (int s = 0; s < NST - 1; ++s) issue_stage(kt_begin + s, s);
-        for (int k = 0; k < nk; ++k) {
-            dc_ring_sync<DC_EXP_NO_DMA ? 0 : NGW * (NST - 2)>();   // this wave's pieces of stage k have landed and its reads of stage k-1 have
-                                                          // returned; after the barrier: everyone else's too
-            if (k == 0) DC_STAMP_AT(1);
-            load_frags(k % NST);
-            issue_stage(kt_begin + k + NST - 1, (k + NST - 1) % NST);
-            mfma_frags(true);
-        }
-        wait_vmcnt<0>();
+    for (int s = 0; s < NST - 1; ++s) issue_stage(kt_begin + s, s);
+    for (int k = 0; k < nk; ++k) {
+        dc_ring_sync<NGW * (NST - 2)>();               // this wave's pieces of stage k have landed and its reads of stage k-1 have
+                                                      // returned; after the barrier: everyone else's too
+        if (k == 0) DC_STAMP_AT(1);
+        load_frags(k % NST);
+        issue_stage(kt_begin + k + NST - 1, (k + NST - 1) % NST);
+        mfma_frags();
     }
+    wait_vmcnt<0>();
     DC_STAMP_AT(2);
 
     const long long slab = (long long)d.N * d.Ho * d.Wo * d.Cout;   // elements per split-K slab
@@ -479,7 +398,7 @@ __global__ __launch_bounds__(256, 2) void gemm_dma_kernel(const dc_conv_desc d)
     }
 }
 
-template <int TM, int TN, int NST, bool A_REG, int EPI>
+template <int TM, int TN, int NST, int EPI>
 int launch_gemm_e(const dc_conv_desc& d, hipStream_t st)
 {
     constexpr int BM = 2 * TM * 16, BN = 2 * TN * 16;
@@ -487,7 +406,7 @@ int launch_gemm_e(const dc_conv_desc& d, hipStream_t st)
     const int nblk = dc_cdiv(M, BM) * dc_cdiv(d.Cout, BN);
     const dim3 grid(nblk, d.splitk > 1 ? d.splitk : 1);
     const size_t lds = (size_t)NST * (BM + BN) * 128;
-    auto kern = gemm_dma_kernel<TM, TN, NST, A_REG, EPI>;
+    auto kern = gemm_dma_kernel<TM, TN, NST, EPI>;
     static std::atomic<unsigned long long> attr_done{0};
     dc_set_max_dyn_lds((const void*)kern, (int)lds, attr_done);
     hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, d);
@@ -497,28 +416,23 @@ int launch_gemm_e(const dc_conv_desc& d, hipStream_t st)
 // epilogue mode of a descriptor (see the kernel's EPI comment); 0 = the generic run-time-flag epilogue
 int epi_mode(const dc_conv_desc& d)
 {
-    if (!DC_EPI_SPECIALIZE) return 0;
     if (d.out_f32 || d.splitk > 1 || d.row_add || d.act) return 0;
     if (d.epilogue == 1) return (d.residual || d.stats_out || d.gn_part_out) ? 0 : (d.ln_stats ? 5 : 4);
     if (d.ln_stats) return (d.residual || d.stats_out || d.gn_part_out) ? 0 : 3;
     return d.residual ? 2 : 1;
 }
 
-// PROD: the four tile shapes the dispatcher uses get every specialised epilogue; developer-knob shapes only the generic one
-template <int TM, int TN, int NST, bool A_REG = false, bool PROD = false>
+template <int TM, int TN, int NST>
 int launch_gemm(const dc_conv_desc& d, hipStream_t st)
 {
-    if constexpr (PROD) {
-        switch (epi_mode(d)) {
-            case 1: return launch_gemm_e<TM, TN, NST, A_REG, 1>(d, st);
-            case 2: return launch_gemm_e<TM, TN, NST, A_REG, 2>(d, st);
-            case 3: return launch_gemm_e<TM, TN, NST, A_REG, 3>(d, st);
-            case 4: return launch_gemm_e<TM, TN, NST, A_REG, 4>(d, st);
-            case 5: return launch_gemm_e<TM, TN, NST, A_REG, 5>(d, st);
-            default: break;
-        }
+    switch (epi_mode(d)) {
+        case 1: return launch_gemm_e<TM, TN, NST, 1>(d, st);
+        case 2: return launch_gemm_e<TM, TN, NST, 2>(d, st);
+        case 3: return launch_gemm_e<TM, TN, NST, 3>(d, st);
+        case 4: return launch_gemm_e<TM, TN, NST, 4>(d, st);
+        case 5: return launch_gemm_e<TM, TN, NST, 5>(d, st);
+        default: return launch_gemm_e<TM, TN, NST, 0>(d, st);
     }
-    return launch_gemm_e<TM, TN, NST, A_REG, 0>(d, st);
 }
 
 }  // namespace
@@ -548,7 +462,8 @@ int dc_gemm_rowpanel_launch(const dc_conv_desc& d, int epi, hipStream_t st);
 int dc_gemm_rowpanel_gn_chunks(const dc_conv_desc& d);
 
 // The decision of dc_gemm_dma_launch for a 1x1 descriptor: kernel, gemm_dma template (variant = TM*10000 + TN*1000 + stages*100 +
-// A_REG*10 + PROD), epilogue mode, and whether the LayerNorm finalize runs first.  The launch and dc_conv_route both read it.
+// A_REG*10 + PROD, where the A_REG digit is always 0 and the PROD digit always 1: kept so that recorded routes stay valid),
+// epilogue mode, and whether the LayerNorm finalize runs first.  The launch and dc_conv_route both read it.
 int dc_gemm_dma_route(const dc_conv_desc& d, dc_route& r)
 {
     const long long M = (long long)d.N * d.Ho * d.Wo;
@@ -588,9 +503,8 @@ int dc_gemm_dma_route(const dc_conv_desc& d, dc_route& r)
     if (d.ln_stats && !d.ln_colsum) return DC_ERR_INVALID;
     if (d.stats_out && d.epilogue != 0) return DC_ERR_INVALID;
     r.kernel = DC_ROUTE_GEMM_DMA;
-    auto pick = [&](int tm, int tn, int nst, int a_reg, int prod) {
-        r.variant = tm * 10000 + tn * 1000 + nst * 100 + a_reg * 10 + prod;
-        if (!prod) r.epi = 0;                                   // developer-knob shapes: the generic epilogue only
+    auto pick = [&](int tm, int tn, int nst) {
+        r.variant = tm * 10000 + tn * 1000 + nst * 100 + 1;
         return DC_OK;
     };
     const bool n160 = (d.Cout % 160 == 0) && d.epilogue == 0;
@@ -598,26 +512,16 @@ int dc_gemm_dma_route(const dc_conv_desc& d, dc_route& r)
     const long long big = ((M + 127) / 128) * ((d.Cout + bn - 1) / bn) * (d.splitk > 1 ? d.splitk : 1);
     // 2 LDS stages for the big tiles keep two workgroups resident per CU (2 waves per SIMD: one computes while the
     // other waits for its DMA); the small tiles afford 3 stages at the same residency.
-    static const int force_nst = DC_KNOB("DC_GEMM_NST", 0);   // developer knobs
-    static const int force_small = DC_KNOB("DC_GEMM_SMALL", 0);
-    if (force_small == 1) return n160 ? pick(2, 5, 2, 0, 0) : pick(2, 4, 3, 0, 0);
-    if (force_small == 2) return pick(2, 2, 3, 0, 0);
-    if (force_small == 3) return pick(2, 4, 2, 0, 0);
-    static const int hybrid = DC_KNOB("DC_GEMM_HYBRID", 0);   // measured: no gain over all-DMA
-    if (hybrid && big >= 256) return n160 ? pick(4, 5, 2, 1, 0) : pick(4, 4, 2, 1, 0);
-    if (hybrid) return n160 ? pick(2, 5, 2, 1, 0) : pick(2, 4, 2, 1, 0);
-    if (force_nst == 4 && big >= 256) return n160 ? pick(4, 5, 4, 0, 0) : pick(4, 4, 4, 0, 0);
-    if (force_nst == 3 && big >= 256) return n160 ? pick(4, 5, 3, 0, 0) : pick(4, 4, 3, 0, 0);
-    if (big >= 256) return n160 ? pick(4, 5, 2, 0, 1) : pick(4, 4, 2, 0, 1);
+    // (Staging the activation tile through registers and only the weights by LDS-DMA was measured: no gain over all-DMA.)
+    if (big >= 256) return n160 ? pick(4, 5, 2) : pick(4, 4, 2);
     // Grids that cannot even put one workgroup on every CU (the 16x16 / 8x8 levels of a one- or two-frame decode) are bound by
     // the serial K loop: one LDS-DMA round trip per 64-wide step.  They take a deeper ring — the whole CU's LDS for one
     // workgroup, three or four stages in flight instead of one — with the same tile shape (so the statistics / GroupNorm partial
     // layouts are unchanged).  M = 512, N = 1280, K = 1280: 26 -> see tools/bench_gemm.py 2.
-    static const int deep = DC_KNOB("DC_GEMM_DEEP", 1);        // developer A/B knob
     const long long small = ((M + 63) / 64) * ((d.Cout + bn - 1) / bn) * (d.splitk > 1 ? d.splitk : 1);
     const int KT = (d.C1 + d.C2) >> 6;
-    if (deep && small <= 256 && KT >= 6) return n160 ? pick(2, 5, 4, 0, 1) : pick(2, 4, 5, 0, 1);
-    return n160 ? pick(2, 5, 2, 0, 1) : pick(2, 4, 3, 0, 1);
+    if (small <= 256 && KT >= 6) return n160 ? pick(2, 5, 4) : pick(2, 4, 5);
+    return n160 ? pick(2, 5, 2) : pick(2, 4, 3);
 }
 
 namespace {
@@ -625,28 +529,14 @@ namespace {
 int launch_gemm_variant(const dc_conv_desc& d, int variant, hipStream_t st)
 {
     switch (variant) {
-#define DC_DMA_VARIANT(TM, TN, NST, AR, PR) \
-    case TM * 10000 + TN * 1000 + NST * 100 + AR * 10 + PR: return launch_gemm<TM, TN, NST, (AR != 0), (PR != 0)>(d, st);
-        DC_DMA_VARIANT(4, 5, 2, 0, 1)
-        DC_DMA_VARIANT(4, 4, 2, 0, 1)
-        DC_DMA_VARIANT(2, 5, 4, 0, 1)
-        DC_DMA_VARIANT(2, 4, 5, 0, 1)
-        DC_DMA_VARIANT(2, 5, 2, 0, 1)
-        DC_DMA_VARIANT(2, 4, 3, 0, 1)
-#ifdef DC_DEV_KNOBS
-        DC_DMA_VARIANT(2, 5, 2, 0, 0)
-        DC_DMA_VARIANT(2, 4, 3, 0, 0)
-        DC_DMA_VARIANT(2, 2, 3, 0, 0)
-        DC_DMA_VARIANT(2, 4, 2, 0, 0)
-        DC_DMA_VARIANT(4, 5, 2, 1, 0)
-        DC_DMA_VARIANT(4, 4, 2, 1, 0)
-        DC_DMA_VARIANT(2, 5, 2, 1, 0)
-        DC_DMA_VARIANT(2, 4, 2, 1, 0)
-        DC_DMA_VARIANT(4, 5, 4, 0, 0)
-        DC_DMA_VARIANT(4, 4, 4, 0, 0)
-        DC_DMA_VARIANT(4, 5, 3, 0, 0)
-        DC_DMA_VARIANT(4, 4, 3, 0, 0)
-#endif
+#define DC_DMA_VARIANT(TM, TN, NST) \
+    case TM * 10000 + TN * 1000 + NST * 100 + 1: return launch_gemm<TM, TN, NST>(d, st);
+        DC_DMA_VARIANT(4, 5, 2)
+        DC_DMA_VARIANT(4, 4, 2)
+        DC_DMA_VARIANT(2, 5, 4)
+        DC_DMA_VARIANT(2, 4, 5)
+        DC_DMA_VARIANT(2, 5, 2)
+        DC_DMA_VARIANT(2, 4, 3)
 #undef DC_DMA_VARIANT
         default: return DC_ERR_INVALID;
     }

@@ -36,9 +36,6 @@ typedef const void __attribute__((address_space(1))) * gptr_t;
 typedef void __attribute__((address_space(3))) * lptr_t;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 
-#ifndef P8_ABL
-#define P8_ABL 0                                    // developer timing ablations (wrong results): 1 no DMA in the K loop, 2 no fragment reads, 4 no MFMAs, 8 no barriers, 16 no output stores
-#endif
 constexpr int P8_HALF = 128 * 128;                  // bytes of a half tile
 constexpr int P8_BUF = 4 * P8_HALF;                 // one K tile
 constexpr int P8_RING = 2 * P8_BUF;                 // 128 KB
@@ -47,10 +44,11 @@ constexpr int P8_PAR_BIAS = P8_STAGE_MAX;           // fp32 [256] bias, [256] we
 constexpr int P8_PAR_CS = P8_PAR_BIAS + 1024;
 constexpr int P8_PAR_LN = P8_PAR_CS + 1024;
 constexpr int P8_LDS = P8_PAR_LN + 2048;
+constexpr int P8_GM = 8;                            // row tiles per group of the tile order (see gemm_p8_kernel)
 
 __device__ __forceinline__ void p8_barrier()
 {
-    if (!(P8_ABL & 8)) __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 }
 template <int N>
@@ -67,7 +65,7 @@ __device__ __forceinline__ void p8_wait_lgkm()
 
 // EPI: 1 bias, 3 folded LayerNorm + bias, 4 GEGLU, 5 folded LayerNorm + GEGLU (the numbering of gemm_dma.hip)
 template <int EPI>
-__global__ __launch_bounds__(512, 2) void gemm_p8_kernel(const dc_conv_desc d, const int gm)
+__global__ __launch_bounds__(512, 2) void gemm_p8_kernel(const dc_conv_desc d)
 {
     constexpr bool e_geglu = EPI >= 4, e_ln = EPI == 3 || EPI == 5;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -82,26 +80,16 @@ __global__ __launch_bounds__(512, 2) void gemm_p8_kernel(const dc_conv_desc d, c
     const int nk = K >> 6;
     const int n_tiles = (d.Cout + 255) >> 8;                // the last N tile may be half full (Cout % 256 == 128): clamped W rows, guarded stores
     const int nblk = n_tiles * (M >> 8);
-    int bid = blockIdx.x;
-    {
-        const int xq = nblk >> 3, xr = nblk & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + idx;
-    }
-    // Tile order inside an XCD's contiguous range: groups of `gm` row tiles, the row tile the fastest index inside a group, so the 32
-    // workgroups an XCD runs together form a gm x (32 / gm) block of tiles and share gm X panels + 32 / gm W panels in its L2
-    // (column-fastest order: 1 + 32 panels — 7.4x the algorithmic bytes from beyond L2 at N = 10240).
-    int tile_m, tile_n;
-    if (gm > 0) {
-        const int per_group = gm * n_tiles;
-        const int group = bid / per_group, in_group = bid - group * per_group;
-        const int first_m = group * gm;
-        const int rows = min(gm, (M >> 8) - first_m);
-        tile_m = first_m + in_group % rows;
-        tile_n = in_group / rows;
-    } else {
-        tile_n = bid % n_tiles;
-        tile_m = bid / n_tiles;
-    }
+    const int bid = dc_xcd_remap(blockIdx.x, nblk);
+    // Tile order inside an XCD's contiguous range: groups of P8_GM = 8 row tiles, the row tile the fastest index inside a group, so
+    // the 32 workgroups an XCD runs together form an 8 x 4 block of tiles and share 8 X panels + 4 W panels in its L2 (column-fastest
+    // order: 1 + 32 panels — 7.4x the algorithmic bytes from beyond L2 at N = 10240).
+    const int per_group = P8_GM * n_tiles;
+    const int group = bid / per_group, in_group = bid - group * per_group;
+    const int first_m = group * P8_GM;
+    const int rows = min(P8_GM, (M >> 8) - first_m);
+    const int tile_m = first_m + in_group % rows;
+    const int tile_n = in_group / rows;
     const int m0 = tile_m << 8, n0 = tile_n << 8;
 
     // ---- DMA sources.  Piece j of a half tile = its rows [8j, 8j+8); this wave issues pieces `wave` and `wave + 8`; lane s ->
@@ -180,14 +168,12 @@ __global__ __launch_bounds__(512, 2) void gemm_p8_kernel(const dc_conv_desc d, c
     if (grp == 1) p8_barrier();                      // group 1 runs one barrier behind
 
     auto read_x = [&](const char* buf, int half_off) {
-        if ((P8_ABL & 2) && buf != smem) return;
 #pragma unroll
         for (int s = 0; s < 2; ++s)
 #pragma unroll
             for (int tm = 0; tm < 4; ++tm) xa[s][tm] = *(const bf16x8*)(buf + half_off + xa_off[s] + tm * 2048);
     };
     auto read_w = [&](bf16x8 (&wb)[2][2], const char* buf, int half_off) {
-        if ((P8_ABL & 2) && buf != smem) return;
 #pragma unroll
         for (int s = 0; s < 2; ++s)
 #pragma unroll
@@ -195,10 +181,6 @@ __global__ __launch_bounds__(512, 2) void gemm_p8_kernel(const dc_conv_desc d, c
     };
     auto quadrant = [&](auto nh_c, auto mh_c, const bf16x8 (&wb)[2][2]) {
         constexpr int nh = decltype(nh_c)::value, mh = decltype(mh_c)::value;
-        if (P8_ABL & 4) {
-            asm volatile("" ::"v"(xa[0][0]), "v"(xa[1][3]), "v"(wb[0][0]), "v"(wb[1][1]));
-            return;
-        }
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int s = 0; s < 2; ++s)
@@ -223,27 +205,27 @@ __global__ __launch_bounds__(512, 2) void gemm_p8_kernel(const dc_conv_desc d, c
         read_w(wb0, buf, 1 * P8_HALF);
         __builtin_amdgcn_sched_barrier(0);
         read_x(buf, 0);
-        if (n1 && !(P8_ABL & 1)) issue_half(3, t + 1, P ^ 1);
+        if (n1) issue_half(3, t + 1, P ^ 1);
         p8_wait_lgkm();
         p8_barrier();
         quadrant(I0{}, I0{}, wb0);
         p8_barrier();
         // phase 2: W cols 32-63
         read_w(wb1, buf, 2 * P8_HALF);
-        if (n2 && !(P8_ABL & 1)) issue_half(0, t + 2, P);
+        if (n2) issue_half(0, t + 2, P);
         p8_wait_lgkm();
         p8_barrier();
         quadrant(I1{}, I0{}, wb1);
         p8_barrier();
         // phase 3: X rows 64-127
         read_x(buf, 3 * P8_HALF);
-        if (n2 && !(P8_ABL & 1)) issue_half(1, t + 2, P);
+        if (n2) issue_half(1, t + 2, P);
         p8_wait_lgkm();
         p8_barrier();
         quadrant(I1{}, I1{}, wb1);
         p8_barrier();
         // phase 4: no reads (W cols 0-31 are still in registers); all of tile t+1 must have landed before the next phase reads it
-        if (n2 && !(P8_ABL & 1)) issue_half(2, t + 2, P);
+        if (n2) issue_half(2, t + 2, P);
         if (n2) p8_wait_vm_lgkm<6>();
         else p8_wait_vm_lgkm<0>();
         p8_barrier();
@@ -312,7 +294,6 @@ __global__ __launch_bounds__(512, 2) void gemm_p8_kernel(const dc_conv_desc d, c
     constexpr int pieces = OC / 8;                   // 16-byte pieces per staged row
     for (int i = tid; i < 256 * pieces; i += 512) {
         const int row = i / pieces, pc = i - row * pieces;
-        if ((P8_ABL & 16) && row != 1000) continue;
         if (col0 + pc * 8 < out_cols)
             *(u32x4*)(o + (long long)(m0 + row) * out_cols + col0 + pc * 8) = dc_stage_unswz(*(const u32x4*)(smem + row * PITCH + pc * 16), row);
     }
@@ -323,30 +304,26 @@ int launch_p8(const dc_conv_desc& d, hipStream_t st)
 {
     const long long M = (long long)d.N * d.Ho * d.Wo;
     const int nblk = (int)(M >> 8) * ((d.Cout + 255) >> 8);
-    static const int gm = DC_KNOB("DC_P8_GM", 8);           // developer A/B knob: 0 = column-fastest order
     auto kern = gemm_p8_kernel<EPI>;
     static std::atomic<unsigned long long> attr_done{0};
     dc_set_max_dyn_lds((const void*)kern, P8_LDS, attr_done);
-    hipLaunchKernelGGL(kern, dim3(nblk), dim3(512), P8_LDS, st, d, gm);
+    hipLaunchKernelGGL(kern, dim3(nblk), dim3(512), P8_LDS, st, d);
     return dc_launch_status();
 }
 
 }  // namespace
 
 // The 256 x 256 kernel takes a launch when its epilogue modes apply (no residual, no statistics), the operands are whole tiles,
-// and the tile grid fills the chip for more than one round.  DC_GEMM_P8: 0 = never (A/B), 1 = default rule, 2 = whenever legal.
+// and the tile grid fills the chip for more than one round (K >= 640, at least 448 tiles).
 int dc_gemm_p8_wanted(const dc_conv_desc& d, int epi)
 {
-    static const int mode = DC_KNOB("DC_GEMM_P8", 1);
-    static const int min_k = DC_KNOB("DC_GEMM_P8_MIN_K", 640);
-    static const int min_tiles = DC_KNOB("DC_GEMM_P8_MIN_TILES", 448);
-    if (mode == 0 || !(epi == 1 || epi == 3 || epi == 4 || epi == 5)) return 0;
+    constexpr int min_k = 640, min_tiles = 448;
+    if (!(epi == 1 || epi == 3 || epi == 4 || epi == 5)) return 0;
     if (d.ksize != 1 || d.gn_ab || d.splitk > 1 || d.out_f32 || d.C2 != 0 || d.residual || d.stats_out || d.gn_part_out) return 0;
     if (d.ln_stats && d.ln_parts > 0) return 0;             // the dispatcher finalizes first and comes back with pairs
     const int K = d.C1;
     const long long M = (long long)d.N * d.Ho * d.Wo;
     if (K < 128 || (K & 63) || (M & 255) || (d.Cout & 127)) return 0;
-    if (mode == 2) return 1;
     const long long tiles = (M >> 8) * ((d.Cout + 255) >> 8);
     if ((d.Cout & 255) && d.Cout < 1792) return 0;          // a half-full last tile only where it is <= 1/15 of the columns' work
     return K >= min_k && tiles >= min_tiles;

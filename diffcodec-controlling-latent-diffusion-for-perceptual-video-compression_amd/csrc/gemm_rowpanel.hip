@@ -48,14 +48,6 @@
 #define RP_STAMP_AT(i)
 #endif
 
-// Developer experiments (scratch builds of tools/build_dev.sh only; wrong results): which resource bounds a launch?
-#ifndef DC_EXP_RP_NOSTORE
-#define DC_EXP_RP_NOSTORE 0     // 1: the row stores are compiled out (everything else, staging reads included, stays)
-#endif
-#ifndef DC_EXP_RP_NOMFMA
-#define DC_EXP_RP_NOMFMA 0      // 1: one MFMA per k-step instead of eight
-#endif
-
 namespace {
 
 typedef const void __attribute__((address_space(1))) * gptr_t;
@@ -246,10 +238,7 @@ __global__ __launch_bounds__(512, 2) void gemm_rowpanel_kernel(const dc_conv_des
             for (int tn = 0; tn < RP_TN; ++tn)
 #pragma unroll
                 for (int tm = 0; tm < RP_TM; ++tm)
-                    if (!DC_EXP_RP_NOMFMA || (tn == 0 && tm == 0))
-                        acc[tn][tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[k & 1][tn], xf[tm][k], acc[tn][tm], 0, 0, 0);
-                    else
-                        asm volatile("" ::"v"(wf[k & 1][tn]), "v"(xf[tm][k]));      // operands stay fetched
+                    acc[tn][tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[k & 1][tn], xf[tm][k], acc[tn][tm], 0, 0, 0);
             if (k + 1 < RP_KS) __builtin_amdgcn_sched_group_barrier(0x100, RP_TN, 0);       // the next step's reads first ...
             __builtin_amdgcn_sched_group_barrier(0x008, RP_TN * RP_TM, 0);                  // ... then this step's MFMAs
         }
@@ -325,7 +314,7 @@ __global__ __launch_bounds__(512, 2) void gemm_rowpanel_kernel(const dc_conv_des
                 const int row = (lane >> 2) + 16 * i, c = lane & 3;
                 u32x4 v = *(const u32x4*)(stg + row * 64 + ((c ^ ((row >> 1) & 3)) << 4));
                 if ((row >> 3) & 1) v = u32x4{v[2], v[3], v[0], v[1]};
-                if (!DC_EXP_RP_NOSTORE || v[0] == 0x12345678u) *(u32x4*)(o + (mw + row) * out_cols + s * (RP_SC / 2) + c * 8) = v;
+                *(u32x4*)(o + (mw + row) * out_cols + s * (RP_SC / 2) + c * 8) = v;
             }
         } else {
 #pragma unroll
@@ -333,7 +322,7 @@ __global__ __launch_bounds__(512, 2) void gemm_rowpanel_kernel(const dc_conv_des
                 const int row = (lane >> 3) + 8 * i, c = lane & 7;
                 u32x4 v = *(const u32x4*)(stg + row * 128 + ((c ^ (row & 7)) << 4));
                 if (i & 1) v = u32x4{v[2], v[3], v[0], v[1]};
-                if (!DC_EXP_RP_NOSTORE || v[0] == 0x12345678u) *(u32x4*)(o + (mw + row) * out_cols + s * RP_SC + c * 8) = v;
+                *(u32x4*)(o + (mw + row) * out_cols + s * RP_SC + c * 8) = v;
             }
         }
         RP_STAMP_AT(4 + 3 * s);
@@ -388,11 +377,9 @@ int dc_gemm_rowpanel_gn_chunks(const dc_conv_desc& d)
 // Takes a launch when K = 320 (one source; load-side transform: none, or a GroupNorm affine without SiLU), a specialised epilogue mode applies, the columns split
 // into whole 64-wide stages and the row panels fill the chip (>= one workgroup per CU).  Never depends on whether the optional
 // statistics outputs are set, so that the chunk query and the launch agree.
-// DC_GEMM_ROWPANEL (developer builds): 0 = never.
 int dc_gemm_rowpanel_wanted(const dc_conv_desc& d, int epi)
 {
-    static const int mode = DC_KNOB("DC_GEMM_ROWPANEL", 1);
-    if (mode == 0 || epi < 1 || epi > 5 || d.ksize != 1 || d.splitk > 1 || d.out_f32) return 0;
+    if (epi < 1 || epi > 5 || d.ksize != 1 || d.splitk > 1 || d.out_f32) return 0;
     if (d.gn_ab && (d.gn_silu || d.gn_batch <= 0)) return 0;           // the affine on load only (the X prologue has no SiLU)
     if (d.ln_parts > DC_LN_PARTS_MAX) return 0;                        // (the dispatcher finalizes first and comes back with pairs)
     if (d.C1 != RP_K || d.C2 != 0 || d.x2 || !d.bias) return 0;

@@ -74,11 +74,7 @@ __global__ __launch_bounds__(512, 2) void gemm_wide_kernel(const dc_conv_desc d)
     const int n_tiles = (d.Cout + BN - 1) / BN;
     const int m_tiles = (M + BM - 1) / BM;
     const int nblk = n_tiles * m_tiles;
-    int bid = blockIdx.x;
-    {
-        const int xq = nblk >> 3, xr = nblk & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + idx;
-    }
+    const int bid = dc_xcd_remap(blockIdx.x, nblk);
     const int tile_n = bid % n_tiles, tile_m = bid / n_tiles;
     const int m0 = tile_m * BM, n0 = tile_n * BN;
 
@@ -346,19 +342,16 @@ int dc_gemm_wide_gn_chunks(const dc_conv_desc& d)
 
 // The wide kernel takes a launch when the specialised epilogue modes apply, K is long enough for the 3-stage ring to pay for
 // the unoverlapped prologue / epilogue of a one-workgroup-per-CU kernel, and the tile grid fills the chip.
-// DC_GEMM_WIDE: 0 = never (A/B), 1 = default rule, 2 = whenever legal.
 int dc_gemm_wide_wanted(const dc_conv_desc& d, int epi)
 {
-    static const int mode = DC_KNOB("DC_GEMM_WIDE", 1);
-    static const int min_k = DC_KNOB("DC_GEMM_WIDE_MIN_K", 640);
-    if (mode == 0 || epi < 1 || epi > 5 || d.ksize != 1 || d.gn_ab || d.splitk > 1 || d.out_f32) return 0;
+    constexpr int min_k = 640;
+    if (epi < 1 || epi > 5 || d.ksize != 1 || d.gn_ab || d.splitk > 1 || d.out_f32) return 0;
     const int K = d.C1 + d.C2;
     const long long M = (long long)d.N * d.Ho * d.Wo;
     const bool geglu = epi >= 4;
     const int bn = (!geglu && d.Cout % 160 == 0) ? 160 : 128;
     if (d.Cout % bn) return 0;                              // whole N tiles only (the 128-row kernel clamps ragged ones)
     if ((d.stats_out || d.gn_part_out) && ((long long)d.Ho * d.Wo) % 256) return 0;
-    if (mode == 2) return M >= 256;
     const long long tiles = ((M + 255) / 256) * (d.Cout / bn);
     // measured (tools/bench_gemm.py, same box, model batch 32): +4..13 % for K 640-2560, 0..-2 % at K 640 x N 640, -4 % at K 5120
     return K >= min_k && K <= 2560 && M % 256 == 0 && tiles >= 192;

@@ -62,11 +62,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const dc_conv_desc d)
     const int n_tiles = (d.Cout + BN - 1) / BN;
     const int m_tiles = (M + BM - 1) / BM;
     const int nblk = n_tiles * m_tiles;
-    int bid = blockIdx.x;
-    {
-        const int xq = nblk >> 3, xr = nblk & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + idx;
-    }
+    const int bid = dc_xcd_remap(blockIdx.x, nblk);
     const int tile_n = bid % n_tiles;
     const int tile_m = bid / n_tiles;
     const int m0 = tile_m * BM;

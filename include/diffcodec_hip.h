@@ -131,7 +131,8 @@ int dc_conv_igemm_bf16(const dc_conv_desc* desc, void* stream);
  * Returns what the launch would return for its descriptor checks (0 or DC_ERR_INVALID; operand checks that do not steer the
  * route — splitk_ws and ln_scratch being set — are left to the launch) and fills info[DC_ROUTE_INFO_INTS]:
  *   info[0] kernel: one of DC_ROUTE_*;
- *   info[1] variant: gemm_dma TM*10000 + TN*1000 + stages*100 + A_REG*10 + PROD (its template); igemm TM*10 + TN;
+ *   info[1] variant: gemm_dma TM*10000 + TN*1000 + stages*100 + A_REG*10 + PROD (its template; the A_REG digit is always 0 and
+ *           the PROD digit always 1, kept so that recorded routes stay valid); igemm TM*10 + TN;
  *           conv3x3_tile its tile rows (2 / 4, 8 = two 8x8 images per tile); 0 for the other kernels;
  *   info[2] epilogue mode (gemm_dma family and conv3x3_tile: the specialised epilogue; 0 = generic run-time flags);
  *   info[3] effective split-K (after shrinking to the fixpoint where every split owns a non-empty K range);
@@ -199,7 +200,7 @@ int dc_layernorm_bf16(const void* x, const float* gamma, const float* beta, void
 int dc_attention_bf16(const void* q, const void* k, const void* v, void* out, int B, int heads, int Nq, int Nk, int D,
                       long long q_stride, long long k_stride, long long v_stride, long long o_stride, float scale,
                       void* stream);
-/* The form dc_attention_bf16 launches for a shape, without launching anything (host code; reads the same developer knobs).
+/* The form dc_attention_bf16 launches for a shape, without launching anything (host code; the same form rule as the launch).
  * Returns 0, or DC_ERR_INVALID for a shape the launch would refuse, and fills info[DC_ATTN_ROUTE_INFO_INTS] with the template
  * arguments of the attn_kernel<D, QB, SHORT, RAGGED, PP> instance: head dim, 32-query blocks per wave, short-context form (both
  * key tiles resident), ragged last key tile (key masking compiled in), ping-pong form. */

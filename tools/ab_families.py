@@ -1,5 +1,7 @@
-"""Developer tool: same-box A/B of build / run-time variants, per kernel family (in-situ launch timer of bench.py).
-usage: python tools/ab_families.py name=ENV1=v,ENV2=v ...   (name 'base' = no overrides)"""
+"""Developer tool: same-box A/B of two builds, per kernel family (in-situ launch timer of bench.py).  bench.py loads the library of
+its own tree, so a variant is another commit checked out in a git worktree and built there (python -m diffcodec_amd.build);
+AB_TREE=<worktree> runs that tree's bench.py.
+usage: python tools/ab_families.py base parent=AB_TREE=/path/to/worktree [name=ENV1=v,ENV2=v ...]   (name 'base' = no overrides)"""
 import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 rows = {}
@@ -9,7 +11,7 @@ for spec in sys.argv[1:]:
     for kv in filter(None, envs.split(",")):
         k, _, v = kv.partition("=")
         env[k] = v.replace("$ROOT", ROOT)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"],
+    out = subprocess.run([sys.executable, os.path.join(env.pop("AB_TREE", ROOT), "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"],
                          env=env, capture_output=True, text=True)
     try:
         d = json.loads(out.stdout.strip().splitlines()[-1])

@@ -3,7 +3,7 @@ import sys, os, math
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from diffcodec_amd import lib, ops
-if os.environ.get("DC_LIB_PATH"):        # A/B another build of the same ABI (tools/build_dev.sh)
+if os.environ.get("DC_LIB_PATH"):        # A/B another build of the same ABI: another commit's libdiffcodec_hip.so
     lib.LIB_PATH = os.path.abspath(os.environ["DC_LIB_PATH"])
 
 DEV = "cuda"

@@ -1,5 +1,5 @@
-"""Developer tool (GPU): outputs of the 1x1 / linear launcher on the long-K decode shapes, saved for a bit-comparison between two builds /
-knob settings (DC_GEMM_P8=0 vs 2 with the developer library).  usage: python tools/check_gemm_p8.py save <file> | cmp <a> <b>"""
+"""Developer tool (GPU): outputs of the 1x1 / linear launcher on the long-K decode shapes, saved for a bit-comparison between two builds
+(DC_LIB_PATH = another commit's libdiffcodec_hip.so, built in a git worktree).  usage: python tools/check_gemm_p8.py save <file> | cmp <a> <b>"""
 import sys, os, math
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

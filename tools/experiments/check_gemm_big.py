@@ -1,7 +1,8 @@
-"""Developer tool (GPU): outputs of the 1x1 / linear launcher on the long-K decode shapes, saved for a bit-comparison between two builds /
-knob settings (DC_GEMM_BIG=0 vs 2 with the developer library).  usage: python tools/check_gemm_big.py save <file> | cmp <a> <b>"""
+"""Developer tool (GPU): outputs of the 1x1 / linear launcher on the long-K decode shapes, saved for a bit-comparison between two builds
+(round 4: the library against a scratch build with gemm_big_prototype.hip hooked in, its DC_GEMM_BIG=0 vs 2).  usage:
+python tools/experiments/check_gemm_big.py save <file> | cmp <a> <b>"""
 import sys, os, math
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
 if sys.argv[1] == "cmp":
     a, b = torch.load(sys.argv[2]), torch.load(sys.argv[3])
