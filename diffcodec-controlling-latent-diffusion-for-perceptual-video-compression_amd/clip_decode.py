@@ -261,9 +261,12 @@ def blend_frames(unit_u8, units, height, width, overlap=64):
     return {f: t.cpu().numpy() for f, t in _blend_frame_tensors(unit_u8, units, height, width, overlap).items()}
 
 
-def score_frames(frames, source):
+def score_frames(frames, source, lpips=None):
     """{frame: uint8 [H,W,3] tensor} -> {frame: {"psnr": dB, "ms_ssim": value}} against `source.ground_truth(frame)`, with L = 255
-    (test_utils.py:23-24, :55; validation.py:147-150 on x / 255 gives the same values), on the device of the frames."""
+    (test_utils.py:23-24, :55; validation.py:147-150 on x / 255 gives the same values), on the device of the frames.
+    `lpips` (a `metrics.LPIPS` with weights loaded) adds "lpips": as test_utils.py:58 computes it, on frame / 255 with
+    normalize=False.  That is the reference's quirk, kept for comparable numbers: it feeds [0,1] images where the net expects
+    [-1,1] (the library's `normalize=True` would map them)."""
     from . import metrics
     scores = {}
     for f, pred in sorted(frames.items()):
@@ -272,19 +275,23 @@ def score_frames(frames, source):
             raise ValueError(f"ground truth of frame {f} has shape {tuple(gt.shape)}, the decoded frame {tuple(pred.shape)}")
         x, y = pred.unsqueeze(0), gt.unsqueeze(0)
         scores[f] = dict(psnr=float(metrics.psnr(x, y, data_range=255.0)[0]), ms_ssim=float(metrics.ms_ssim(x, y, data_range=255)))
+        if lpips is not None:
+            scores[f]["lpips"] = float(lpips(x, y, normalize=False).reshape(-1)[0])
     return scores
 
 
-def gather_scores(scores, units, rank, world, dst=0):
-    """Every rank's {frame: {"psnr", "ms_ssim"}} -> the union on `dst` (None elsewhere): ONE `dist.gather` of a float64
-    [inter frames, 3] tensor (scored flag, PSNR, MS-SSIM) per rank; no pixels travel."""
+def gather_scores(scores, units, rank, world, dst=0, lpips=False):
+    """Every rank's {frame: {"psnr", "ms_ssim"[, "lpips"]}} -> the union on `dst` (None elsewhere): ONE `dist.gather` of a float64
+    [inter frames, 3] tensor (scored flag, PSNR, MS-SSIM) per rank, with a fourth column (LPIPS) when `lpips` is set (every rank
+    passes the same value); no pixels travel."""
     import torch.distributed as dist
     frames = sorted({u.frame for u in units})
     row = {f: i for i, f in enumerate(frames)}
     dev = "cpu" if dist.get_backend() == "gloo" else torch.device("cuda", torch.cuda.current_device())
-    send = torch.zeros((len(frames), 3), dtype=torch.float64)
+    keys = ("psnr", "ms_ssim", "lpips") if lpips else ("psnr", "ms_ssim")
+    send = torch.zeros((len(frames), 1 + len(keys)), dtype=torch.float64)
     for f, s in scores.items():
-        send[row[f]] = torch.tensor([1.0, s["psnr"], s["ms_ssim"]], dtype=torch.float64)
+        send[row[f]] = torch.tensor([1.0] + [s[k] for k in keys], dtype=torch.float64)
     send = send.to(dev)
     bufs = [torch.empty_like(send) for _ in range(world)] if rank == dst else None
     dist.gather(send, bufs, dst=dst)
@@ -292,19 +299,21 @@ def gather_scores(scores, units, rank, world, dst=0):
         return None
     out = {}
     for b in bufs:
-        for f, (have, p, m) in zip(frames, b.cpu().tolist()):
+        for f, (have, *vals) in zip(frames, b.cpu().tolist()):
             if have:
-                out[f] = dict(psnr=p, ms_ssim=m)
+                out[f] = dict(zip(keys, vals))
     return dict(sorted(out.items()))
 
 
 @torch.no_grad()
 def decode_clip(pipe, source, num_frames, gop_size, height, width, prompt_embeds, negative_prompt_embeds=None, *, tile=512,
-                overlap=64, batch=16, seed=0, rank=None, world=None, shard_mode="unit", gather=True, score=False, **pipe_kwargs):
+                overlap=64, batch=16, seed=0, rank=None, world=None, shard_mode="unit", gather=True, score=False, lpips=None,
+                **pipe_kwargs):
     """Whole pipeline for one clip on this rank.  Returns dict(units=all units, mine=this rank's, images=this rank's fp32 unit
     images, frames={frame: uint8 HxWx3} on the gathering rank (or for locally complete frames when gather=False)).
     score=True adds scores={frame: {"psnr": dB, "ms_ssim": value}}: each blended frame against `source.ground_truth(frame)` on
-    the device, from the uint8 frames `frames` holds (score_frames).  With gather=False and world > 1 every rank scores its
+    the device, from the uint8 frames `frames` holds (score_frames); `lpips=` (a `metrics.LPIPS` with weights loaded) adds "lpips"
+    to each frame's dict and a fourth column to the gather.  With gather=False and world > 1 every rank scores its
     complete frames and one gather of the scores (not the pixels) gives rank 0 all of them; other ranks keep their own."""
     if rank is None or world is None:
         ini = torch.distributed.is_available() and torch.distributed.is_initialized()
@@ -324,7 +333,7 @@ def decode_clip(pipe, source, num_frames, gop_size, height, width, prompt_embeds
         nonlocal scores
         dev = _blend_frame_tensors(unit_u8, us, height, width, overlap)
         if score:
-            scores = score_frames(dev, source)
+            scores = score_frames(dev, source, lpips)
         return {f: t.cpu().numpy() for f, t in dev.items()}
 
     if gather and world > 1:
@@ -342,7 +351,7 @@ def decode_clip(pipe, source, num_frames, gop_size, height, width, prompt_embeds
         if complete:
             frames = blend(u8[complete], [mine[k] for k in complete])
         if score and world > 1 and torch.distributed.is_available() and torch.distributed.is_initialized():
-            merged = gather_scores(scores or {}, units, rank, world, dst=0)
+            merged = gather_scores(scores or {}, units, rank, world, dst=0, lpips=lpips is not None)
             if rank == 0:
                 scores = merged
     out = dict(units=units, mine=mine, images=images, frames=frames)

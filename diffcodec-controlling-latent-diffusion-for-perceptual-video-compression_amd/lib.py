@@ -82,6 +82,12 @@ SIGNATURES = {
     "dc_ssim": [vp, vp, i32, POINTER(i64), i32, i32, i32, i32, POINTER(f32), i32, f32, f32, f32, i32, vp, vp, vp],
     "dc_psnr_ws_bytes": [i32],
     "dc_psnr": [vp, vp, i32, POINTER(i64), i32, i32, i32, i32, f64, vp, vp, vp],
+    "dc_lpips_weight_floats": [],
+    "dc_lpips_ws_bytes": [i32, i32, i32],
+    "dc_lpips_alex": [vp, vp, i32, POINTER(i64), i32, i32, i32, i32, i32, vp, vp, vp, vp],
+    "dc_lpips_features_ws_bytes": [i32, i32, i32],
+    "dc_lpips_alex_features": [vp, i32, POINTER(i64), i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
+    "dc_lpips_conv": [i32, vp, i32, POINTER(i64), i32, i32, i32, i32, vp, vp, vp],
 }
 
 _lib = None

@@ -1,4 +1,4 @@
-"""Frame quality metrics on the device: PSNR, SSIM and MS-SSIM (csrc/metrics.hip).
+"""Frame quality metrics on the device: PSNR, SSIM and MS-SSIM (csrc/metrics.hip) and LPIPS (csrc/lpips.hip, `class LPIPS` below).
 
 The reference harness scores every decoded frame against its ground truth: validation.py:120-155 (`ms_ssim(pred, gt,
 data_range=1.0)`, `10*log10(1/mse)`) and test_utils.py:23-55 (`psnr`, `ms_ssim(..., data_range=255)`), both through
@@ -188,11 +188,191 @@ def psnr(X, Y, data_range=255.0):
 
 
 def summarize(scores):
-    """Means over frames of {frame: {"psnr": dB, "ms_ssim": value}} (decode_clip(score=True)), following test_utils.py:49-55: a
-    frame whose PSNR exceeds 1000 dB (identical images) is left out of both means.  Returns dict(psnr, ms_ssim, frames = the
-    number averaged, identical = the number left out); the means are NaN when no frame is left."""
+    """Means over frames of {frame: {"psnr": dB, "ms_ssim": value[, "lpips": value]}} (decode_clip(score=True)), following
+    test_utils.py:49-55: a frame whose PSNR exceeds 1000 dB (identical images) is left out of the means.  Returns dict(psnr,
+    ms_ssim, frames = the number averaged, identical = the number left out) and, when the scores carry it, lpips; the means are
+    NaN when no frame is left."""
     kept = [s for _, s in sorted(scores.items()) if not s["psnr"] > 1000]
     m = len(kept)
-    return dict(psnr=sum(s["psnr"] for s in kept) / m if m else float("nan"),
-                ms_ssim=sum(s["ms_ssim"] for s in kept) / m if m else float("nan"),
-                frames=m, identical=len(scores) - m)
+    out = dict(psnr=sum(s["psnr"] for s in kept) / m if m else float("nan"),
+               ms_ssim=sum(s["ms_ssim"] for s in kept) / m if m else float("nan"),
+               frames=m, identical=len(scores) - m)
+    if any("lpips" in s for s in scores.values()):
+        out["lpips"] = sum(s["lpips"] for s in kept) / m if m else float("nan")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------- LPIPS
+LPIPS_CHANNELS = (64, 192, 384, 256, 256)
+LPIPS_CIN = (3, 64, 192, 384, 256)
+LPIPS_KERNEL = (11, 5, 3, 3, 3)
+LPIPS_FEATURE_INDEX = (0, 3, 6, 8, 10)               # torchvision alexnet.features positions of the five convolutions
+LPIPS_MIN_SIZE = 31
+LPIPS_CHUNK_BYTES = 1 << 30                          # scratch bound of one launch sequence (12.4 MB of maps per 512x512 image)
+
+
+def lpips_map_sizes(h, w):
+    """(H, W) of relu1 .. relu5 for an h x w image: conv 11/4/2, max_pool 3/2, conv 5/1/2, max_pool 3/2, three conv 3/1/1."""
+    def down(v):
+        return (v - 3) // 2 + 1
+    s1 = ((h - 7) // 4 + 1, (w - 7) // 4 + 1)
+    s2 = (down(s1[0]), down(s1[1]))
+    s3 = (down(s2[0]), down(s2[1]))
+    return [s1, s2, s3, s3, s3]
+
+
+def _lpips_tensor(sd, key, shape):
+    if key not in sd:
+        raise ValueError(f"LPIPS state dict: missing key {key!r}")
+    t = sd[key]
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"LPIPS state dict: {key!r} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+    return t.detach().to("cpu", torch.float32)
+
+
+def pack_lpips_weights(state_dict, lin_state_dict=None):
+    """One fp32 CPU vector in the layout dc_lpips_alex reads: per conv the K-major matrix [(ci, ky, kx)][Cout] (conv1 followed by
+    one zero row, 363 -> 364) and its bias, then the five lin vectors.  Accepts the two layouts of LPIPS.load_state_dict."""
+    sd = dict(state_dict)
+    if lin_state_dict is not None:
+        sd.update(lin_state_dict)
+    library = any(k.startswith("net.slice") for k in sd)
+    parts = []
+    for l, (co, ci, k, pos) in enumerate(zip(LPIPS_CHANNELS, LPIPS_CIN, LPIPS_KERNEL, LPIPS_FEATURE_INDEX)):
+        stem = f"net.slice{l + 1}.{pos}" if library else f"features.{pos}"
+        w = _lpips_tensor(sd, stem + ".weight", (co, ci, k, k))
+        b = _lpips_tensor(sd, stem + ".bias", (co,))
+        wk = w.reshape(co, ci * k * k).t().contiguous()
+        if l == 0:
+            wk = torch.cat([wk, torch.zeros(1, co)], 0)
+        parts += [wk.reshape(-1), b]
+    for l, co in enumerate(LPIPS_CHANNELS):
+        parts.append(_lpips_tensor(sd, f"lin{l}.model.1.weight", (1, co, 1, 1)).reshape(-1))
+    return torch.cat(parts).contiguous()
+
+
+class LPIPS:
+    """`lpips.LPIPS(net='alex')` (version 0.1) on the device in exact fp32 (csrc/lpips.hip): call surface of the library's module,
+    `model(in0, in1, retPerLayer=False, normalize=False)` -> fp32 [N,1,1,1] (and the list of five per-layer [N,1,1,1]).
+
+        scaling   (x - shift) / scale, shift = (-.030, -.088, -.188), scale = (.458, .448, .450); normalize=True maps [0,1] to
+                  [-1,1] first (2x - 1); uint8 operands are x / 255
+        features  relu1 .. relu5 of torchvision's AlexNet: conv 3->64 11/4/2, max_pool 3/2, conv 64->192 5/1/2, max_pool 3/2,
+                  conv 192->384, 384->256, 256->256 3/1/1, a ReLU after each conv
+        distance  per layer, per pixel: sum_c w_c (x_c / (|x| + 1e-10) - y_c / (|y| + 1e-10))^2 with |x| = sqrt(sum_c x_c^2), its
+                  spatial mean; the value is the sum over the five layers.  normfix=True normalises by sqrt(sum_c (x_c^2 + 1e-8)),
+                  the form of the reference's training loss (controlnet/lpips_loss.py:27-29)
+
+    No weights ship with the package and none are downloaded: load the published checkpoint with `load_state_dict` /
+    `LPIPS.from_state_dict`, which take either
+      - the library module's own state dict: `net.slice{1..5}.{0,3,6,8,10}.weight|bias` and `lin{0..4}.model.1.weight` of shape
+        [1,C,1,1] (its `lins.*` duplicates and `scaling_layer.*` buffers are ignored), or
+      - a torchvision AlexNet state dict (`features.{0,3,6,8,10}.weight|bias`; `classifier.*` ignored) together with the lin
+        dict of the library's weights/v0.1/alex.pth (`lin{0..4}.model.1.weight`), as a second argument or merged into the first.
+    These key names are recalled from the published packages and are unpinned (neither lpips nor torchvision is a dependency);
+    tests/lpips_ref.py restates the rules above in fp64 and the device results are checked against that with seeded weights.
+
+    Operands and placement as for `ms_ssim`: uint8 NHWC or floating NCHW (any strides, read in place; float dtypes other than
+    fp32 are converted), C = 3, H and W >= 31.  Device tensors give device results on the current stream with no host
+    synchronisation (graph-capturable once the weights are on the device: `model.to(device)` or a first call); CPU tensors are
+    copied to the current GPU and the result comes back on the CPU.  Large batches run in chunks that bound the scratch; every
+    pair's result is independent of its position and of the batch size, bit for bit."""
+
+    def __init__(self, net="alex", version="0.1", normfix=False):
+        if net != "alex":
+            raise NotImplementedError(f"LPIPS net {net!r}: only 'alex' is implemented")
+        if str(version) != "0.1":
+            raise NotImplementedError(f"LPIPS version {version!r}: only '0.1' is implemented")
+        self.normfix = bool(normfix)
+        self.packed = None              # fp32 CPU vector (pack_lpips_weights)
+        self._on_device = {}
+
+    @classmethod
+    def from_state_dict(cls, state_dict, lin_state_dict=None, **kwargs):
+        m = cls(**kwargs)
+        m.load_state_dict(state_dict, lin_state_dict)
+        return m
+
+    def load_state_dict(self, state_dict, lin_state_dict=None):
+        packed = pack_lpips_weights(state_dict, lin_state_dict)
+        want = lib.load().dc_lpips_weight_floats()
+        if packed.numel() != want:
+            raise RuntimeError(f"packed LPIPS weights hold {packed.numel()} floats, the library expects {want}")
+        self.packed = packed
+        self._on_device = {}
+        return self
+
+    def to(self, device):
+        self._weights(torch.device(device))
+        return self
+
+    def _weights(self, device):
+        if self.packed is None:
+            raise RuntimeError("LPIPS has no weights: call load_state_dict / LPIPS.from_state_dict (nothing is downloaded)")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        w = self._on_device.get(device)
+        if w is None:
+            w = self._on_device[device] = self.packed.to(device)
+        return w
+
+    @staticmethod
+    def _check_image(c, h, w):
+        if c != 3:
+            raise ValueError(f"LPIPS takes 3-channel images, got {c} channels")
+        if h < LPIPS_MIN_SIZE or w < LPIPS_MIN_SIZE:
+            raise ValueError(f"LPIPS needs H, W >= {LPIPS_MIN_SIZE}, got {h}x{w}")
+
+    def __call__(self, in0, in1, retPerLayer=False, normalize=False):
+        X, Y = _check_pair(in0, in1)
+        (n, c, h, w), _ = _nchw(X)
+        self._check_image(c, h, w)
+        X, Y, host = _to_device(X, Y)
+        if X.dtype != torch.uint8 and X.dtype != torch.float32:
+            X, Y = X.float(), Y.float()
+        wts = self._weights(X.device)
+        L = lib.load()
+        step = max(1, min(n, LPIPS_CHUNK_BYTES // max(1, L.dc_lpips_ws_bytes(1, h, w))))
+        outs = []
+        with torch.cuda.device(X.device):
+            stream = torch.cuda.current_stream().cuda_stream
+            for i in range(0, n, step):
+                xs, ys, (m, _, _, _), strides, u8 = _prepare(X[i:i + step], Y[i:i + step])
+                scratch = torch.empty(L.dc_lpips_ws_bytes(m, h, w), dtype=torch.uint8, device=X.device)
+                out = torch.empty(6 * m, dtype=torch.float64, device=X.device)
+                lib.call("dc_lpips_alex", xs.data_ptr(), ys.data_ptr(), u8, strides, m, h, w, int(bool(normalize)), int(self.normfix),
+                         wts.data_ptr(), scratch.data_ptr(), out.data_ptr(), stream)
+                outs.append(out.view(6, m))
+        res = (outs[0] if len(outs) == 1 else torch.cat(outs, 1)).float()
+        if host:
+            res = res.cpu()
+        val = res[5].reshape(n, 1, 1, 1)
+        if retPerLayer:
+            return val, [res[l].reshape(n, 1, 1, 1) for l in range(5)]
+        return val
+
+    forward = __call__
+
+    def features(self, x, normalize=False):
+        """The five post-ReLU maps [relu1 .. relu5] of `x` (uint8 NHWC or float NCHW), contiguous fp32 NCHW."""
+        X, _ = _check_pair(x, x)
+        (n, c, h, w), _ = _nchw(X)
+        self._check_image(c, h, w)
+        X, _, host = _to_device(X, X)
+        if X.dtype != torch.uint8 and X.dtype != torch.float32:
+            X = X.float()
+        wts = self._weights(X.device)
+        L = lib.load()
+        sizes = lpips_map_sizes(h, w)
+        feats = [torch.empty((n, co) + s, dtype=torch.float32, device=X.device) for co, s in zip(LPIPS_CHANNELS, sizes)]
+        step = max(1, min(n, LPIPS_CHUNK_BYTES // max(1, L.dc_lpips_features_ws_bytes(1, h, w))))
+        with torch.cuda.device(X.device):
+            stream = torch.cuda.current_stream().cuda_stream
+            for i in range(0, n, step):
+                xs = X[i:i + step]
+                m = xs.shape[0]
+                _, sx = _nchw(xs)
+                scratch = torch.empty(L.dc_lpips_features_ws_bytes(m, h, w), dtype=torch.uint8, device=X.device)
+                lib.call("dc_lpips_alex_features", xs.data_ptr(), int(xs.dtype == torch.uint8), (ctypes.c_longlong * 4)(*sx), m, h, w,
+                         int(bool(normalize)), wts.data_ptr(), scratch.data_ptr(), *[f[i:i + step].data_ptr() for f in feats], stream)
+        return [f.cpu() for f in feats] if host else feats

@@ -295,6 +295,32 @@ long long dc_psnr_ws_bytes(int N);
 int dc_psnr(const void* x, const void* y, int x_u8, const long long* strides, int N, int C, int H, int W, double data_range,
             void* ws, double* out, void* stream);
 
+/* LPIPS, AlexNet, version 0.1 (test_utils.py:13,58: lpips.LPIPS(net='alex')) of N image pairs, exact fp32 on the fp32 matrix
+ * instruction, sums in a fixed order (bitwise reproducible, independent of a pair's position in the batch, no float atomics).
+ * Operands as above with C = 3: uint8 is mapped to x / 255; normalize = 1 applies 2x - 1; then the ScalingLayer
+ * (x - shift) / scale, the five conv + ReLU stages (zero padding in the scaled space), per layer the channel-unit-normalised
+ * squared difference weighted by the lin vector, its spatial mean, and their sum.  normfix = 1 normalises by
+ * sqrt(sum_c (x_c^2 + 1e-8)) (controlnet/lpips_loss.py:27-29) instead of sqrt(sum_c x_c^2) + 1e-10.
+ * weights (device, fp32, 16-byte aligned, dc_lpips_weight_floats() elements): for conv1..conv5 the K-major matrix
+ * [K = (ci, ky, kx)][Cout] followed by the bias [Cout] (conv1's K = 363 is followed by one zero row: 364 rows), then the five
+ * lin vectors [64][192][384][256][256].  ws: dc_lpips_ws_bytes(N, H, W) bytes (-1 when H or W < 31 or N is out of range).
+ * out (device, fp64) [5 N + N]: the per-layer values [layer][n], then their sum per pair. */
+int dc_lpips_weight_floats(void);
+long long dc_lpips_ws_bytes(int N, int H, int W);
+int dc_lpips_alex(const void* x, const void* y, int x_u8, const long long* strides, int N, int H, int W, int normalize, int normfix,
+                  const float* weights, void* ws, double* out, void* stream);
+/* The five post-ReLU maps of one operand (strides[0..3]), contiguous fp32 NCHW: f1 [N,64,H1,W1], f2 [N,192,H2,W2],
+ * f3 [N,384,H3,W3], f4 / f5 [N,256,H3,W3] with H1 = (H - 7) / 4 + 1, H2 = (H1 - 3) / 2 + 1, H3 = (H2 - 3) / 2 + 1 (floor).
+ * ws: dc_lpips_features_ws_bytes(N, H, W) bytes. */
+long long dc_lpips_features_ws_bytes(int N, int H, int W);
+int dc_lpips_alex_features(const void* x, int x_u8, const long long* strides, int N, int H, int W, int normalize,
+                           const float* weights, void* ws, float* f1, float* f2, float* f3, float* f4, float* f5, void* stream);
+/* One conv + bias + ReLU stage on its own (tools/bench_metrics.py times the layers through it).  layer 0: x is the image operand
+ * (x_u8, strides[0..3], M images of H x W) and y is [M,64,H1,W1]; layer 1..4: x is a contiguous fp32 map [M,Cin,H,W] (x_u8 and
+ * strides are ignored; H, W <= 4096) and y is [M,Cout,H,W]. */
+int dc_lpips_conv(int layer, const void* x, int x_u8, const long long* strides, int M, int H, int W, int normalize,
+                  const float* weights, float* y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,11 @@
 512x512 and at 1080p.  Prints one JSON line per shape: event-timed milliseconds per call and per pair (host launch overhead
 included).  Kernel times: run under `rocprofv3 --kernel-trace --stats -d <dir> -- python tools/bench_metrics.py`.
 
-    python tools/bench_metrics.py [--batch 16] [--iters 20]"""
+LPIPS leg (csrc/lpips.hip, seeded random weights): at 512x512 for 1 and 16 pairs and at 1080p for 1 pair, one JSON line with the
+whole call (ms per call and per pair) and, per conv layer, the time of the layer's kernel alone on the call's 2N images
+(dc_lpips_conv, back-to-back launches between two events) with its TFLOP/s.
+
+    python tools/bench_metrics.py [--batch 16] [--iters 20] [--no-lpips]"""
 import argparse
 import json
 import os
@@ -13,10 +17,64 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 
+def lpips_leg(iters):
+    import ctypes
+    from diffcodec_amd import lib, metrics as M
+    g = torch.Generator().manual_seed(0)
+    sd = {}
+    for l, (co, ci, k, pos) in enumerate(zip(M.LPIPS_CHANNELS, M.LPIPS_CIN, M.LPIPS_KERNEL, M.LPIPS_FEATURE_INDEX)):
+        a = (ci * k * k) ** -0.5
+        sd[f"features.{pos}.weight"] = (torch.rand(co, ci, k, k, generator=g) * 2 - 1) * 1.7 * a
+        sd[f"features.{pos}.bias"] = (torch.rand(co, generator=g) * 2 - 1) * a
+        sd[f"lin{l}.model.1.weight"] = torch.rand(1, co, 1, 1, generator=g)
+    model = M.LPIPS.from_state_dict(sd).to("cuda")
+    wts = model._weights(torch.device("cuda"))
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def timed(fn):
+        for _ in range(3):
+            fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / iters
+
+    gd = torch.Generator(device="cuda").manual_seed(0)
+    for h, w, n in ((512, 512, 1), (512, 512, 16), (1080, 1920, 1)):
+        x = torch.randint(0, 256, (n, h, w, 3), dtype=torch.uint8, device="cuda", generator=gd)
+        y = (x.int() + torch.randint(-8, 9, (n, h, w, 3), device="cuda", generator=gd)).clamp(0, 255).to(torch.uint8)
+        ms = timed(lambda: model(x, y))
+        both = torch.cat([x, y])
+        feats = model.features(both)
+        sizes = M.lpips_map_sizes(h, w)
+        strides = (ctypes.c_longlong * 4)(*M._nchw(both)[1])
+        layers = {}
+        for l, (co, ci, k) in enumerate(zip(M.LPIPS_CHANNELS, M.LPIPS_CIN, M.LPIPS_KERNEL)):
+            hh, ww = sizes[l]
+            if l == 0:
+                src, a_h, a_w = both, h, w
+            else:
+                src = torch.nn.functional.max_pool2d(feats[l - 1], 3, 2) if l in (1, 2) else feats[l - 1]
+                src, a_h, a_w = src.contiguous(), hh, ww
+            out = torch.empty_like(feats[l])
+            t = timed(lambda: lib.call("dc_lpips_conv", l, src.data_ptr(), int(l == 0), strides, 2 * n, a_h, a_w, 0, wts.data_ptr(),
+                                       out.data_ptr(), stream))
+            assert torch.equal(out, feats[l]), f"conv{l + 1} alone differs from the fused sequence"
+            flop = 2.0 * (2 * n) * co * hh * ww * ci * k * k
+            layers[f"conv{l + 1}"] = dict(us=round(t * 1e3, 1), tflops=round(flop / (t * 1e-3) / 1e12, 1))
+        conv_ms = sum(v["us"] for v in layers.values()) / 1e3
+        print(json.dumps(dict(lpips=f"{h}x{w}", pairs=n, ms_per_call=round(ms, 4), ms_per_pair=round(ms / n, 4),
+                              conv_ms=round(conv_ms, 4), pool_tail_host_ms=round(ms - conv_ms, 4), **layers)), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--no-lpips", action="store_true")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_metrics needs the GPU"
     from diffcodec_amd import metrics as M
@@ -40,6 +98,8 @@ def main():
             ms = e0.elapsed_time(e1) / a.iters
             res[name] = dict(ms_per_call=round(ms, 4), ms_per_pair=round(ms / a.batch, 5))
         print(json.dumps(dict(shape=f"{h}x{w}", batch=a.batch, **res)), flush=True)
+    if not a.no_lpips:
+        lpips_leg(a.iters)
 
 
 if __name__ == "__main__":
