@@ -3,6 +3,7 @@
     python -m diffcodec_amd.build        -> <package>/libdiffcodec_hip.so
 
 The .so is built in-tree so that it travels with the repo snapshot to the GPU box."""
+import glob
 import os
 import subprocess
 import sys
@@ -29,7 +30,7 @@ def build(force=False, verbose=False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
-    hdrs = [os.path.join(CSRC, "dc_common.h"), os.path.join(os.path.dirname(HERE), "include", "diffcodec_hip.h")]
+    hdrs = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(os.path.dirname(HERE), "include", "diffcodec_hip.h")]
     jobs = []
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
     if not force and os.path.exists(LIB) and not _stale(LIB, srcs + hdrs):

@@ -17,8 +17,7 @@
 //
 // LDS images are row-major 128-B rows with the 16-B chunk index XORed by (row & 7): ds_write_b128 of a row piece and
 // the v_mfma_f32_16x16x32_bf16 fragment ds_read_b128 are both bank-conflict-free, and rows stay whole 128-B lines.
-#include "dc_common.h"
-#include "../../include/diffcodec_hip.h"
+#include "dc_conv_route.h"
 #include <cstdlib>
 #include <utility>
 
@@ -608,18 +607,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_tile_kernel(const dc_conv_desc
 #endif
 }
 
-}  // namespace
-
-// Specialised epilogue mode of a halo-tile launch (0 = generic run-time flags, 1 = plain, 2 = residual).
-int dc_conv3x3_tile_epi(const dc_conv_desc& d)
-{
-    return (d.splitk > 1 || d.out_f32 || d.act) ? 0 : (d.residual ? 2 : 1);
-}
-
-namespace {
-
-template <int TM, int TN, int NSTB, bool FAST = false, bool UPS = false, bool SH = false>
-int launch_tile(const dc_conv_desc& d, hipStream_t st)
+template <int TM, int TN, int NSTB, bool FAST, bool UPS, bool SH>
+int launch_tile(const dc_conv_desc& d, const dc_route& r, hipStream_t st)
 {
     constexpr int TH = 2 * TM, BN = 2 * TN * 16;
     const int sh = d.Wo < 16 ? 1 : 0;
@@ -628,26 +617,25 @@ int launch_tile(const dc_conv_desc& d, hipStream_t st)
     constexpr int HALO_ROWS = UPS ? (TH / 2 + 2) * 10 : SH ? (TM == 4 ? 200 : ((TH << 1) + 2) * 10) : ((TM == 4 && !FAST) ? 200 : (TH + 2) * 18);
     const dim3 grid(nblk, d.splitk > 1 ? d.splitk : 1);
     const size_t lds = HALO_ROWS * (FAST ? 160 : 128) + NSTB * BN * 128;
-    const int epi = dc_conv3x3_tile_epi(d);
     // tile order inside an XCD's range (see the kernel): pixel tiles fastest when the weight tensor is larger than the activations
     const int order = (long long)d.Cout * 9 > (long long)d.N * d.H * d.W ? 1 : 0;
 #define DC_TILE_LAUNCH1(GN, EPI)                                                                                \
     do {                                                                                                        \
-        auto kern = conv3x3_tile_kernel<TM, TN, GN, NSTB, EPI, FAST, (UPS && !GN), (SH && !GN)>;                                                    \
+        auto kern = conv3x3_tile_kernel<TM, TN, GN, NSTB, EPI, FAST, UPS, SH>;                                  \
         static std::atomic<unsigned long long> attr_done{0};                                                    \
         dc_set_max_dyn_lds((const void*)kern, (int)lds, attr_done);                                             \
         hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, d, order);                                           \
     } while (0)
-#define DC_TILE_LAUNCH(GN)                          \
-    do {                                            \
-        if (epi == 1) DC_TILE_LAUNCH1(GN, 1);       \
-        else if (epi == 2) DC_TILE_LAUNCH1(GN, 2);  \
-        else DC_TILE_LAUNCH1(GN, 0);                \
+#define DC_TILE_LAUNCH(GN)                            \
+    do {                                              \
+        if (r.epi == 1) DC_TILE_LAUNCH1(GN, 1);       \
+        else if (r.epi == 2) DC_TILE_LAUNCH1(GN, 2);  \
+        else DC_TILE_LAUNCH1(GN, 0);                  \
     } while (0)
     if constexpr (UPS || SH) {
-        DC_TILE_LAUNCH(false);                                  // (the dispatcher sends GroupNorm-on-load upsamples to the other form)
+        DC_TILE_LAUNCH(false);                                  // (the route sends GroupNorm-on-load upsamples and narrow maps to the other form)
     } else {
-        if (d.gn_ab) DC_TILE_LAUNCH(true);
+        if (r.gn) DC_TILE_LAUNCH(true);
         else DC_TILE_LAUNCH(false);
     }
 #undef DC_TILE_LAUNCH
@@ -657,79 +645,67 @@ int launch_tile(const dc_conv_desc& d, hipStream_t st)
 
 }  // namespace
 
-// Returns 1 if the halo-tile kernel can take this descriptor (3x3, stride 1, pad 1, tile-aligned output).
-int dc_conv3x3_tile_supported(const dc_conv_desc& d)
-{
-    if (!(d.ksize == 3 && d.stride == 1 && d.pad == 1 && d.epilogue == 0)) return 0;
-    if (d.Wo == 8) return !d.upsample && (d.Ho % 8) == 0;       // narrow: tile = 8 rows x 8 cols (TM = 2)
-    return (d.Wo % 16) == 0 && (d.Ho % 4) == 0;
-}
-
-// Tile-shape decision shared by the launcher and the statistics-chunk query: 4 = 8-row tiles (TM = 4), 2 = 4-row tiles,
-// 8 = two whole 8x8 images per tile (TM = 4, dual).
+// Takes a 3x3, stride 1, pad 1 conv with a tile-aligned output, and decides its instance.
+// Tile shape (variant): 4 = 8-row tiles (TM = 4), 2 = 4-row tiles, 8 = two whole 8x8 images per tile (TM = 4, dual).
 // N tile: 160 columns whenever Cout is a multiple of 160 (all SD-1.5 UNet widths), also where Cout is a multiple of 128 as well
 // (640, 1280) and the 128-column tile would afford a 3-stage weight ring at two workgroups per CU (the 160-column tile has room
 // for two stages only).
-static bool use_n160(const dc_conv_desc& d)
+int dc_conv3x3_tile_route(const dc_conv_desc& d, dc_route& r)
 {
-    return d.Cout % 160 == 0;
-}
-
-static int tile_variant(const dc_conv_desc& d)
-{
-    const bool n160 = use_n160(d);
-    const int bn = n160 ? 160 : 128;
-    const long long big = (long long)d.N * (d.Ho / 8) * (d.Wo / 16) * dc_cdiv(d.Cout, bn) * (d.splitk > 1 ? d.splitk : 1);
+    if (!(d.ksize == 3 && d.stride == 1 && d.pad == 1 && d.epilogue == 0)) return DC_ROUTE_PASS;
+    if (d.Wo == 8 ? (d.upsample || d.Ho % 8) : (d.Wo % 16 || d.Ho % 4)) return DC_ROUTE_PASS;   // narrow: tile = 8 rows x 8 cols (TM = 2)
+    const int bn = dc_n_tile(d), sk = d.splitk > 1 ? d.splitk : 1, n_tiles = dc_cdiv(d.Cout, bn);
+    const long long big = (long long)d.N * (d.Ho / 8) * (d.Wo / 16) * n_tiles * sk;
+    int v = 2;
     // LDS budget keeps two workgroups per CU: 8-row tile with BN=160 affords a 2-stage weight ring, the others 3 stages
-    if (d.Wo >= 16 && (d.Ho % 8) == 0 && big >= 512) return 4;
+    if (d.Wo >= 16 && (d.Ho % 8) == 0 && big >= 512) v = 4;
     // 8x8 maps: two images per tile when the batch is even, nothing is fused on load and enough tiles remain
-    if (d.Wo == 8 && d.Ho == 8 && (d.N & 1) == 0 && !d.gn_ab &&
-        (long long)(d.N / 2) * dc_cdiv(d.Cout, bn) * (d.splitk > 1 ? d.splitk : 1) >= 512)   // measured: below 2 workgroups/CU the 4-row tiles win
-        return 8;
-    return 2;
+    else if (d.Wo == 8 && d.Ho == 8 && (d.N & 1) == 0 && !d.gn_ab &&
+             (long long)(d.N / 2) * n_tiles * sk >= 512)   // measured: below 2 workgroups/CU the 4-row tiles win
+        v = 8;
+    r.kernel = DC_ROUTE_CONV3X3_TILE;
+    r.variant = v;
+    r.epi = (d.splitk > 1 || d.out_f32 || d.act) ? 0 : (d.residual ? 2 : 1);   // 0 = generic run-time flags, 1 = plain, 2 = residual
+    r.tm = v == 2 ? 2 : 4;
+    r.tn = bn / 32;
+    r.gn = d.gn_ab != nullptr;
+    // the half-step pipeline (FAST, see the kernel comment) takes Cout % 8 == 0: plain maps at least 16 wide, and without GroupNorm
+    // on load the Upsample2D convs (UPS) and the 8-wide maps (SH)
+    const bool c8 = (d.Cout & 7) == 0, plain = c8 && !d.upsample && d.Wo >= 16;
+    r.ups = c8 && d.upsample && !d.gn_ab && d.Wo >= 16;
+    r.sh = c8 && d.Wo == 8 && !d.upsample && !d.gn_ab;
+    r.fast = plain || r.ups || r.sh;
+    // weight ring: two stages on the pipeline, four for a plain map with at most one workgroup per CU (one- or two-frame decodes: three
+    // taps of weights in flight); the other form affords three stages except with the 8-row 160-column tile
+    const long long wgs = (long long)d.N * (d.Ho / (2 * r.tm)) * (d.Wo / 16) * n_tiles * sk;
+    r.nst = r.fast ? 2 : (r.tm == 4 && r.tn == 5) ? 2 : 3;
+    // Cout <= 32 (UNet conv_out 320 -> 4, VAE conv_out 128 -> 3 + 1): one 32-column N tile instead of a mostly empty 128-column
+    // one — a fifth of the MFMA work per pixel tile (the launch is then paced by the GroupNorm+SiLU of its halo, done once)
+    if (d.Cout <= 32 && (plain || (!r.fast && v != 8))) r.tn = 1, r.nst = plain ? 2 : 3;
+    else if (plain && wgs <= 256) r.nst = 4;
+    if (d.gn_part_out && d.splitk <= 1) {                   // (split-K partial tiles are finished elsewhere)
+        const int sh = d.Wo < 16 ? 1 : 0;
+        r.gn_chunks = v == 8 ? 1 : (d.Ho / ((2 * r.tm) << sh)) * (d.Wo / (16 >> sh)) * 2;
+    }
+    return DC_OK;
 }
 
-int dc_conv3x3_tile_variant(const dc_conv_desc& d) { return tile_variant(d); }
+// Every launch_tile<TM, TN, NSTB, FAST, UPS, SH> the route can name, in the order that fixes the kernels' order in the code object.
+#define DC_TILE_INSTANCES(X)                                                                                       \
+    X(4, 1, 2, true, false, false) X(2, 1, 2, true, false, false)                                                  \
+    X(4, 5, 4, true, false, false) X(4, 4, 4, true, false, false) X(2, 5, 4, true, false, false) X(2, 4, 4, true, false, false)  \
+    X(4, 5, 2, true, false, false) X(4, 4, 2, true, false, false) X(2, 5, 2, true, false, false) X(2, 4, 2, true, false, false)  \
+    X(4, 5, 2, true, true, false) X(4, 4, 2, true, true, false) X(2, 5, 2, true, true, false) X(2, 4, 2, true, true, false)      \
+    X(4, 5, 2, true, false, true) X(4, 4, 2, true, false, true) X(2, 5, 2, true, false, true) X(2, 4, 2, true, false, true)      \
+    X(4, 1, 3, false, false, false) X(2, 1, 3, false, false, false)                                                \
+    X(4, 5, 2, false, false, false) X(4, 4, 3, false, false, false) X(2, 5, 3, false, false, false) X(2, 4, 3, false, false, false)
 
-// gn_part_out chunks per sample of this launch (0: not available — split-K partial tiles are finished elsewhere).
-int dc_conv3x3_tile_gn_chunks(const dc_conv_desc& d)
+int dc_conv3x3_tile_launch(const dc_conv_desc& d, const dc_route& r, hipStream_t st)
 {
-    if (d.splitk > 1) return 0;
-    const int v = tile_variant(d);
-    if (v == 8) return 1;
-    const int sh = d.Wo < 16 ? 1 : 0;
-    const int th = (v == 4 ? 8 : 4) << sh, tw = 16 >> sh;
-    return (d.Ho / th) * (d.Wo / tw) * 2;
-}
-
-// Called by dc_conv_igemm_bf16 after validation (workspace already zeroed for splitk > 1).
-int dc_conv3x3_tile_launch(const dc_conv_desc& d, hipStream_t st)
-{
-    const bool n160 = use_n160(d);
-    const int v = tile_variant(d);
-    if (!d.upsample && d.Wo >= 16 && (d.Cout & 7) == 0) {            // plain maps: half-step pipeline (see the kernel comment)
-        // at most one workgroup per CU (one- or two-frame decodes): a four-slot weight ring, three taps of weights in flight
-        const int th = v == 4 ? 8 : 4, bn = n160 ? 160 : 128;
-        const long long wgs = (long long)d.N * (d.Ho / th) * (d.Wo / 16) * dc_cdiv(d.Cout, bn) * (d.splitk > 1 ? d.splitk : 1);
-        // Cout <= 32 (UNet conv_out 320 -> 4, VAE conv_out 128 -> 3 + 1): one 32-column N tile instead of a mostly empty 128-column
-        // one — a fifth of the MFMA work per pixel tile (the launch is then paced by the GroupNorm+SiLU of its halo, done once)
-        if (d.Cout <= 32) return v == 4 ? launch_tile<4, 1, 2, true>(d, st) : launch_tile<2, 1, 2, true>(d, st);
-        if (wgs <= 256) {
-            if (v == 4) return n160 ? launch_tile<4, 5, 4, true>(d, st) : launch_tile<4, 4, 4, true>(d, st);
-            return n160 ? launch_tile<2, 5, 4, true>(d, st) : launch_tile<2, 4, 4, true>(d, st);
-        }
-        if (v == 4) return n160 ? launch_tile<4, 5, 2, true>(d, st) : launch_tile<4, 4, 2, true>(d, st);
-        return n160 ? launch_tile<2, 5, 2, true>(d, st) : launch_tile<2, 4, 2, true>(d, st);
-    }
-    if (d.upsample && !d.gn_ab && d.Wo >= 16 && (d.Cout & 7) == 0) {       // Upsample2D convs: the same pipeline
-        if (v == 4) return n160 ? launch_tile<4, 5, 2, true, true>(d, st) : launch_tile<4, 4, 2, true, true>(d, st);
-        return n160 ? launch_tile<2, 5, 2, true, true>(d, st) : launch_tile<2, 4, 2, true, true>(d, st);
-    }
-    if (d.Wo == 8 && !d.upsample && !d.gn_ab && (d.Cout & 7) == 0) {        // 8x8 maps: the same pipeline
-        if (v == 8) return n160 ? launch_tile<4, 5, 2, true, false, true>(d, st) : launch_tile<4, 4, 2, true, false, true>(d, st);
-        return n160 ? launch_tile<2, 5, 2, true, false, true>(d, st) : launch_tile<2, 4, 2, true, false, true>(d, st);
-    }
-    if (d.Cout <= 32 && v != 8) return v == 4 ? launch_tile<4, 1, 3>(d, st) : launch_tile<2, 1, 3>(d, st);   // (Cout = 4: not a multiple of 8)
-    if (v == 4 || v == 8) return n160 ? launch_tile<4, 5, 2>(d, st) : launch_tile<4, 4, 3>(d, st);
-    return n160 ? launch_tile<2, 5, 3>(d, st) : launch_tile<2, 4, 3>(d, st);
+#define DC_TILE_CASE(TM, TN, NSTB, FAST, UPS, SH)                                                                  \
+    if (r.tm == TM && r.tn == TN && r.nst == NSTB && r.fast == FAST && r.ups == UPS && r.sh == SH)                 \
+        return launch_tile<TM, TN, NSTB, FAST, UPS, SH>(d, r, st);
+    DC_TILE_INSTANCES(DC_TILE_CASE)
+#undef DC_TILE_CASE
+    return DC_ERR_INVALID;
 }

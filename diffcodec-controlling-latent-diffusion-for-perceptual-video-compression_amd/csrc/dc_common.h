@@ -19,16 +19,6 @@ typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
 
 #define DC_WAVE 64
 
-// Kernel choice for one dc_conv_desc (DC_ROUTE_* of diffcodec_hip.h): computed once by the routing functions and read both by the
-// launchers and by the dc_conv_route query, so that the two cannot disagree.
-struct dc_route {
-    int kernel;     // DC_ROUTE_*
-    int variant;    // template / tile form inside the kernel family (see dc_conv_route)
-    int epi;        // specialised epilogue mode (0 = generic)
-    int splitk;     // effective split-K
-    int ln_first;   // the LayerNorm finalize pass runs first, into ln_scratch
-};
-
 // XCD-aware block order: the hardware deals workgroups round-robin over the 8 XCDs (blocks b, b + 8, ... share one XCD and its
 // L2), so logical block `bid` of `nblk` is remapped to give each XCD one contiguous range of tiles.
 __host__ __device__ inline int dc_xcd_remap(int bid, int nblk)

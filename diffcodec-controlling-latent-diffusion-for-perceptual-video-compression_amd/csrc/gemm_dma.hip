@@ -9,8 +9,7 @@
 // the v_mfma_f32_16x16x32_bf16 fragment ds_read_b128 stay conflict-free.  NST LDS stages form a ring: the DMA of
 // K-step k+NST-1 is issued right after the barrier that opens step k, and a counted `s_waitcnt vmcnt(N)` (never 0 in
 // the loop) leaves NST-2 stages in flight across every raw `s_barrier` — one barrier per K-step.
-#include "dc_common.h"
-#include "../../include/diffcodec_hip.h"
+#include "dc_conv_route.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -423,9 +422,9 @@ int epi_mode(const dc_conv_desc& d)
 }
 
 template <int TM, int TN, int NST>
-int launch_gemm(const dc_conv_desc& d, hipStream_t st)
+int launch_gemm(const dc_conv_desc& d, int epi, hipStream_t st)
 {
-    switch (epi_mode(d)) {
+    switch (epi) {
         case 1: return launch_gemm_e<TM, TN, NST, 1>(d, st);
         case 2: return launch_gemm_e<TM, TN, NST, 2>(d, st);
         case 3: return launch_gemm_e<TM, TN, NST, 3>(d, st);
@@ -439,98 +438,65 @@ int launch_gemm(const dc_conv_desc& d, hipStream_t st)
 
 extern "C" int dc_gemm_row_stats_parts(int Cout) { return dc_row_stats_parts_rule(Cout); }
 
-int dc_gemm_rowpanel_wanted(const dc_conv_desc& d, int epi);
-// 1x1 launches of the LDS-DMA GEMM family.  A GroupNorm affine on load exists in the row-panel kernel only: such a launch belongs here
+// The decision for a 1x1 descriptor: kernel, gemm_dma template (variant = TM*10000 + TN*1000 + stages*100 + A_REG*10 + PROD, where
+// the A_REG digit is always 0 and the PROD digit always 1: kept so that recorded routes stay valid), epilogue mode, and whether the
+// LayerNorm finalize runs first.  A GroupNorm affine on load exists in the row-panel kernel only: such a launch belongs to the family
 // exactly when that kernel takes it (the gather GEMM of igemm.hip serves the others).
-int dc_gemm_dma_supported(const dc_conv_desc& d)
-{
-    if (d.ksize != 1) return 0;
-    return d.gn_ab == nullptr || dc_gemm_rowpanel_wanted(d, epi_mode(d));
-}
-
-int dc_gemm_dma_gn_chunks(const dc_conv_desc& d);
-// gemm_wide.hip: the 256-row ping-pong kernel for long-K launches
-int dc_gemm_wide_wanted(const dc_conv_desc& d, int epi);
-int dc_gemm_wide_launch(const dc_conv_desc& d, int epi, hipStream_t st);
-int dc_gemm_wide_gn_chunks(const dc_conv_desc& d);
-// gemm_p8.hip: the 256 x 256 four-phase kernel for the long-K, wide-N linears without residual / statistics
-int dc_gemm_p8_wanted(const dc_conv_desc& d, int epi);
-int dc_gemm_p8_launch(const dc_conv_desc& d, int epi, hipStream_t st);
-// gemm_rowpanel.hip: the K = 320 kernel that keeps a 256-row activation panel in registers and streams only W
-int dc_gemm_rowpanel_wanted(const dc_conv_desc& d, int epi);
-int dc_gemm_rowpanel_launch(const dc_conv_desc& d, int epi, hipStream_t st);
-int dc_gemm_rowpanel_gn_chunks(const dc_conv_desc& d);
-
-// The decision of dc_gemm_dma_launch for a 1x1 descriptor: kernel, gemm_dma template (variant = TM*10000 + TN*1000 + stages*100 +
-// A_REG*10 + PROD, where the A_REG digit is always 0 and the PROD digit always 1: kept so that recorded routes stay valid),
-// epilogue mode, and whether the LayerNorm finalize runs first.  The launch and dc_conv_route both read it.
 int dc_gemm_dma_route(const dc_conv_desc& d, dc_route& r)
 {
-    const long long M = (long long)d.N * d.Ho * d.Wo;
-    // the folded LayerNorm and the row statistics live in the staged (bf16, unsplit) epilogue only
+    if (d.ksize != 1) return DC_ROUTE_PASS;
+    r.epi = epi_mode(d);
+    int rc = dc_gemm_rowpanel_route(d, r);
+    if (rc == DC_ROUTE_PASS && d.gn_ab) {
+        r.epi = 0;
+        return DC_ROUTE_PASS;
+    }
+    // the folded LayerNorm and the row / GroupNorm statistics live in the staged (bf16, unsplit) epilogue only
     if ((d.ln_stats || d.stats_out || d.gn_part_out) && (d.out_f32 || d.splitk > 1)) return DC_ERR_INVALID;
-    if (d.gn_part_out && dc_gemm_dma_gn_chunks(d) == 0) return DC_ERR_INVALID;
-    r.variant = 0;
-    {
-        const int epi = epi_mode(d);
-        r.epi = epi;
-        if (dc_gemm_rowpanel_wanted(d, epi)) {
-            if (d.gn_part_out && epi > 2) return DC_ERR_INVALID;
-            if ((epi == 3 || epi == 5) && !d.ln_colsum) return DC_ERR_INVALID;
-            r.kernel = DC_ROUTE_GEMM_ROWPANEL;
-            return DC_OK;
-        }
-        if (d.ln_stats && d.ln_parts > 0) {
-            // raw LayerNorm partials and a kernel whose waves do not own whole rows: the finalize pass runs first, into the
-            // caller's scratch, and the launch proceeds on (mean, rstd) pairs — the same bits as finalizing beforehand
-            dc_conv_desc q = d;
-            if (q.ln_scratch) q.ln_stats = q.ln_scratch;
-            q.ln_parts = 0;
-            const int rc = dc_gemm_dma_route(q, r);
-            r.ln_first = 1;
-            return rc;
-        }
-        if (d.ln_stats && !d.ln_colsum) return DC_ERR_INVALID;
-        if (dc_gemm_p8_wanted(d, epi)) {
-            r.kernel = DC_ROUTE_GEMM_P8;
-            return DC_OK;
-        }
-        if (dc_gemm_wide_wanted(d, epi)) {
-            r.kernel = DC_ROUTE_GEMM_WIDE;
-            return DC_OK;
-        }
+    if (d.gn_part_out && (d.epilogue != 0 || d.ln_stats)) return DC_ERR_INVALID;
+    if (rc != DC_ROUTE_PASS) return rc;
+    if (d.ln_stats && d.ln_parts > 0) {
+        // raw LayerNorm partials and a kernel whose waves do not own whole rows: the finalize pass runs first, into the
+        // caller's scratch, and the launch proceeds on (mean, rstd) pairs — the same bits as finalizing beforehand
+        dc_conv_desc q = d;
+        if (q.ln_scratch) q.ln_stats = q.ln_scratch;
+        q.ln_parts = 0;
+        rc = dc_gemm_dma_route(q, r);
+        r.ln_first = 1;
+        return rc;
     }
     if (d.ln_stats && !d.ln_colsum) return DC_ERR_INVALID;
+    rc = dc_gemm_p8_route(d, r);
+    if (rc == DC_ROUTE_PASS) rc = dc_gemm_wide_route(d, r);
+    if (rc != DC_ROUTE_PASS) return rc;
     if (d.stats_out && d.epilogue != 0) return DC_ERR_INVALID;
+    const long long M = (long long)d.N * d.Ho * d.Wo, hw = (long long)d.Ho * d.Wo;
+    const int bn = dc_n_tile(d), sk = d.splitk > 1 ? d.splitk : 1, KT = (d.C1 + d.C2) >> 6;
+    const long long big = ((M + 127) / 128) * ((d.Cout + bn - 1) / bn) * sk;
+    const long long small = ((M + 63) / 64) * ((d.Cout + bn - 1) / bn) * sk;
     r.kernel = DC_ROUTE_GEMM_DMA;
-    auto pick = [&](int tm, int tn, int nst) {
-        r.variant = tm * 10000 + tn * 1000 + nst * 100 + 1;
-        return DC_OK;
-    };
-    const bool n160 = (d.Cout % 160 == 0) && d.epilogue == 0;
-    const int bn = n160 ? 160 : 128;
-    const long long big = ((M + 127) / 128) * ((d.Cout + bn - 1) / bn) * (d.splitk > 1 ? d.splitk : 1);
+    r.tn = bn / 32;
     // 2 LDS stages for the big tiles keep two workgroups resident per CU (2 waves per SIMD: one computes while the
     // other waits for its DMA); the small tiles afford 3 stages at the same residency.
     // (Staging the activation tile through registers and only the weights by LDS-DMA was measured: no gain over all-DMA.)
-    if (big >= 256) return n160 ? pick(4, 5, 2) : pick(4, 4, 2);
+    if (big >= 256) r.tm = 4, r.nst = 2;
     // Grids that cannot even put one workgroup on every CU (the 16x16 / 8x8 levels of a one- or two-frame decode) are bound by
     // the serial K loop: one LDS-DMA round trip per 64-wide step.  They take a deeper ring — the whole CU's LDS for one
     // workgroup, three or four stages in flight instead of one — with the same tile shape (so the statistics / GroupNorm partial
     // layouts are unchanged).  M = 512, N = 1280, K = 1280: 26 -> see tools/bench_gemm.py 2.
-    const long long small = ((M + 63) / 64) * ((d.Cout + bn - 1) / bn) * (d.splitk > 1 ? d.splitk : 1);
-    const int KT = (d.C1 + d.C2) >> 6;
-    if (small <= 256 && KT >= 6) return n160 ? pick(2, 5, 4) : pick(2, 4, 5);
-    return n160 ? pick(2, 5, 2) : pick(2, 4, 3);
+    else if (small <= 256 && KT >= 6) r.tm = 2, r.nst = bn == 160 ? 4 : 5;
+    else r.tm = 2, r.nst = bn == 160 ? 2 : 3;
+    r.variant = r.tm * 10000 + r.tn * 1000 + r.nst * 100 + 1;
+    // GroupNorm partials: chunk = (row tile within the sample, wave row); a row tile must not straddle two samples
+    if (d.gn_part_out && hw % (32 * r.tm) == 0) r.gn_chunks = (int)(hw / (32 * r.tm)) * 2;
+    return DC_OK;
 }
 
-namespace {
-
-int launch_gemm_variant(const dc_conv_desc& d, int variant, hipStream_t st)
+int dc_gemm_dma_launch(const dc_conv_desc& d, const dc_route& r, hipStream_t st)
 {
-    switch (variant) {
+    switch (r.variant) {
 #define DC_DMA_VARIANT(TM, TN, NST) \
-    case TM * 10000 + TN * 1000 + NST * 100 + 1: return launch_gemm<TM, TN, NST>(d, st);
+    case TM * 10000 + TN * 1000 + NST * 100 + 1: return launch_gemm<TM, TN, NST>(d, r.epi, st);
         DC_DMA_VARIANT(4, 5, 2)
         DC_DMA_VARIANT(4, 4, 2)
         DC_DMA_VARIANT(2, 5, 4)
@@ -540,47 +506,4 @@ int launch_gemm_variant(const dc_conv_desc& d, int variant, hipStream_t st)
 #undef DC_DMA_VARIANT
         default: return DC_ERR_INVALID;
     }
-}
-
-}  // namespace
-
-int dc_gemm_dma_launch(const dc_conv_desc& d, hipStream_t st)
-{
-    dc_route r{};
-    int rc = dc_gemm_dma_route(d, r);
-    if (rc != DC_OK) return rc;
-    dc_conv_desc q = d;
-    if (r.ln_first) {
-        if (!d.ln_scratch) return DC_ERR_INVALID;
-        const long long M = (long long)d.N * d.Ho * d.Wo;
-        rc = dc_ln_finalize(d.ln_stats, d.ln_scratch, M, d.ln_parts, d.C1 + d.C2, d.ln_eps, (void*)st);
-        if (rc != DC_OK) return rc;
-        q.ln_stats = d.ln_scratch;
-        q.ln_parts = 0;
-    }
-    switch (r.kernel) {
-        case DC_ROUTE_GEMM_ROWPANEL: return dc_gemm_rowpanel_launch(q, r.epi, st);
-        case DC_ROUTE_GEMM_P8: return dc_gemm_p8_launch(q, r.epi, st);
-        case DC_ROUTE_GEMM_WIDE: return dc_gemm_wide_launch(q, r.epi, st);
-        default: return launch_gemm_variant(q, r.variant, st);
-    }
-}
-
-// gn_part_out chunks per sample of this launch (0: not available)
-int dc_gemm_dma_gn_chunks(const dc_conv_desc& d)
-{
-    if (d.out_f32 || d.splitk > 1 || d.epilogue != 0 || d.ln_stats) return 0;
-    {   // the launch decision must be the one dc_gemm_dma_launch takes with gn_part_out set (the host sizes the buffer from here)
-        dc_conv_desc q = d;
-        if (!q.gn_part_out) q.gn_part_out = (float*)(uintptr_t)16;
-        if (dc_gemm_rowpanel_wanted(q, epi_mode(q))) return dc_gemm_rowpanel_gn_chunks(q);
-        if (dc_gemm_wide_wanted(q, epi_mode(q))) return dc_gemm_wide_gn_chunks(q);
-    }
-    const long long M = (long long)d.N * d.Ho * d.Wo;
-    const int bn = (d.Cout % 160 == 0) ? 160 : 128;
-    const long long big = ((M + 127) / 128) * ((d.Cout + bn - 1) / bn);
-    const int bm = big >= 256 ? 128 : 64;
-    const long long hw = (long long)d.Ho * d.Wo;
-    if (hw % bm) return 0;                                  // a row tile would straddle two samples
-    return (int)(hw / bm) * 2;
 }

@@ -25,8 +25,7 @@
 //        the barrier that closes the reading phase of either group.
 // Accumulation order over K is the tile kernels' (ascending 32-wide MFMA steps), the epilogue arithmetic is theirs
 // (dc_common.h): outputs are bit-identical with gemm_dma.hip / gemm_wide.hip.
-#include "dc_common.h"
-#include "../../include/diffcodec_hip.h"
+#include "dc_conv_route.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -315,23 +314,26 @@ int launch_p8(const dc_conv_desc& d, hipStream_t st)
 
 // The 256 x 256 kernel takes a launch when its epilogue modes apply (no residual, no statistics), the operands are whole tiles,
 // and the tile grid fills the chip for more than one round (K >= 640, at least 448 tiles).
-int dc_gemm_p8_wanted(const dc_conv_desc& d, int epi)
+int dc_gemm_p8_route(const dc_conv_desc& d, dc_route& r)
 {
     constexpr int min_k = 640, min_tiles = 448;
-    if (!(epi == 1 || epi == 3 || epi == 4 || epi == 5)) return 0;
-    if (d.ksize != 1 || d.gn_ab || d.splitk > 1 || d.out_f32 || d.C2 != 0 || d.residual || d.stats_out || d.gn_part_out) return 0;
-    if (d.ln_stats && d.ln_parts > 0) return 0;             // the dispatcher finalizes first and comes back with pairs
+    const int epi = r.epi;
+    if (!(epi == 1 || epi == 3 || epi == 4 || epi == 5)) return DC_ROUTE_PASS;
+    if (d.ksize != 1 || d.gn_ab || d.splitk > 1 || d.out_f32 || d.C2 != 0 || d.residual || d.stats_out || d.gn_part_out) return DC_ROUTE_PASS;
+    if (d.ln_stats && d.ln_parts > 0) return DC_ROUTE_PASS;  // the dispatcher finalizes first and comes back with pairs
     const int K = d.C1;
     const long long M = (long long)d.N * d.Ho * d.Wo;
-    if (K < 128 || (K & 63) || (M & 255) || (d.Cout & 127)) return 0;
+    if (K < 128 || (K & 63) || (M & 255) || (d.Cout & 127)) return DC_ROUTE_PASS;
     const long long tiles = (M >> 8) * ((d.Cout + 255) >> 8);
-    if ((d.Cout & 255) && d.Cout < 1792) return 0;          // a half-full last tile only where it is <= 1/15 of the columns' work
-    return K >= min_k && tiles >= min_tiles;
+    if ((d.Cout & 255) && d.Cout < 1792) return DC_ROUTE_PASS;   // a half-full last tile only where it is <= 1/15 of the columns' work
+    if (!(K >= min_k && tiles >= min_tiles)) return DC_ROUTE_PASS;
+    r.kernel = DC_ROUTE_GEMM_P8;
+    return DC_OK;
 }
 
-int dc_gemm_p8_launch(const dc_conv_desc& d, int epi, hipStream_t st)
+int dc_gemm_p8_launch(const dc_conv_desc& d, const dc_route& r, hipStream_t st)
 {
-    switch (epi) {
+    switch (r.epi) {
         case 1: return launch_p8<1>(d, st);
         case 3: return launch_p8<3>(d, st);
         case 4: return launch_p8<4>(d, st);

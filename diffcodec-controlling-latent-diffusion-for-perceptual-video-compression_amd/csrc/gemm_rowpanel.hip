@@ -27,8 +27,7 @@
 // vmcnt(P + T + R + 2 (F + G)) and the wait in front of the first read of the residual rows is vmcnt(P).
 // The accumulators see the same k order as gemm_dma.hip (ten 32-wide steps in sequence, v_mfma_f32_16x16x32_bf16) and the
 // epilogue arithmetic is the same expressions, so the bf16 outputs are bit-identical to the tile kernels'.
-#include "dc_common.h"
-#include "../../include/diffcodec_hip.h"
+#include "dc_conv_route.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -367,37 +366,32 @@ int launch_rowpanel(const dc_conv_desc& d, hipStream_t st)
 
 }  // namespace
 
-// GroupNorm-partials chunking of the row-panel kernel: one chunk per 32-row wave panel.
-int dc_gemm_rowpanel_gn_chunks(const dc_conv_desc& d)
-{
-    const long long hw = (long long)d.Ho * d.Wo;
-    return hw % 256 ? 0 : (int)(hw / 32);
-}
-
 // Takes a launch when K = 320 (one source; load-side transform: none, or a GroupNorm affine without SiLU), a specialised epilogue mode applies, the columns split
 // into whole 64-wide stages and the row panels fill the chip (>= one workgroup per CU).  Never depends on whether the optional
 // statistics outputs are set, so that the chunk query and the launch agree.
-int dc_gemm_rowpanel_wanted(const dc_conv_desc& d, int epi)
+int dc_gemm_rowpanel_route(const dc_conv_desc& d, dc_route& r)
 {
-    if (epi < 1 || epi > 5 || d.ksize != 1 || d.splitk > 1 || d.out_f32) return 0;
-    if (d.gn_ab && (d.gn_silu || d.gn_batch <= 0)) return 0;           // the affine on load only (the X prologue has no SiLU)
-    if (d.ln_parts > DC_LN_PARTS_MAX) return 0;                        // (the dispatcher finalizes first and comes back with pairs)
-    if (d.C1 != RP_K || d.C2 != 0 || d.x2 || !d.bias) return 0;
-    const long long M = (long long)d.N * d.Ho * d.Wo;
-    if (M % 256 || M < 256 * 256) return 0;
-    if (d.Cout % RP_SC || d.Cout < 5 * RP_SC) return 0;
-    if (((long long)d.Ho * d.Wo) % 256) return 0;           // GroupNorm partials need a panel inside one sample
-    return 1;
+    const int epi = r.epi;
+    if (epi < 1 || epi > 5 || d.ksize != 1 || d.splitk > 1 || d.out_f32) return DC_ROUTE_PASS;
+    if (d.gn_ab && (d.gn_silu || d.gn_batch <= 0)) return DC_ROUTE_PASS;   // the affine on load only (the X prologue has no SiLU)
+    if (d.ln_parts > DC_LN_PARTS_MAX) return DC_ROUTE_PASS;            // (the dispatcher finalizes first and comes back with pairs)
+    if (d.C1 != RP_K || d.C2 != 0 || d.x2 || !d.bias) return DC_ROUTE_PASS;
+    const long long M = (long long)d.N * d.Ho * d.Wo, hw = (long long)d.Ho * d.Wo;
+    if (M % 256 || M < 256 * 256) return DC_ROUTE_PASS;
+    if (d.Cout % RP_SC || d.Cout < 5 * RP_SC) return DC_ROUTE_PASS;
+    if (hw % 256) return DC_ROUTE_PASS;                     // GroupNorm partials need a panel inside one sample
+    if ((epi == 3 || epi == 5) && !d.ln_colsum) return DC_ERR_INVALID;
+    r.kernel = DC_ROUTE_GEMM_ROWPANEL;
+    r.gn = d.gn_part_out != nullptr;                        // (epilogue modes 1 / 2 only: the others are never chosen with gn_part_out)
+    if (r.gn) r.gn_chunks = (int)(hw / 32);                 // GroupNorm partials: one chunk per 32-row wave panel
+    return DC_OK;
 }
 
-int dc_gemm_rowpanel_launch(const dc_conv_desc& d, int epi, hipStream_t st)
+int dc_gemm_rowpanel_launch(const dc_conv_desc& d, const dc_route& r, hipStream_t st)
 {
-    const bool gn = d.gn_part_out != nullptr;
-    if (gn && epi > 2) return DC_ERR_INVALID;
-    if ((epi == 3 || epi == 5) && !d.ln_colsum) return DC_ERR_INVALID;
-    switch (epi) {
-        case 1: return gn ? launch_rowpanel<1, true>(d, st) : launch_rowpanel<1, false>(d, st);
-        case 2: return gn ? launch_rowpanel<2, true>(d, st) : launch_rowpanel<2, false>(d, st);
+    switch (r.epi) {
+        case 1: return r.gn ? launch_rowpanel<1, true>(d, st) : launch_rowpanel<1, false>(d, st);
+        case 2: return r.gn ? launch_rowpanel<2, true>(d, st) : launch_rowpanel<2, false>(d, st);
         case 3: return launch_rowpanel<3, false>(d, st);
         case 4: return launch_rowpanel<4, false>(d, st);
         case 5: return launch_rowpanel<5, false>(d, st);

@@ -17,8 +17,7 @@
 // either group;  WAR — stage k+2 reuses the slot of stage k-1, whose last reads (group 1, I(2k-1)) are retired by that
 // same lgkmcnt(0) before the barrier that opens I(2k), the earliest interval in which a piece of stage k+2 is issued.
 // No DMA is issued past the last stage (the epilogue stages its rows through the ring's LDS), so the final waits are vmcnt(0).
-#include "dc_common.h"
-#include "../../include/diffcodec_hip.h"
+#include "dc_conv_route.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -317,10 +316,10 @@ int launch_wide_st(const dc_conv_desc& d, hipStream_t st)
 }
 
 template <int TN, int EPI>
-int launch_wide(const dc_conv_desc& d, hipStream_t st)
+int launch_wide(const dc_conv_desc& d, int stats, hipStream_t st)
 {
     if constexpr (EPI == 1 || EPI == 2) {
-        switch ((d.stats_out ? 1 : 0) | (d.gn_part_out ? 2 : 0)) {
+        switch (stats) {
             case 1: return launch_wide_st<TN, EPI, 1>(d, st);
             case 2: return launch_wide_st<TN, EPI, 2>(d, st);
             case 3: return launch_wide_st<TN, EPI, 3>(d, st);
@@ -333,39 +332,37 @@ int launch_wide(const dc_conv_desc& d, hipStream_t st)
 
 }  // namespace
 
-// GroupNorm-partials chunking of the wide kernel: one chunk per 64-row wave row.
-int dc_gemm_wide_gn_chunks(const dc_conv_desc& d)
-{
-    const long long hw = (long long)d.Ho * d.Wo;
-    return hw % 256 ? 0 : (int)(hw / 64);
-}
-
 // The wide kernel takes a launch when the specialised epilogue modes apply, K is long enough for the 3-stage ring to pay for
 // the unoverlapped prologue / epilogue of a one-workgroup-per-CU kernel, and the tile grid fills the chip.
-int dc_gemm_wide_wanted(const dc_conv_desc& d, int epi)
+int dc_gemm_wide_route(const dc_conv_desc& d, dc_route& r)
 {
     constexpr int min_k = 640;
-    if (epi < 1 || epi > 5 || d.ksize != 1 || d.gn_ab || d.splitk > 1 || d.out_f32) return 0;
+    const int epi = r.epi;
+    if (epi < 1 || epi > 5 || d.ksize != 1 || d.gn_ab || d.splitk > 1 || d.out_f32) return DC_ROUTE_PASS;
     const int K = d.C1 + d.C2;
-    const long long M = (long long)d.N * d.Ho * d.Wo;
-    const bool geglu = epi >= 4;
-    const int bn = (!geglu && d.Cout % 160 == 0) ? 160 : 128;
-    if (d.Cout % bn) return 0;                              // whole N tiles only (the 128-row kernel clamps ragged ones)
-    if ((d.stats_out || d.gn_part_out) && ((long long)d.Ho * d.Wo) % 256) return 0;
+    const long long M = (long long)d.N * d.Ho * d.Wo, hw = (long long)d.Ho * d.Wo;
+    const int bn = dc_n_tile(d);
+    if (d.Cout % bn) return DC_ROUTE_PASS;                  // whole N tiles only (the 128-row kernel clamps ragged ones)
+    if ((d.stats_out || d.gn_part_out) && hw % 256) return DC_ROUTE_PASS;
     const long long tiles = ((M + 255) / 256) * (d.Cout / bn);
     // measured (tools/bench_gemm.py, same box, model batch 32): +4..13 % for K 640-2560, 0..-2 % at K 640 x N 640, -4 % at K 5120
-    return K >= min_k && K <= 2560 && M % 256 == 0 && tiles >= 192;
+    if (!(K >= min_k && K <= 2560 && M % 256 == 0 && tiles >= 192)) return DC_ROUTE_PASS;
+    r.kernel = DC_ROUTE_GEMM_WIDE;
+    r.tn = bn / 32;
+    r.st = epi <= 2 ? (d.stats_out ? 1 : 0) | (d.gn_part_out ? 2 : 0) : 0;
+    if (d.gn_part_out) r.gn_chunks = (int)(hw / 64);        // GroupNorm partials: one chunk per 64-row wave row
+    return DC_OK;
 }
 
-int dc_gemm_wide_launch(const dc_conv_desc& d, int epi, hipStream_t st)
+int dc_gemm_wide_launch(const dc_conv_desc& d, const dc_route& r, hipStream_t st)
 {
-    const bool n160 = epi < 4 && d.Cout % 160 == 0;
-    switch (epi) {
-        case 1: return n160 ? launch_wide<5, 1>(d, st) : launch_wide<4, 1>(d, st);
-        case 2: return n160 ? launch_wide<5, 2>(d, st) : launch_wide<4, 2>(d, st);
-        case 3: return n160 ? launch_wide<5, 3>(d, st) : launch_wide<4, 3>(d, st);
-        case 4: return launch_wide<4, 4>(d, st);
-        case 5: return launch_wide<4, 5>(d, st);
+    const bool n160 = r.tn == 5;
+    switch (r.epi) {
+        case 1: return n160 ? launch_wide<5, 1>(d, r.st, st) : launch_wide<4, 1>(d, r.st, st);
+        case 2: return n160 ? launch_wide<5, 2>(d, r.st, st) : launch_wide<4, 2>(d, r.st, st);
+        case 3: return n160 ? launch_wide<5, 3>(d, r.st, st) : launch_wide<4, 3>(d, r.st, st);
+        case 4: return launch_wide<4, 4>(d, r.st, st);
+        case 5: return launch_wide<4, 5>(d, r.st, st);
         default: return DC_ERR_INVALID;
     }
 }

@@ -11,20 +11,7 @@
 //   K-tile's global loads are issued before the current tile's MFMAs (one barrier per K-step).
 //   The MFMA computes the transposed tile (A-operand = weights, B-operand = pixels) so that each lane ends up
 //   with 4 consecutive output channels of one pixel -> 8-byte NHWC stores, float4 bias loads.
-#include "dc_common.h"
-#include "../../include/diffcodec_hip.h"
-
-// conv3x3_tile.hip: LDS-staged 2D-tile kernel for 3x3 stride-1 convs with tile-aligned outputs
-int dc_conv3x3_tile_supported(const dc_conv_desc& d);
-int dc_conv3x3_tile_launch(const dc_conv_desc& d, hipStream_t st);
-// gemm_dma.hip: LDS-DMA pipelined GEMM for 1x1 convs / linears without a load-side transform
-int dc_gemm_dma_supported(const dc_conv_desc& d);
-int dc_gemm_dma_launch(const dc_conv_desc& d, hipStream_t st);
-int dc_gemm_dma_route(const dc_conv_desc& d, dc_route& r);
-int dc_conv3x3_tile_variant(const dc_conv_desc& d);
-int dc_conv3x3_tile_epi(const dc_conv_desc& d);
-int dc_gemm_dma_gn_chunks(const dc_conv_desc& d);
-int dc_conv3x3_tile_gn_chunks(const dc_conv_desc& d);
+#include "dc_conv_route.h"
 
 namespace {
 
@@ -344,14 +331,13 @@ __global__ void splitk_finish_kernel(const dc_conv_desc d, long long total4)
 }
 
 template <int WM, int WN, int TM, int TN>
-int launch_cfg(const dc_conv_desc& d, hipStream_t st)
+int launch_cfg(const dc_conv_desc& d, const dc_route& r, hipStream_t st)
 {
     constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
     const int M = d.N * d.Ho * d.Wo;
     const int nblk = dc_cdiv(M, BM) * dc_cdiv(d.Cout, BN);
     const dim3 grid(nblk, d.splitk > 1 ? d.splitk : 1);
     const size_t lds = 2 * (BM + BN) * 128;
-    const bool gn = d.gn_ab != nullptr;
 #define DC_IGEMM_LAUNCH(KS3, GN)                                                                              \
     do {                                                                                                      \
         auto kern = igemm_kernel<WM, WN, TM, TN, KS3, GN>;                                                    \
@@ -359,36 +345,58 @@ int launch_cfg(const dc_conv_desc& d, hipStream_t st)
         dc_set_max_dyn_lds((const void*)kern, (int)lds, attr_done);                                           \
         hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, d);                                                \
     } while (0)
-    if (d.ksize == 3) {
-        if (gn) DC_IGEMM_LAUNCH(true, true);
+    if (r.ks3) {
+        if (r.gn) DC_IGEMM_LAUNCH(true, true);
         else DC_IGEMM_LAUNCH(true, false);
     } else {
-        if (gn) DC_IGEMM_LAUNCH(false, true);
+        if (r.gn) DC_IGEMM_LAUNCH(false, true);
         else DC_IGEMM_LAUNCH(false, false);
     }
 #undef DC_IGEMM_LAUNCH
     return dc_launch_status();
 }
 
-}  // namespace
-
-extern "C" int dc_conv_gn_part_chunks(const dc_conv_desc* dp)
+// The gather GEMM takes every launch the other families pass.  Tile choice: wide-N tile (160) when dc_n_tile says so, else 128;
+// tall-M tile (128) only when that still yields >= 2 workgroups per CU.
+int igemm_route(const dc_conv_desc& d, dc_route& r)
 {
-    if (!dp || dp->splitk > 1) return 0;
-    if (dc_gemm_dma_supported(*dp)) return dc_gemm_dma_gn_chunks(*dp);
-    if (dc_conv3x3_tile_supported(*dp)) return dc_conv3x3_tile_gn_chunks(*dp);
-    return 0;                                               // gather GEMM (strided / GN-on-load 1x1): no statistics epilogue
+    const long long M = (long long)d.N * d.Ho * d.Wo;
+    const int bn = dc_n_tile(d);
+    const long long big_tiles = ((M + 127) / 128) * ((d.Cout + bn - 1) / bn) * d.splitk;
+    r.kernel = DC_ROUTE_IGEMM;
+    r.tm = big_tiles >= 512 ? 4 : 2;
+    r.tn = bn / 32;
+    r.variant = r.tm * 10 + r.tn;
+    r.ks3 = d.ksize == 3;
+    r.gn = d.gn_ab != nullptr;
+    return DC_OK;
 }
 
-extern "C" long long dc_conv_igemm_ws_bytes(const dc_conv_desc* d)
+int igemm_launch(const dc_conv_desc& d, const dc_route& r, hipStream_t st)
 {
-    if (!d || d->splitk <= 1) return 0;
-    return (long long)d->N * d->Ho * d->Wo * d->Cout * 4 * d->splitk;
+    switch (r.variant) {
+        case 45: return launch_cfg<2, 2, 4, 5>(d, r, st);
+        case 44: return launch_cfg<2, 2, 4, 4>(d, r, st);
+        case 25: return launch_cfg<2, 2, 2, 5>(d, r, st);
+        default: return launch_cfg<2, 2, 2, 4>(d, r, st);
+    }
+}
+
+// every split must own a non-empty range of the `units` its kernel partitions, or its slab would stay unwritten: shrink to the
+// fixpoint of splitk = ceil(units / ceil(units / splitk))
+int splitk_fixpoint(int splitk, int units)
+{
+    for (;;) {
+        const int per = (units + splitk - 1) / splitk, s2 = (units + per - 1) / per;
+        if (s2 == splitk) return splitk;
+        splitk = s2;
+    }
 }
 
 // Descriptor checks, normalisation (split-K fixpoint, row_add_stride) and kernel choice: the one routing function of
-// dc_conv_igemm_bf16 and dc_conv_route.  `d` receives the normalised descriptor the kernels are launched with.
-static int conv_route(const dc_conv_desc& in, dc_conv_desc& d, dc_route& r)
+// dc_conv_igemm_bf16, dc_conv_route, dc_conv_instance and dc_conv_gn_part_chunks.  `d` receives the normalised descriptor the kernels
+// are launched with.  Each family is asked once, in priority order: the 1x1 GEMMs, the halo-tile 3x3 kernel, the gather GEMM.
+int conv_route(const dc_conv_desc& in, dc_conv_desc& d, dc_route& r)
 {
     d = in;
     r = dc_route{};
@@ -396,10 +404,7 @@ static int conv_route(const dc_conv_desc& in, dc_conv_desc& d, dc_route& r)
     if (!d.x1 || !d.w || !d.out) return DC_ERR_INVALID;
     if (d.ksize != 1 && d.ksize != 3) return DC_ERR_INVALID;
     if (Cin <= 0 || (Cin & 63) || (d.C1 & 63) || (d.C2 && !d.x2)) return DC_ERR_INVALID;
-    // Cout: multiples of 16 everywhere; the halo-tile 3x3 kernel alone also takes multiples of 4 (clamped weight rows,
-    // guarded 4-channel epilogue) — UNet conv_out 320->4 runs there on one mostly empty N-tile instead of on the VALU
-    if (d.Cout <= 0 || (d.Cout & 3)) return DC_ERR_INVALID;
-    if ((d.Cout & 15) && !(dc_conv3x3_tile_supported(d) && !dc_gemm_dma_supported(d) && d.splitk <= 1)) return DC_ERR_INVALID;
+    if (d.Cout <= 0 || (d.Cout & 3)) return DC_ERR_INVALID;             // (multiples of 4: the halo-tile kernel only, see below)
     if (d.N <= 0 || d.H <= 0 || d.W <= 0 || d.Ho <= 0 || d.Wo <= 0) return DC_ERR_INVALID;
     if (d.ksize == 1 && (d.stride != 1 || d.upsample || d.Ho != d.H || d.Wo != d.W)) return DC_ERR_INVALID;
     if (d.ksize == 3) {
@@ -414,41 +419,40 @@ static int conv_route(const dc_conv_desc& in, dc_conv_desc& d, dc_route& r)
     if (d.splitk < 1) d.splitk = 1;
     if (d.row_add_stride == 0) d.row_add_stride = d.Cout;
     if (d.epilogue == 1 && (d.splitk > 1 || (d.Cout & 31) || d.residual || d.row_add || d.out_f32)) return DC_ERR_INVALID;
-    if (d.splitk > 1) {
-        // every split must own a non-empty K range, or its slab would stay unwritten: shrink to the fixpoint of
-        // splitk = ceil(KT / ceil(KT / splitk)) (KT = 64-wide K steps, the unit all three kernels partition by)
-        const int nkc = (d.C1 + d.C2) >> 6;
-        const bool tile = !dc_gemm_dma_supported(d) && dc_conv3x3_tile_supported(d);     // splits channel chunks, not taps
-        const int KT = (d.ksize == 3 && !tile) ? 9 * nkc : nkc;
-        for (;;) {
-            const int per = (KT + d.splitk - 1) / d.splitk, s2 = (KT + per - 1) / per;
-            if (s2 == d.splitk) break;
-            d.splitk = s2;
-        }
+    const int asked = d.splitk, nkc = Cin >> 6;
+    d.splitk = r.splitk = splitk_fixpoint(asked, nkc);                  // the GEMMs and the halo-tile kernel split 64-channel chunks,
+    int rc = dc_gemm_dma_route(d, r);
+    if (rc == DC_ROUTE_PASS) rc = dc_conv3x3_tile_route(d, r);
+    if (rc == DC_ROUTE_PASS) {
+        d.splitk = r.splitk = splitk_fixpoint(asked, (d.ksize == 3 ? 9 : 1) * nkc);   // the gather GEMM (tap, chunk) steps
+        rc = igemm_route(d, r);
     }
-    r.splitk = d.splitk;
-    const long long M = (long long)d.N * d.Ho * d.Wo;
-    // Tile choice: wide-N tile (160) when Cout is a multiple of 160 (all SD-1.5 UNet widths), else 128;
-    // tall-M tile (128) only when that still yields >= 2 workgroups per CU.
-    const bool n160 = (d.Cout % 160 == 0) && d.epilogue == 0;
-    const int bn = n160 ? 160 : 128;
-    const long long big_tiles = ((M + 127) / 128) * ((d.Cout + bn - 1) / bn) * d.splitk;
-    if ((d.ln_stats || d.stats_out) && !dc_gemm_dma_supported(d)) return DC_ERR_INVALID;   // LDS-DMA GEMM epilogue only
-    if (d.gn_part_out && dc_conv_gn_part_chunks(&d) == 0) return DC_ERR_INVALID;
-    if (dc_gemm_dma_supported(d)) {
-        const int rc = dc_gemm_dma_route(d, r);
-        r.splitk = d.splitk;
-        return rc;
-    }
-    if (dc_conv3x3_tile_supported(d)) {
-        r.kernel = DC_ROUTE_CONV3X3_TILE;
-        r.variant = dc_conv3x3_tile_variant(d);
-        r.epi = dc_conv3x3_tile_epi(d);
-        return DC_OK;
-    }
-    r.kernel = DC_ROUTE_IGEMM;
-    r.variant = (big_tiles >= 512 ? 40 : 20) + (n160 ? 5 : 4);
+    if (rc != DC_OK) return rc;
+    // Cout: multiples of 16 everywhere; the halo-tile 3x3 kernel alone also takes multiples of 4 (clamped weight rows,
+    // guarded 4-channel epilogue) — UNet conv_out 320->4 runs there on one mostly empty N-tile instead of on the VALU
+    if ((d.Cout & 15) && !(r.kernel == DC_ROUTE_CONV3X3_TILE && asked == 1)) return DC_ERR_INVALID;
+    const bool gemm = r.kernel != DC_ROUTE_CONV3X3_TILE && r.kernel != DC_ROUTE_IGEMM;
+    if ((d.ln_stats || d.stats_out) && !gemm) return DC_ERR_INVALID;     // LDS-DMA GEMM epilogue only
+    if (d.gn_part_out && r.gn_chunks == 0) return DC_ERR_INVALID;       // (the gather GEMM has no statistics epilogue)
     return DC_OK;
+}
+
+}  // namespace
+
+extern "C" int dc_conv_gn_part_chunks(const dc_conv_desc* dp)
+{
+    if (!dp || dp->splitk > 1) return 0;
+    // the launch decision must be the one dc_conv_igemm_bf16 takes with gn_part_out set (the host sizes the buffer from here)
+    dc_conv_desc q = *dp, d;
+    if (!q.gn_part_out) q.gn_part_out = (float*)(uintptr_t)16;
+    dc_route r;
+    return conv_route(q, d, r) == DC_OK ? r.gn_chunks : 0;
+}
+
+extern "C" long long dc_conv_igemm_ws_bytes(const dc_conv_desc* d)
+{
+    if (!d || d->splitk <= 1) return 0;
+    return (long long)d->N * d->Ho * d->Wo * d->Cout * 4 * d->splitk;
 }
 
 extern "C" int dc_conv_route(const dc_conv_desc* dp, int* info)
@@ -468,6 +472,30 @@ extern "C" int dc_conv_route(const dc_conv_desc* dp, int* info)
     return DC_OK;
 }
 
+extern "C" int dc_conv_instance(const dc_conv_desc* dp, int* info)
+{
+    if (!info) return DC_ERR_INVALID;
+    for (int i = 0; i < DC_CONV_INSTANCE_INTS; ++i) info[i] = 0;
+    if (!dp) return DC_ERR_INVALID;
+    dc_conv_desc d;
+    dc_route r;
+    const int rc = conv_route(*dp, d, r);
+    if (rc != DC_OK) return rc;
+    info[0] = r.kernel;
+    int* a = info + 1;                                      // the template arguments, in the order of the kernel's template
+    switch (r.kernel) {
+        case DC_ROUTE_GEMM_DMA: a[0] = r.tm, a[1] = r.tn, a[2] = r.nst, a[3] = r.epi; break;
+        case DC_ROUTE_GEMM_WIDE: a[0] = r.tn, a[1] = r.epi, a[2] = r.st; break;
+        case DC_ROUTE_GEMM_P8: a[0] = r.epi; break;
+        case DC_ROUTE_GEMM_ROWPANEL: a[0] = r.epi, a[1] = r.gn; break;
+        case DC_ROUTE_CONV3X3_TILE:
+            a[0] = r.tm, a[1] = r.tn, a[2] = r.gn, a[3] = r.nst, a[4] = r.epi, a[5] = r.fast, a[6] = r.ups, a[7] = r.sh;
+            break;
+        default: a[0] = r.tm, a[1] = r.tn, a[2] = r.ks3, a[3] = r.gn; break;
+    }
+    return DC_OK;
+}
+
 extern "C" int dc_conv_igemm_bf16(const dc_conv_desc* dp, void* stream)
 {
     if (!dp) return DC_ERR_INVALID;
@@ -477,17 +505,20 @@ extern "C" int dc_conv_igemm_bf16(const dc_conv_desc* dp, void* stream)
     int rc = conv_route(*dp, d, r);
     if (rc != DC_OK) return rc;
     if (d.splitk > 1 && !d.splitk_ws) return DC_ERR_INVALID;
+    if (r.ln_first) {                                       // raw LayerNorm partials -> (mean, rstd) pairs in the caller's scratch
+        if (!d.ln_scratch) return DC_ERR_INVALID;
+        rc = dc_ln_finalize(d.ln_stats, d.ln_scratch, (long long)d.N * d.Ho * d.Wo, d.ln_parts, d.C1 + d.C2, d.ln_eps, stream);
+        if (rc != DC_OK) return rc;
+        d.ln_stats = d.ln_scratch;
+        d.ln_parts = 0;
+    }
     switch (r.kernel) {
-        case DC_ROUTE_CONV3X3_TILE: rc = dc_conv3x3_tile_launch(d, st); break;
-        case DC_ROUTE_IGEMM:
-            switch (r.variant) {
-                case 45: rc = launch_cfg<2, 2, 4, 5>(d, st); break;
-                case 44: rc = launch_cfg<2, 2, 4, 4>(d, st); break;
-                case 25: rc = launch_cfg<2, 2, 2, 5>(d, st); break;
-                default: rc = launch_cfg<2, 2, 2, 4>(d, st); break;
-            }
-            break;
-        default: rc = dc_gemm_dma_launch(d, st); break;        // re-derives the same dc_gemm_dma_route decision
+        case DC_ROUTE_GEMM_DMA: rc = dc_gemm_dma_launch(d, r, st); break;
+        case DC_ROUTE_GEMM_WIDE: rc = dc_gemm_wide_launch(d, r, st); break;
+        case DC_ROUTE_GEMM_P8: rc = dc_gemm_p8_launch(d, r, st); break;
+        case DC_ROUTE_GEMM_ROWPANEL: rc = dc_gemm_rowpanel_launch(d, r, st); break;
+        case DC_ROUTE_CONV3X3_TILE: rc = dc_conv3x3_tile_launch(d, r, st); break;
+        default: rc = igemm_launch(d, r, st); break;
     }
     if (rc != DC_OK) return rc;
     if (d.splitk > 1) {

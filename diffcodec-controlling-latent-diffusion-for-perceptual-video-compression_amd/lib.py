@@ -42,6 +42,7 @@ SIGNATURES = {
     "dc_f32_to_bf16": [vp, vp, i64, vp],
     "dc_conv_igemm_bf16": [POINTER(ConvDesc), vp],
     "dc_conv_route": [POINTER(ConvDesc), POINTER(i32)],
+    "dc_conv_instance": [POINTER(ConvDesc), POINTER(i32)],
     "dc_conv_igemm_ws_bytes": [POINTER(ConvDesc)],
     "dc_gemm_row_stats_parts": [i32],
     "dc_conv_gn_part_chunks": [POINTER(ConvDesc)],

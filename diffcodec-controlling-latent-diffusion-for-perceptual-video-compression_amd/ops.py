@@ -198,8 +198,25 @@ def conv_route(d):
     return ConvRoute(tuple(info))
 
 
+# template arguments of each kernel's instance, in the order dc_conv_instance reports them
+INSTANCE_ARGS = {"gemm_dma": ("TM", "TN", "NST", "EPI"), "gemm_wide": ("TN", "EPI", "ST"), "gemm_p8": ("EPI",),
+                 "gemm_rowpanel": ("EPI", "GN"), "conv3x3_tile": ("TM", "TN", "GN", "NSTB", "EPI", "FAST", "UPS", "SH"),
+                 "igemm": ("TM", "TN", "KS3", "GN")}
+
+
+def conv_instance(d):
+    """The kernel instance dc_conv_igemm_bf16 launches for a ConvDesc (dc_conv_instance): {"kernel": name, template argument: value}.
+    Raises as conv_route does."""
+    info = (ctypes.c_int * 9)()
+    rc = lib.load().dc_conv_instance(d, info)
+    if rc != 0:
+        raise lib.HipLaunchError(f"dc_conv_instance returned {rc} (invalid argument)")
+    kernel = ROUTE_NAMES[info[0]]
+    return dict(zip(INSTANCE_ARGS[kernel], info[1:]), kernel=kernel)
+
+
 def rowpanel_takes(rows, rows_per_sample, cin, cout):
-    """Mirror of dc_gemm_rowpanel_wanted (csrc/gemm_rowpanel.hip) for plain / residual / folded-LN 1x1 launches: the K = 320 kernel that
+    """Mirror of dc_gemm_rowpanel_route (csrc/gemm_rowpanel.hip) for plain / residual / folded-LN 1x1 launches: the K = 320 kernel that
     keeps a 256-row panel in registers — the only GEMM of the family that can apply a GroupNorm affine on load (`gn_ab` without SiLU).
     The C side stays the authority: a launch this rule admits and the library does not take fails with DC_ERR_INVALID."""
     return cin == 320 and cout >= 320 and cout % 64 == 0 and rows >= 65536 and rows % 256 == 0 and rows_per_sample % 256 == 0
@@ -267,13 +284,6 @@ def conv(x1, pc, *, x2=None, gn_ab=None, gn_silu=False, row_add=None, residual=N
         ln_parts = int(ln_stats.shape[1])
     if ln_stats is not None or stats_out is not None:
         splitk = 1                          # the folded LayerNorm / row statistics live in the unsplit bf16 epilogue
-    if splitk is None:
-        tile3 = k == 3 and stride == 1 and pad == 1 and (wo % 16 == 0 and ho % 4 == 0 or wo == 8 and ho % 8 == 0 and not upsample)
-        if k == 3 and stride == 2 and not pc.geglu:
-            splitk = _pick_splitk_strided(m, pc.cout, kt)
-        else:
-            splitk = 1 if pc.geglu else _pick_splitk(m, pc.cout, kt, pc.cin // 64 if tile3 else None, rows_per_image=ho * wo)
-    ws = torch.empty((splitk, m, pc.cout), device=x1.device, dtype=F32) if splitk > 1 else None
     if gn_ab is not None:
         _chk(gn_ab, F32, "gn_ab")
         assert gn_ab.shape[1] == pc.cin
@@ -293,12 +303,23 @@ def conv(x1, pc, *, x2=None, gn_ab=None, gn_silu=False, row_add=None, residual=N
         assert row_add.dtype == F32 and row_add.is_cuda and row_add.shape == (n, pc.cout) and row_add.stride(1) == 1
         ras = row_add.stride(0)
     d = ConvDesc(x1=x1.data_ptr(), x2=_ptr(x2), w=pc.w.data_ptr(), bias=_ptr(pc.bias), gn_ab=_ptr(gn_ab),
-                 row_add=_ptr(row_add), residual=_ptr(residual), out=out.data_ptr(), splitk_ws=_ptr(ws),
+                 row_add=_ptr(row_add), residual=_ptr(residual), out=out.data_ptr(), splitk_ws=0,
                  N=n, H=h, W=w, C1=c1, C2=c2, Cout=pc.cout, ksize=k, stride=stride, pad=int(pad), upsample=int(upsample),
                  Ho=ho, Wo=wo, gn_silu=int(gn_silu), epilogue=1 if pc.geglu else 0, out_f32=int(out_f32),
-                 out_scale=float(out_scale), splitk=int(splitk), gn_batch=0 if gn_ab is None else gn_ab.shape[0],
+                 out_scale=float(out_scale), splitk=int(splitk or 1), gn_batch=0 if gn_ab is None else gn_ab.shape[0],
                  act=int(act), row_add_stride=int(ras), ln_stats=_ptr(ln_stats), ln_colsum=_ptr(pc.colsum if ln_stats is not None else None),
                  stats_out=_ptr(stats_out), gn_part_out=0, ln_parts=ln_parts, ln_eps=float(ln_eps), ln_scratch=_ptr(ln_scratch))
+    if splitk is None:
+        if k == 3 and stride == 2 and not pc.geglu:
+            splitk = _pick_splitk_strided(m, pc.cout, kt)
+        elif pc.geglu:
+            splitk = 1
+        else:                               # the halo-tile 3x3 kernel splits 64-channel chunks, the others 64-wide K steps
+            tile3 = k == 3 and stride == 1 and conv_route(d).kernel == "conv3x3_tile"
+            splitk = _pick_splitk(m, pc.cout, kt, pc.cin // 64 if tile3 else None, rows_per_image=ho * wo)
+        d.splitk = int(splitk)
+    ws = torch.empty((splitk, m, pc.cout), device=x1.device, dtype=F32) if splitk > 1 else None
+    d.splitk_ws = _ptr(ws)
     if ln_parts > 0 and conv_route(d).ln_first:
         # scratch for (mean, rstd) only where the dispatcher runs the finalize pass first (the row-panel kernel finalizes in its
         # prologue): the library's own routing decides, not a Python restatement of it
@@ -313,12 +334,13 @@ def conv(x1, pc, *, x2=None, gn_ab=None, gn_silu=False, row_add=None, residual=N
     meta = None
     if lib.TIMER is not None:
         kk = pc.cin * k * k
-        if k == 1 and (gn_ab is None or (not gn_silu and x2 is None and rowpanel_takes(m, ho * wo, pc.cin, pc.cout))):
-            fam = "gemm_dma_kernel + gemm_wide_kernel + gemm_p8_kernel + gemm_rowpanel_kernel (1x1 conv / linear GEMM family)"
-        elif k == 3 and stride == 1 and pad == 1 and (wo % 16 == 0 and ho % 4 == 0 or wo == 8 and ho % 8 == 0 and not upsample):
+        kernel = conv_route(d).kernel
+        if kernel == "conv3x3_tile":
             fam = "conv3x3_tile_kernel (3x3 stride-1 halo-tile conv)"
-        else:
+        elif kernel == "igemm":
             fam = "igemm_kernel (strided / GN-on-load gather GEMM)"
+        else:
+            fam = "gemm_dma_kernel + gemm_wide_kernel + gemm_p8_kernel + gemm_rowpanel_kernel (1x1 conv / linear GEMM family)"
         # algorithmic bytes: every operand once — activations (low-res input for the fused upsample), weights, output, residual
         nbytes = 2.0 * (n * h * w * pc.cin + pc.cout * kk + m * cout_eff * (2 if out_f32 else 1) + (m * pc.cout if residual is not None else 0))
         meta = _meta(fam, f"{k}x{k} s{stride} up{int(upsample)} M={m} N={pc.cout} K={kk} gn={int(gn_ab is not None)} geglu={int(pc.geglu)} "

@@ -145,6 +145,18 @@ int dc_conv_igemm_bf16(const dc_conv_desc* desc, void* stream);
 #define DC_ROUTE_CONV3X3_TILE 5
 #define DC_ROUTE_IGEMM 6
 int dc_conv_route(const dc_conv_desc* desc, int* info);
+/* The kernel instance dc_conv_igemm_bf16 launches for `desc`, from the same routing function: returns as dc_conv_route does and
+ * fills info[DC_CONV_INSTANCE_INTS] with info[0] = kernel (DC_ROUTE_*) followed by the template arguments of that kernel's instance
+ * (unused slots 0):
+ *   gemm_dma       gemm_dma_kernel<TM, TN, NST, EPI>: wave tile rows / columns in 16s, LDS stages, epilogue mode;
+ *   gemm_wide      gemm_wide_kernel<TN, EPI, ST>: ST bit 0 = row statistics out, bit 1 = GroupNorm partials out;
+ *   gemm_p8        gemm_p8_kernel<EPI>;
+ *   gemm_rowpanel  gemm_rowpanel_kernel<EPI, GN>: GN = GroupNorm partials out;
+ *   conv3x3_tile   conv3x3_tile_kernel<TM, TN, GN, NSTB, EPI, FAST, UPS, SH>: GN = GroupNorm affine on load, weight-ring stages,
+ *                  half-step pipeline and its fused-upsample / 8-wide-map forms;
+ *   igemm          igemm_kernel<2, 2, TM, TN, KS3, GN>: 3x3 gather, GroupNorm affine on load. */
+#define DC_CONV_INSTANCE_INTS 9
+int dc_conv_instance(const dc_conv_desc* desc, int* info);
 /* Workspace bytes needed for splitk>1 (0 otherwise). */
 long long dc_conv_igemm_ws_bytes(const dc_conv_desc* desc);
 /* Partials per output row that a 1x1 / linear launch with `stats_out` writes (one per wave column slice of the tile grid). */

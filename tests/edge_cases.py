@@ -6,8 +6,8 @@ Plain module (imported by tests/test_edge_coverage.py on the CPU and tests/test_
   pitched view) hold a NaN with a distinctive payload.  An output view is pre-filled with the same pattern, so an element the
   kernel never writes stays non-finite (L.check treats it as infinitely wrong); `bad()` lists every guard element that no longer
   holds the pattern, compared as integers.
-* `conv_key` / `attention_key`: the kernel instance a launch runs, from the dispatcher's own route query (dc_conv_route,
-  dc_attention_route) refined by the descriptor flags that pick a different template inside the launchers.
+* `conv_key` / `attention_key`: the kernel instance a launch runs, from the dispatcher's own queries (dc_conv_route and
+  dc_conv_instance, dc_attention_route).
 * `CONV_CASES`, `ATTN_CASES`, `NORM_CASES`: the tables.  Every conv / attention case declares the instance it targets;
   tests/test_edge_coverage.py proves that every instance the dispatcher can reach has a case and that every case routes where it
   says."""
@@ -153,47 +153,27 @@ def case_desc(c):
     return d
 
 
-def conv_key(d, route=None):
-    """Instance key of a dc_conv_desc: (kernel, variant, epi, split-K > 1, ln_first) from dc_conv_route, refined by the flags that
-    select another template in the launchers:
-      conv3x3_tile  GroupNorm on load, fused upsample, narrow map (Wo < 16), and the (TN, NSTB, FAST) template arguments
-                    dc_conv3x3_tile_launch picks (`_tile_template`);
-      gemm_rowpanel GroupNorm partials out (GN template flag);
-      gemm_wide     statistics template ST (stats_out | gn_part_out) of the epi 1 / 2 kernels, and TN (160- or 128-column tile);
-      igemm         3x3 gather, GroupNorm on load."""
+def conv_key(d):
+    """Instance key of a dc_conv_desc: (kernel, variant, epi, split-K > 1, ln_first) from dc_conv_route, then the template arguments
+    of the launched instance that those five do not imply, from dc_conv_instance:
+      conv3x3_tile  GN (GroupNorm on load), TN, NSTB, FAST — and the fused upsample and the narrow map (Wo < 16), which are run-time
+                    paths of the FAST = 0 instances, so they come from the descriptor;
+      gemm_rowpanel GN (GroupNorm partials out);
+      gemm_wide     ST (statistics outputs of the epi 1 / 2 kernels) and TN (160- or 128-column tile);
+      igemm         KS3 (3x3 gather), GN (GroupNorm on load)."""
     from diffcodec_amd import ops
-    r = ops.conv_route(d) if route is None else route
+    r, t = ops.conv_route(d), ops.conv_instance(d)
     key = (r.kernel, r.variant, r.epi, r.splitk > 1, r.ln_first)
     if r.kernel == "conv3x3_tile":
-        tn, nst, fast = _tile_template(d, r.variant, r.splitk)
-        key += (("gn", bool(d.gn_ab)), ("up", bool(d.upsample)), ("narrow", d.Wo < 16), ("tn", tn), ("nst", nst), ("fast", fast))
+        key += (("gn", bool(t["GN"])), ("up", bool(d.upsample)), ("narrow", d.Wo < 16), ("tn", t["TN"]), ("nst", t["NSTB"]),
+                ("fast", bool(t["FAST"])))
     elif r.kernel == "gemm_rowpanel":
-        key += (("gn_part", bool(d.gn_part_out)),)
+        key += (("gn_part", bool(t["GN"])),)
     elif r.kernel == "gemm_wide":
-        key += (("st", (1 if d.stats_out else 0) | (2 if d.gn_part_out else 0) if r.epi in (1, 2) else 0),
-                ("tn", 5 if r.epi < 4 and d.Cout % 160 == 0 else 4))
+        key += (("st", t["ST"]), ("tn", t["TN"]))
     elif r.kernel == "igemm":
-        key += (("k3", d.ksize == 3), ("gn", bool(d.gn_ab)))
+        key += (("k3", bool(t["KS3"])), ("gn", bool(t["GN"])))
     return key
-
-
-def _tile_template(d, variant, splitk):
-    """(TN, NSTB, FAST) of the launch_tile<TM, TN, NSTB, FAST, UPS, SH> instance dc_conv3x3_tile_launch (conv3x3_tile.hip) takes for
-    a descriptor of tile variant `variant` (TM = 2 for variant 2, else 4; UPS / SH = fused upsample / narrow map without GroupNorm)."""
-    tn = 5 if d.Cout % 160 == 0 else 4
-    if not d.upsample and d.Wo >= 16 and d.Cout % 8 == 0:             # plain maps: half-step pipeline
-        th, bn = (8 if variant == 4 else 4), (160 if tn == 5 else 128)
-        wgs = d.N * (d.Ho // th) * (d.Wo // 16) * -(-d.Cout // bn) * splitk
-        if d.Cout <= 32:
-            return 1, 2, True
-        return tn, (4 if wgs <= 256 else 2), True
-    if d.Cout % 8 == 0 and not d.gn_ab and ((d.upsample and d.Wo >= 16) or (d.Wo == 8 and not d.upsample)):
-        return tn, 2, True
-    if d.Cout <= 32 and variant != 8:
-        return 1, 3, False
-    if variant in (4, 8):
-        return (5, 2, False) if tn == 5 else (4, 3, False)
-    return tn, 3, False
 
 
 def key_str(key):
