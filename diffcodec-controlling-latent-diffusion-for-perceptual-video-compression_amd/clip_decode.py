@@ -261,14 +261,10 @@ def blend_frames(unit_u8, units, height, width, overlap=64):
     return {f: t.cpu().numpy() for f, t in _blend_frame_tensors(unit_u8, units, height, width, overlap).items()}
 
 
-def score_frames(frames, source, lpips=None):
-    """{frame: uint8 [H,W,3] tensor} -> {frame: {"psnr": dB, "ms_ssim": value}} against `source.ground_truth(frame)`, with L = 255
-    (test_utils.py:23-24, :55; validation.py:147-150 on x / 255 gives the same values), on the device of the frames.
-    `lpips` (a `metrics.LPIPS` with weights loaded) adds "lpips": as test_utils.py:58 computes it, on frame / 255 with
-    normalize=False.  That is the reference's quirk, kept for comparable numbers: it feeds [0,1] images where the net expects
-    [-1,1] (the library's `normalize=True` would map them)."""
+def _score_frames(frames, source, lpips=None, fid=None):
+    """(scores, {frame: (decoded [64], truth [64])} fp32 FID feature rows on the host, empty without `fid`)"""
     from . import metrics
-    scores = {}
+    scores, rows = {}, {}
     for f, pred in sorted(frames.items()):
         gt = source.ground_truth(f).to(pred.device)
         if gt.shape != pred.shape:
@@ -277,6 +273,39 @@ def score_frames(frames, source, lpips=None):
         scores[f] = dict(psnr=float(metrics.psnr(x, y, data_range=255.0)[0]), ms_ssim=float(metrics.ms_ssim(x, y, data_range=255)))
         if lpips is not None:
             scores[f]["lpips"] = float(lpips(x, y, normalize=False).reshape(-1)[0])
+        if fid is not None and not scores[f]["psnr"] > 1000:
+            r = fid.features(torch.cat([x, y])).cpu()
+            rows[f] = (r[0], r[1])
+    return scores, rows
+
+
+def fid_update_rows(fid, rows):
+    """Add {frame: (decoded [64], truth [64])} to `fid` in ascending frame order: decoded rows to the fake side, truth rows to the
+    real side.  The state depends on the rows and their order only, not on which rank computed them."""
+    order = sorted(rows)
+    if order:
+        fid.update_features(torch.stack([rows[f][0] for f in order]), real=False)
+        fid.update_features(torch.stack([rows[f][1] for f in order]), real=True)
+
+
+def _fid_value(fid):
+    real, fake = fid.state()
+    return fid.compute() if min(float(real[0]), float(fake[0])) >= 2 else float("nan")
+
+
+def score_frames(frames, source, lpips=None, fid=None):
+    """{frame: uint8 [H,W,3] tensor} -> {frame: {"psnr": dB, "ms_ssim": value}} against `source.ground_truth(frame)`, with L = 255
+    (test_utils.py:23-24, :55; validation.py:147-150 on x / 255 gives the same values), on the device of the frames.
+    `lpips` (a `metrics.LPIPS` with weights loaded) adds "lpips": as test_utils.py:58 computes it, on frame / 255 with
+    normalize=False.  That is the reference's quirk, kept for comparable numbers: it feeds [0,1] images where the net expects
+    [-1,1] (the library's `normalize=True` would map them).
+    `fid` (a `metrics.FrechetInceptionDistance` with weights loaded) is updated with every frame (fake side) and its ground truth
+    (real side) in ascending frame order, as test_utils.py:62-63 does; it is not reset here, `fid.compute()` gives the value.  FID is
+    a statistic of the set, so the per-frame dicts do not change.  test_utils.py:51-52 `continue`s past identical frames before the
+    update: a frame whose PSNR exceeds 1000 dB is left out."""
+    scores, rows = _score_frames(frames, source, lpips, fid)
+    if fid is not None:
+        fid_update_rows(fid, rows)
     return scores
 
 
@@ -305,16 +334,48 @@ def gather_scores(scores, units, rank, world, dst=0, lpips=False):
     return dict(sorted(out.items()))
 
 
+def gather_fid_rows(rows, units, rank, world, dst=0):
+    """Every rank's {frame: (decoded [64], truth [64])} -> the union on `dst` (None elsewhere): ONE `dist.gather` of a float64
+    [inter frames, 1 + 128] tensor (flag, decoded row, truth row) per rank, shaped like `gather_scores`.  The rows travel, not the
+    sums: `dst` accumulates them in frame order, so the value has the bits of a single-rank run (fp32 -> fp64 -> fp32 is exact)."""
+    import torch.distributed as dist
+    frames = sorted({u.frame for u in units})
+    row = {f: i for i, f in enumerate(frames)}
+    dev = "cpu" if dist.get_backend() == "gloo" else torch.device("cuda", torch.cuda.current_device())
+    send = torch.zeros((len(frames), 129), dtype=torch.float64)
+    for f, (d, t) in rows.items():
+        send[row[f], 0] = 1.0
+        send[row[f], 1:65] = d.double()
+        send[row[f], 65:] = t.double()
+    send = send.to(dev)
+    bufs = [torch.empty_like(send) for _ in range(world)] if rank == dst else None
+    dist.gather(send, bufs, dst=dst)
+    if rank != dst:
+        return None
+    out = {}
+    for b in bufs:
+        b = b.cpu()
+        for i, f in enumerate(frames):
+            if b[i, 0]:
+                out[f] = (b[i, 1:65].float(), b[i, 65:].float())
+    return dict(sorted(out.items()))
+
+
 @torch.no_grad()
 def decode_clip(pipe, source, num_frames, gop_size, height, width, prompt_embeds, negative_prompt_embeds=None, *, tile=512,
                 overlap=64, batch=16, seed=0, rank=None, world=None, shard_mode="unit", gather=True, score=False, lpips=None,
-                **pipe_kwargs):
+                fid=None, **pipe_kwargs):
     """Whole pipeline for one clip on this rank.  Returns dict(units=all units, mine=this rank's, images=this rank's fp32 unit
     images, frames={frame: uint8 HxWx3} on the gathering rank (or for locally complete frames when gather=False)).
     score=True adds scores={frame: {"psnr": dB, "ms_ssim": value}}: each blended frame against `source.ground_truth(frame)` on
     the device, from the uint8 frames `frames` holds (score_frames); `lpips=` (a `metrics.LPIPS` with weights loaded) adds "lpips"
     to each frame's dict and a fourth column to the gather.  With gather=False and world > 1 every rank scores its
-    complete frames and one gather of the scores (not the pixels) gives rank 0 all of them; other ranks keep their own."""
+    complete frames and one gather of the scores (not the pixels) gives rank 0 all of them; other ranks keep their own.
+    `fid=` (a `metrics.FrechetInceptionDistance` with weights loaded) leaves the per-frame dicts as they are and adds
+    fid_features={frame: (decoded [64], truth [64])} (fp32 rows on the host; frames whose PSNR exceeds 1000 dB are left out, as
+    test_utils.py:51-52 skips them) and, on the rank that holds the scores, fid = the value (NaN with fewer than two frames): the
+    model is reset, then updated in ascending frame order.  With gather=False and world > 1 one more gather brings the feature rows
+    (not the sums) to rank 0, which accumulates them in frame order: the value has the bits of a single-rank run."""
     if rank is None or world is None:
         ini = torch.distributed.is_available() and torch.distributed.is_initialized()
         rank = torch.distributed.get_rank() if ini else 0
@@ -328,12 +389,17 @@ def decode_clip(pipe, source, num_frames, gop_size, height, width, prompt_embeds
     u8 = units_to_u8(images)
     frames = None
     scores = None
+    rows = {}
+    have_fid = score and fid is not None
+    if have_fid:
+        fid.reset()
+    holds_scores = rank == 0 or not (gather and world > 1)      # whether this rank's result carries the clip's (or its own) scores
 
     def blend(unit_u8, us):
-        nonlocal scores
+        nonlocal scores, rows
         dev = _blend_frame_tensors(unit_u8, us, height, width, overlap)
         if score:
-            scores = score_frames(dev, source, lpips)
+            scores, rows = _score_frames(dev, source, lpips, fid)
         return {f: t.cpu().numpy() for f, t in dev.items()}
 
     if gather and world > 1:
@@ -352,9 +418,19 @@ def decode_clip(pipe, source, num_frames, gop_size, height, width, prompt_embeds
             frames = blend(u8[complete], [mine[k] for k in complete])
         if score and world > 1 and torch.distributed.is_available() and torch.distributed.is_initialized():
             merged = gather_scores(scores or {}, units, rank, world, dst=0, lpips=lpips is not None)
+            if have_fid:
+                allrows = gather_fid_rows(rows, units, rank, world, dst=0)
+                holds_scores = rank == 0
             if rank == 0:
                 scores = merged
+                if have_fid:
+                    rows = allrows
     out = dict(units=units, mine=mine, images=images, frames=frames)
     if score:
         out["scores"] = scores if scores is not None else {}
+    if have_fid:
+        out["fid_features"] = rows
+        if holds_scores:
+            fid_update_rows(fid, rows)
+            out["fid"] = _fid_value(fid)
     return out

@@ -89,6 +89,12 @@ SIGNATURES = {
     "dc_lpips_features_ws_bytes": [i32, i32, i32],
     "dc_lpips_alex_features": [vp, i32, POINTER(i64), i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
     "dc_lpips_conv": [i32, vp, i32, POINTER(i64), i32, i32, i32, i32, vp, vp, vp],
+    "dc_fid_weight_floats": [],
+    "dc_fid_ws_bytes": [i32, i32, i32],
+    "dc_fid_features": [vp, i32, POINTER(i64), i32, i32, i32, vp, vp, vp, vp],
+    "dc_fid_maps": [vp, i32, POINTER(i64), i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
+    "dc_fid_conv": [i32, vp, i32, vp, vp, vp],
+    "dc_fid_accumulate": [vp, i32, vp, vp],
 }
 
 _lib = None

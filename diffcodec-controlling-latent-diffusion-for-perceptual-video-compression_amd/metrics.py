@@ -1,4 +1,5 @@
-"""Frame quality metrics on the device: PSNR, SSIM and MS-SSIM (csrc/metrics.hip) and LPIPS (csrc/lpips.hip, `class LPIPS` below).
+"""Frame quality metrics on the device: PSNR, SSIM and MS-SSIM (csrc/metrics.hip), LPIPS (csrc/lpips.hip, `class LPIPS` below) and
+FID (csrc/fid.hip, `class FrechetInceptionDistance` below).
 
 The reference harness scores every decoded frame against its ground truth: validation.py:120-155 (`ms_ssim(pred, gt,
 data_range=1.0)`, `10*log10(1/mse)`) and test_utils.py:23-55 (`psnr`, `ms_ssim(..., data_range=255)`), both through
@@ -187,11 +188,12 @@ def psnr(X, Y, data_range=255.0):
     return out.cpu() if host else out
 
 
-def summarize(scores):
+def summarize(scores, fid=None):
     """Means over frames of {frame: {"psnr": dB, "ms_ssim": value[, "lpips": value]}} (decode_clip(score=True)), following
     test_utils.py:49-55: a frame whose PSNR exceeds 1000 dB (identical images) is left out of the means.  Returns dict(psnr,
     ms_ssim, frames = the number averaged, identical = the number left out) and, when the scores carry it, lpips; the means are
-    NaN when no frame is left."""
+    NaN when no frame is left.  `fid` (decode_clip's out["fid"], a statistic of the clip and not a mean over frames) is passed
+    through as "fid" when given."""
     kept = [s for _, s in sorted(scores.items()) if not s["psnr"] > 1000]
     m = len(kept)
     out = dict(psnr=sum(s["psnr"] for s in kept) / m if m else float("nan"),
@@ -199,6 +201,8 @@ def summarize(scores):
                frames=m, identical=len(scores) - m)
     if any("lpips" in s for s in scores.values()):
         out["lpips"] = sum(s["lpips"] for s in kept) / m if m else float("nan")
+    if fid is not None:
+        out["fid"] = float(fid)
     return out
 
 
@@ -376,3 +380,239 @@ class LPIPS:
                 lib.call("dc_lpips_alex_features", xs.data_ptr(), int(xs.dtype == torch.uint8), (ctypes.c_longlong * 4)(*sx), m, h, w,
                          int(bool(normalize)), wts.data_ptr(), scratch.data_ptr(), *[f[i:i + step].data_ptr() for f in feats], stream)
         return [f.cpu() for f in feats] if host else feats
+
+
+# ------------------------------------------------------------------------------------------------------------- FID
+FID_BLOCKS = ("Conv2d_1a_3x3", "Conv2d_2a_3x3", "Conv2d_2b_3x3")
+FID_CIN = (3, 32, 32)
+FID_COUT = (32, 32, 64)
+FID_FEATURES = 64
+FID_STATE = 1 + FID_FEATURES + FID_FEATURES * FID_FEATURES       # n, sum f, sum f f^T
+FID_SIZE = 299
+FID_MAP_SHAPES = ((3, 299, 299), (32, 149, 149), (32, 147, 147), (64, 147, 147), (64, 73, 73))
+FID_BN_EPS = 1e-3
+FID_CHUNK_BYTES = 1 << 30                            # scratch bound of one launch sequence (12.2 MB of maps per image)
+
+
+def _fid_tensor(sd, key, shape):
+    if key not in sd:
+        raise ValueError(f"FID state dict: missing key {key!r}")
+    t = sd[key]
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"FID state dict: {key!r} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+    return t.detach().to("cpu", torch.float32)
+
+
+def pack_fid_weights(state_dict):
+    """One fp32 CPU vector in the layout dc_fid_features reads: per block the K-major matrix [(ci, ky, kx)][Cout] (block 1 followed
+    by one zero row, 27 -> 28), then s = bn.weight / sqrt(running_var + 1e-3) and t = bn.bias - running_mean * s, both formed in
+    fp64 and rounded to fp32."""
+    parts = []
+    for l, (name, ci, co) in enumerate(zip(FID_BLOCKS, FID_CIN, FID_COUT)):
+        w = _fid_tensor(state_dict, f"{name}.conv.weight", (co, ci, 3, 3))
+        g, b, m, v = (_fid_tensor(state_dict, f"{name}.bn.{k}", (co,)).double() for k in ("weight", "bias", "running_mean", "running_var"))
+        wk = w.reshape(co, ci * 9).t().contiguous()
+        if l == 0:
+            wk = torch.cat([wk, torch.zeros(1, co)], 0)
+        s = g / torch.sqrt(v + FID_BN_EPS)
+        parts += [wk.reshape(-1), s.float(), (b - m * s).float()]
+    return torch.cat(parts).contiguous()
+
+
+def frechet_distance(state_real, state_fake):
+    """The value from two fp64 state vectors [1 + 64 + 4096] (n, sum f, sum f f^T), on the host in fp64:
+    mu = sum / n, cov = (sumsq - n mu mu^T) / (n - 1), |mu_r - mu_f|^2 + tr cov_r + tr cov_f - 2 sum sqrt(eigvals(cov_r cov_f)).real.
+
+    The last term is evaluated as the sum of the singular values of cov_r^(1/2) cov_f^(1/2): with cov = U diag(a) U^T (eigh) the
+    eigenvalues of cov_r cov_f are the squared singular values of diag(sqrt a_r) U_r^T U_f diag(sqrt a_f).  The value is the same;
+    the error is not.  A general eigen-solver returns the zero eigenvalues of a rank-deficient product (fewer than 65 images on a
+    side) as +-1e-17 |cov|^2, whose square roots add 1e-8 each, so a set against itself came out at -2.5e-8; singular values carry
+    an absolute error of 1e-16 |cov| and the same case gives 1e-14."""
+    stats = []
+    for st in (state_real, state_fake):
+        st = st.detach().to("cpu", torch.float64)
+        n = float(st[0])
+        if n < 2:
+            raise RuntimeError("More than one sample is required for both the real and fake distributed to compute FID")
+        mu = st[1:1 + FID_FEATURES] / n
+        sq = st[1 + FID_FEATURES:].view(FID_FEATURES, FID_FEATURES)
+        stats.append((mu, (sq - n * torch.outer(mu, mu)) / (n - 1)))
+    (mu_r, cov_r), (mu_f, cov_f) = stats
+    d = mu_r - mu_f
+    (a_r, u_r), (a_f, u_f) = torch.linalg.eigh(cov_r), torch.linalg.eigh(cov_f)
+    c = torch.linalg.svdvals((u_r * a_r.clamp_min(0).sqrt()).t() @ (u_f * a_f.clamp_min(0).sqrt())).sum()
+    return float((d * d).sum() + cov_r.trace() + cov_f.trace() - 2 * c)
+
+
+class FrechetInceptionDistance:
+    """`torchmetrics.image.fid.FrechetInceptionDistance(feature=64)` on the device in exact fp32 (csrc/fid.hip): `update(imgs, real)`
+    accumulates, `compute()` returns the value as a Python float.
+
+        input     3-channel images of any H, W >= 1; with normalize=True a float image in [0,1], taken as (x * 255) truncated to uint8
+        resize    to 299 x 299, TF1-legacy bilinear (align_corners=False without the half-pixel offset): for output index o on an
+                  axis of input size I, p = o * (I / 299), i0 = floor(p), i1 = min(i0 + 1, I - 1), l = p - i0;
+                  top = tl + (tr - tl) lx, bot = bl + (br - bl) lx, out = top + (bot - top) ly; then (x - 128) / 128
+        stem      Conv2d_1a_3x3 (3 -> 32, stride 2), Conv2d_2a_3x3 (32 -> 32), Conv2d_2b_3x3 (32 -> 64, pad 1): conv without bias,
+                  eval BatchNorm with eps 1e-3 (applied as one fma per channel), ReLU; maps 149 / 147 / 147
+        pooling   max-pool 3 x 3 stride 2 (73 x 73), then the spatial mean: 64 features per image
+        state     per side (real, fake) n, sum f and sum f f^T in fp64, added image by image in batch order
+        value     mu = sum / n, cov = (sumsq - n mu mu^T) / (n - 1),
+                  |mu_r - mu_f|^2 + tr cov_r + tr cov_f - 2 sum sqrt(eigvals(cov_r cov_f)).real, the last term evaluated as
+                  the singular values of cov_r^(1/2) cov_f^(1/2) (`frechet_distance`): a set against itself gives 0 to 1e-14
+
+    No weights ship with the package and none are downloaded: load the `pt_inception-2015-12-05` FID network's checkpoint with
+    `load_state_dict` / `from_state_dict`; the keys `Conv2d_{1a,2a,2b}_3x3.conv.weight` and
+    `Conv2d_{1a,2a,2b}_3x3.bn.{weight,bias,running_mean,running_var}` are read by name, every other key is ignored.  These rules and
+    key names are recalled from the published packages and are unpinned (neither torchmetrics nor torch-fidelity is a dependency);
+    tests/fid_ref.py restates the rules above in fp64 and the device results are checked against that with seeded weights.
+
+    Deliberate differences from the library: uint8 images are NHWC frames ([N,H,W,3], the package's convention; the library takes
+    uint8 NCHW); float images are NCHW with any strides (read in place) and are taken only with normalize=True; only feature=64.
+
+    Placement: device tensors are read on the current stream and `update` does not synchronise with the host (graph-capturable once
+    the model is on the device: `model.to(device)` or a first call); CPU tensors are copied to the current GPU.  Large batches run
+    in chunks that bound the scratch; an image's features do not depend on its position or on the batch size, and
+    `update(a); update(b)` leaves the bits of `update(cat(a, b))`.  `compute()` copies the 2 x 4161 doubles of the state to the host
+    and runs the 64 x 64 eigenvalue step there in fp64: the one host synchronisation, at the end of a clip."""
+
+    def __init__(self, feature=64, normalize=False):
+        if feature != 64:
+            raise NotImplementedError(f"FrechetInceptionDistance feature {feature!r}: only 64 is implemented")
+        self.normalize = bool(normalize)
+        self.packed = None
+        self._on_device = {}
+        self._state = {True: torch.zeros(FID_STATE, dtype=torch.float64), False: torch.zeros(FID_STATE, dtype=torch.float64)}
+
+    @classmethod
+    def from_state_dict(cls, state_dict, **kwargs):
+        m = cls(**kwargs)
+        m.load_state_dict(state_dict)
+        return m
+
+    def load_state_dict(self, state_dict):
+        packed = pack_fid_weights(state_dict)
+        want = lib.load().dc_fid_weight_floats()
+        if packed.numel() != want:
+            raise RuntimeError(f"packed FID weights hold {packed.numel()} floats, the library expects {want}")
+        self.packed = packed
+        self._on_device = {}
+        return self
+
+    def to(self, device):
+        device = self._device(torch.device(device))
+        self._weights(device)
+        self._state = {k: v.to(device) for k, v in self._state.items()}
+        return self
+
+    @staticmethod
+    def _device(device):
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        return device
+
+    def _weights(self, device):
+        if self.packed is None:
+            raise RuntimeError("FrechetInceptionDistance has no weights: call load_state_dict / from_state_dict (nothing is downloaded)")
+        device = self._device(device)
+        w = self._on_device.get(device)
+        if w is None:
+            w = self._on_device[device] = self.packed.to(device)
+        return w
+
+    def _images(self, imgs):
+        """(operand on the GPU, whether the caller passed a host tensor, (n, h, w))"""
+        if imgs.dim() != 4:
+            raise ValueError(f"FID takes 4-d image batches, got {tuple(imgs.shape)}")
+        if imgs.dtype == torch.uint8:
+            if self.normalize:
+                raise ValueError("normalize=True takes float NCHW images in [0,1], got uint8")
+        elif not imgs.dtype.is_floating_point:
+            raise ValueError(f"FID images should be uint8 (NHWC) or floating point (NCHW, normalize=True), got {imgs.dtype}")
+        elif not self.normalize:
+            raise ValueError("float images are taken only with normalize=True (values in [0,1]); pass uint8 NHWC frames otherwise")
+        (n, c, h, w), _ = _nchw(imgs)
+        if c != 3:
+            raise ValueError(f"FID takes 3-channel images, got {c} channels")
+        if h < 1 or w < 1:
+            raise ValueError(f"FID needs H, W >= 1, got {h}x{w}")
+        X, _, host = _to_device(imgs, imgs)
+        if X.dtype != torch.uint8 and X.dtype != torch.float32:
+            X = X.float()
+        return X, host, (n, h, w)
+
+    def _chunks(self, n, h, w):
+        return max(1, min(n, FID_CHUNK_BYTES // max(1, lib.load().dc_fid_ws_bytes(1, h, w))))
+
+    def features(self, imgs):
+        """fp32 [N,64]: the pooled features of `imgs` (uint8 NHWC, or float NCHW with normalize=True)."""
+        X, host, (n, h, w) = self._images(imgs)
+        wts = self._weights(X.device)
+        L = lib.load()
+        out = torch.empty((n, FID_FEATURES), dtype=torch.float32, device=X.device)
+        step = self._chunks(n, h, w)
+        with torch.cuda.device(X.device):
+            stream = torch.cuda.current_stream().cuda_stream
+            for i in range(0, n, step):
+                xs = X[i:i + step]
+                m = xs.shape[0]
+                scratch = torch.empty(L.dc_fid_ws_bytes(m, h, w), dtype=torch.uint8, device=X.device)
+                lib.call("dc_fid_features", xs.data_ptr(), int(xs.dtype == torch.uint8), (ctypes.c_longlong * 4)(*_nchw(xs)[1]), m, h, w,
+                         wts.data_ptr(), scratch.data_ptr(), out[i:i + step].data_ptr(), stream)
+        return out.cpu() if host else out
+
+    def maps(self, imgs):
+        """[resized [N,3,299,299], relu1 [N,32,149,149], relu2 [N,32,147,147], relu3 [N,64,147,147], pooled [N,64,73,73]],
+        contiguous fp32 NCHW (the test seam; `features` keeps them in scratch)."""
+        X, host, (n, h, w) = self._images(imgs)
+        wts = self._weights(X.device)
+        outs = [torch.empty((n,) + s, dtype=torch.float32, device=X.device) for s in FID_MAP_SHAPES]
+        feat = torch.empty((n, FID_FEATURES), dtype=torch.float32, device=X.device)
+        step = self._chunks(n, h, w)
+        with torch.cuda.device(X.device):
+            stream = torch.cuda.current_stream().cuda_stream
+            for i in range(0, n, step):
+                xs = X[i:i + step]
+                lib.call("dc_fid_maps", xs.data_ptr(), int(xs.dtype == torch.uint8), (ctypes.c_longlong * 4)(*_nchw(xs)[1]), xs.shape[0],
+                         h, w, wts.data_ptr(), *[t[i:i + step].data_ptr() for t in outs], feat[i:i + step].data_ptr(), stream)
+        return [t.cpu() for t in outs] if host else outs
+
+    def update_features(self, f, real):
+        """Add feature rows [N,64] (computed by `features`, here or on another rank) to the real or the fake side, in row order."""
+        if f.dim() != 2 or f.shape[1] != FID_FEATURES:
+            raise ValueError(f"FID feature rows should be [N,{FID_FEATURES}], got {tuple(f.shape)}")
+        if f.shape[0] == 0:
+            return
+        if not f.is_cuda:
+            if not torch.cuda.is_available():
+                raise RuntimeError("diffcodec_amd.metrics computes on the GPU and none is available (there is no CPU path)")
+            f = f.to(torch.device("cuda", torch.cuda.current_device()))
+        f = f.float().contiguous()
+        real = bool(real)
+        if self._state[real].device != f.device:
+            self._state = {k: v.to(f.device) for k, v in self._state.items()}
+        with torch.cuda.device(f.device):
+            lib.call("dc_fid_accumulate", f.data_ptr(), f.shape[0], self._state[real].data_ptr(), torch.cuda.current_stream().cuda_stream)
+
+    def update(self, imgs, real):
+        """Add the images' features to the real (real=True) or the fake side."""
+        f = self.features(imgs)
+        self.update_features(f, real)
+
+    def state(self):
+        """(real, fake): copies of the two fp64 state vectors [1 + 64 + 4096] = n, sum f, sum f f^T (row-major)."""
+        return self._state[True].clone(), self._state[False].clone()
+
+    def merge_state(self, real, fake):
+        """Add two state vectors (another model's `state()`) to this one's sums."""
+        for side, st in ((True, real), (False, fake)):
+            if tuple(st.shape) != (FID_STATE,):
+                raise ValueError(f"FID state vectors hold {FID_STATE} doubles, got {tuple(st.shape)}")
+            self._state[side].add_(st.detach().to(self._state[side].device, torch.float64))
+
+    def reset(self):
+        for v in self._state.values():
+            v.zero_()
+
+    def compute(self):
+        """The Frechet distance of the two accumulated sets as a Python float (synchronises: the state is copied to the host)."""
+        return frechet_distance(self._state[True], self._state[False])

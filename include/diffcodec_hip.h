@@ -333,6 +333,31 @@ int dc_lpips_alex_features(const void* x, int x_u8, const long long* strides, in
 int dc_lpips_conv(int layer, const void* x, int x_u8, const long long* strides, int M, int H, int W, int normalize,
                   const float* weights, float* y, void* stream);
 
+/* FID features, feature = 64 (test_utils.py:14,39: torchmetrics FrechetInceptionDistance(feature=64)): the stem of the FID
+ * InceptionV3 up to its first max-pool, exact fp32 on the fp32 matrix instruction, sums in a fixed order (bitwise reproducible,
+ * independent of an image's position in the batch, no float atomics).  Operand as above with C = 3 and any H, W >= 1
+ * (strides[0..3]); a float image (x_u8 = 0) holds [0,1] values and is taken as (x * 255) truncated to uint8.  Resize to 299 x 299
+ * (TF1-legacy bilinear: p = o * (I / 299), i0 = floor(p), i1 = min(i0 + 1, I - 1)), (x - 128) / 128, then conv 3->32 3x3 / 2,
+ * conv 32->32 3x3, conv 32->64 3x3 pad 1, each followed by eval BatchNorm (one fma per channel) and ReLU, max-pool 3x3 / 2 and
+ * the spatial mean.  weights (device, fp32, 16-byte aligned, dc_fid_weight_floats() elements): per block the K-major matrix
+ * [K = (ci, ky, kx)][Cout] (block 1: K = 27 followed by one zero row), then s [Cout] = bn.weight / sqrt(running_var + 1e-3) and
+ * t [Cout] = bn.bias - running_mean * s.  ws: dc_fid_ws_bytes(N, H, W) bytes (-1 when N, H or W is out of range).
+ * out (device, fp32) [N][64]. */
+int dc_fid_weight_floats(void);
+long long dc_fid_ws_bytes(int N, int H, int W);
+int dc_fid_features(const void* x, int x_u8, const long long* strides, int N, int H, int W, const float* weights, void* ws,
+                    float* out, void* stream);
+/* The same with every intermediate written to the caller's contiguous fp32 NCHW tensors (needs no workspace): resized
+ * [N,3,299,299], the three post-ReLU maps m1 [N,32,149,149], m2 [N,32,147,147], m3 [N,64,147,147], pooled [N,64,73,73]. */
+int dc_fid_maps(const void* x, int x_u8, const long long* strides, int N, int H, int W, const float* weights, float* resized,
+                float* m1, float* m2, float* m3, float* pooled, float* out, void* stream);
+/* One conv + BatchNorm + ReLU block on its own (tools/bench_metrics.py times the blocks through it): layer 0..2, x the block's
+ * contiguous fp32 input [N,3,299,299] / [N,32,149,149] / [N,32,147,147], y its output map. */
+int dc_fid_conv(int layer, const float* x, int N, const float* weights, float* y, void* stream);
+/* state (device, fp64) [1 + 64 + 64 * 64] = n, sum f, sum f f^T (row-major) += the N rows of features [N][64], added image by image
+ * in batch order: two calls leave the bits of one call on the concatenation. */
+int dc_fid_accumulate(const float* features, int N, double* state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

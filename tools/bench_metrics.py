@@ -6,7 +6,11 @@ LPIPS leg (csrc/lpips.hip, seeded random weights): at 512x512 for 1 and 16 pairs
 whole call (ms per call and per pair) and, per conv layer, the time of the layer's kernel alone on the call's 2N images
 (dc_lpips_conv, back-to-back launches between two events) with its TFLOP/s.
 
-    python tools/bench_metrics.py [--batch 16] [--iters 20] [--no-lpips]"""
+FID leg (csrc/fid.hip, seeded random weights): 16 images and 1 image of 512x512, one JSON line with the whole `update` call (ms per
+call and per image), `features` alone, the accumulate launch alone and, per conv block, the time of the block's kernel alone
+(dc_fid_conv, back-to-back launches between two events) with its TFLOP/s; resize + pool + host is the remainder of `features`.
+
+    python tools/bench_metrics.py [--batch 16] [--iters 20] [--no-lpips] [--no-fid]"""
 import argparse
 import json
 import os
@@ -70,11 +74,59 @@ def lpips_leg(iters):
                               conv_ms=round(conv_ms, 4), pool_tail_host_ms=round(ms - conv_ms, 4), **layers)), flush=True)
 
 
+def fid_leg(iters):
+    from diffcodec_amd import lib, metrics as M
+    g = torch.Generator().manual_seed(0)
+    sd = {}
+    for name, ci, co in zip(M.FID_BLOCKS, M.FID_CIN, M.FID_COUT):
+        sd[f"{name}.conv.weight"] = torch.randn(co, ci, 3, 3, generator=g) * (2.0 / (9 * ci)) ** 0.5
+        sd[f"{name}.bn.weight"] = 0.5 + torch.rand(co, generator=g)
+        sd[f"{name}.bn.bias"] = 0.3 * torch.randn(co, generator=g)
+        sd[f"{name}.bn.running_mean"] = 0.2 * torch.randn(co, generator=g)
+        sd[f"{name}.bn.running_var"] = 0.5 + torch.rand(co, generator=g)
+    model = M.FrechetInceptionDistance.from_state_dict(sd).to("cuda")
+    wts = model._weights(torch.device("cuda"))
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def timed(fn):
+        for _ in range(3):
+            fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / iters
+
+    flop = [2.0 * 32 * 149 * 149 * 27, 2.0 * 32 * 147 * 147 * 288, 2.0 * 64 * 147 * 147 * 288]
+    gd = torch.Generator(device="cuda").manual_seed(0)
+    for n in (16, 1):
+        x = torch.randint(0, 256, (n, 512, 512, 3), dtype=torch.uint8, device="cuda", generator=gd)
+        maps = model.maps(x)
+        layers = {}
+        for l in range(3):
+            out = torch.empty_like(maps[l + 1])
+            t = timed(lambda: lib.call("dc_fid_conv", l, maps[l].data_ptr(), n, wts.data_ptr(), out.data_ptr(), stream))
+            assert torch.equal(out, maps[l + 1]), f"conv{l + 1} alone differs from the fused sequence"
+            layers[f"conv{l + 1}"] = dict(us=round(t * 1e3, 1), tflops=round(n * flop[l] / (t * 1e-3) / 1e12, 1))
+        t_feat = timed(lambda: model.features(x))
+        f = model.features(x)
+        t_acc = timed(lambda: model.update_features(f, real=True))
+        t_upd = timed(lambda: model.update(x, real=True))
+        model.reset()
+        conv_ms = sum(v["us"] for v in layers.values()) / 1e3
+        print(json.dumps(dict(fid="512x512", images=n, update_ms_per_call=round(t_upd, 4), update_ms_per_image=round(t_upd / n, 4),
+                              features_ms=round(t_feat, 4), conv_ms=round(conv_ms, 4), resize_pool_host_ms=round(t_feat - conv_ms, 4),
+                              accumulate_us=round(t_acc * 1e3, 1), **layers)), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--no-lpips", action="store_true")
+    ap.add_argument("--no-fid", action="store_true")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_metrics needs the GPU"
     from diffcodec_amd import metrics as M
@@ -100,6 +152,8 @@ def main():
         print(json.dumps(dict(shape=f"{h}x{w}", batch=a.batch, **res)), flush=True)
     if not a.no_lpips:
         lpips_leg(a.iters)
+    if not a.no_fid:
+        fid_leg(a.iters)
 
 
 if __name__ == "__main__":
