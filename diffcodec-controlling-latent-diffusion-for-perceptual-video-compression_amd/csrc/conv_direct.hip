@@ -4,8 +4,7 @@
 //   * NHWC bf16 convs with <= 16 input channels (UNet/ControlNet conv_in 4->320, VAE conv_in, post_quant_conv)
 //   * NHWC bf16 convs with <= 8 output channels (UNet conv_out 320->4 with fused GroupNorm+SiLU, VAE conv_out,
 //     quant_conv): one wave per output pixel, lanes split the (tap, channel-vector) reduction.
-#include "dc_common.h"
-#include "../../include/diffcodec_hip.h"
+#include "dc_conv_f32_route.h"
 #include <cstdlib>
 
 namespace {
@@ -332,31 +331,39 @@ __global__ __launch_bounds__(256) void conv_small_cout_kernel(const bf16_t* __re
 
 }  // namespace
 
-// conv_f32_mfma.hip
-int dc_conv_f32_mfma_wanted(int Cin, int H, int W, int Cout, int stride);
-int dc_conv_f32_mfma_launch(const float* x, long long xbs, const float* w, const float* bias, float* y, int N, int Cin, int H, int W,
-                            int Cout, int stride, int silu, hipStream_t st);
+extern "C" int dc_conv3x3_f32_route(int Cin, int H, int W, int Cout, int stride, int* info)
+{
+    if (!info) return DC_ERR_INVALID;
+    for (int i = 0; i < DC_F32CONV_ROUTE_INFO_INTS; ++i) info[i] = 0;
+    dc_f32_route r;
+    const int rc = dc_conv_f32_route_of(Cin, H, W, Cout, stride, r);
+    if (rc != DC_OK) return rc;
+    info[0] = r.form, info[1] = r.stride, info[2] = r.co_t, info[3] = r.pt, info[4] = r.cols_t, info[5] = r.rows_t;
+    return DC_OK;
+}
 
 extern "C" int dc_conv3x3_nchw_f32(const float* x, long long x_batch_stride, const float* w, const float* bias, float* y,
                                    int N, int Cin, int H, int W, int Cout, int stride, int silu, void* stream)
 {
-    if (!x || !w || !y || N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || (stride != 1 && stride != 2 && stride != 4)) return DC_ERR_INVALID;
+    if (!x || !w || !y || N <= 0) return DC_ERR_INVALID;
+    dc_f32_route r;
+    const int rc = dc_conv_f32_route_of(Cin, H, W, Cout, stride, r);
+    if (rc != DC_OK) return rc;
     const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
     hipStream_t st = (hipStream_t)stream;
-    // GEMM-shaped layers (>= 16 input channels, output channels in whole 32-wide tiles): exact-fp32 MFMA form, conv_f32_mfma.hip
-    if (dc_conv_f32_mfma_wanted(Cin, H, W, Cout, stride)) return dc_conv_f32_mfma_launch(x, x_batch_stride, w, bias, y, N, Cin, H, W, Cout, stride, silu, st);
-    // the register-blocked form (16 x 16 pixels x 64 output channels per workgroup) wins where there are >= 64 output channels to
-    // share an input patch and the map is at least 64 wide (or 32 wide with >= 160 channels); measured per shape, tools/bench_f32conv.py
-    if (stride != 4 && Cout >= 64 && (Wo >= 64 || (Wo >= 32 && Cout >= 160))) {
-        const dim3 bgrid(dc_cdiv(Wo, 16) * dc_cdiv(Ho, 16), dc_cdiv(Cout, 64), N);
-        if (stride == 1) hipLaunchKernelGGL((conv3x3_nchw_f32_blk_kernel<1, 16, 4, 4, 8>), bgrid, dim3(256), 0, st, x, x_batch_stride, w, bias, y, Cin, H, W, Cout, Ho, Wo, silu);
-        else hipLaunchKernelGGL((conv3x3_nchw_f32_blk_kernel<2, 16, 4, 4, 8>), bgrid, dim3(256), 0, st, x, x_batch_stride, w, bias, y, Cin, H, W, Cout, Ho, Wo, silu);
-        return dc_launch_status();
+    if (r.form == DC_F32CONV_MFMA) return dc_conv_f32_mfma_launch(x, x_batch_stride, w, bias, y, N, Cin, H, W, Cout, r, silu, st);
+    // VALU forms: 16 x 16 output pixels x r.co_t output channels per workgroup (measured per shape, tools/bench_f32conv.py)
+    const dim3 grid(dc_cdiv(Wo, r.cols_t) * dc_cdiv(Ho, r.rows_t), dc_cdiv(Cout, r.co_t), N);
+#define DC_F32_GO(K) hipLaunchKernelGGL((K), grid, dim3(256), 0, st, x, x_batch_stride, w, bias, y, Cin, H, W, Cout, Ho, Wo, silu)
+    if (r.form == DC_F32CONV_BLK) {
+        if (r.stride == 1) DC_F32_GO((conv3x3_nchw_f32_blk_kernel<1, 16, 4, 4, 8>));
+        else DC_F32_GO((conv3x3_nchw_f32_blk_kernel<2, 16, 4, 4, 8>));
+    } else {
+        if (r.stride == 1) DC_F32_GO((conv3x3_nchw_f32_kernel<1, 8>));
+        else if (r.stride == 2) DC_F32_GO((conv3x3_nchw_f32_kernel<2, 8>));
+        else DC_F32_GO((conv3x3_nchw_f32_kernel<4, 2>));
     }
-    const dim3 grid(dc_cdiv(Wo, 16) * dc_cdiv(Ho, 16), dc_cdiv(Cout, CO_T), N);
-    if (stride == 1) hipLaunchKernelGGL((conv3x3_nchw_f32_kernel<1, 8>), grid, dim3(256), 0, st, x, x_batch_stride, w, bias, y, Cin, H, W, Cout, Ho, Wo, silu);
-    else if (stride == 2) hipLaunchKernelGGL((conv3x3_nchw_f32_kernel<2, 8>), grid, dim3(256), 0, st, x, x_batch_stride, w, bias, y, Cin, H, W, Cout, Ho, Wo, silu);
-    else hipLaunchKernelGGL((conv3x3_nchw_f32_kernel<4, 2>), grid, dim3(256), 0, st, x, x_batch_stride, w, bias, y, Cin, H, W, Cout, Ho, Wo, silu);
+#undef DC_F32_GO
     return dc_launch_status();
 }
 

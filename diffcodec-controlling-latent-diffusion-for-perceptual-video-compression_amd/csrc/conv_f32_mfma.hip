@@ -15,13 +15,12 @@
 //   weight slice, B = one ds_read_b32 of the patch at the lane's pixel shifted by the tap — consecutive lanes, consecutive words.
 //   C/D layout (dtype-independent): lane & 31 = pixel, 16 registers = channels (r & 3) + 8 (r >> 2) + 4 (lane >> 5): every store
 //   instruction writes 32 consecutive pixels of one channel row.
-#include "dc_common.h"
-#include "../../include/diffcodec_hip.h"
+#include "dc_conv_f32_route.h"
 
 namespace {
 
-constexpr int FM_CK = 8;                       // input channels per LDS chunk
-constexpr int FM_MAXE = 26;                    // patch floats per thread per chunk (largest patch: stride 2, 128 x 1 tile: 8*3*257)
+constexpr int FM_CK = DC_FM_CK;                // input channels per LDS chunk
+constexpr int FM_MAXE = DC_FM_MAXE;            // patch floats per thread per chunk (the route admits no larger patch)
 
 template <int STRIDE, int CO_T, int PT>
 __global__ __launch_bounds__(256, 2) void conv3x3_f32_mfma_kernel(const float* __restrict__ x, long long x_batch_stride,
@@ -149,11 +148,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f32_mfma_kernel(const float* _
 
 template <int STRIDE, int CO_T, int PT>
 int launch_fm(const float* x, long long xbs, const float* w, const float* bias, float* y, int N, int Cin, int H, int W, int Cout,
-              int Ho, int Wo, int silu, hipStream_t st)
+              int cols_t, int rows_t, int silu, hipStream_t st)
 {
-    const int cols_t = Wo < PT ? Wo : PT, rows_t = PT / cols_t;
+    const int Ho = (H + 2 - 3) / STRIDE + 1, Wo = (W + 2 - 3) / STRIDE + 1;
     const int PH = (rows_t - 1) * STRIDE + 3, PW = (cols_t - 1) * STRIDE + 3;
-    if (FM_CK * PH * PW > FM_MAXE * 256) return DC_ERR_INVALID;
     const size_t lds = (size_t)(FM_CK * 9 * CO_T + FM_CK * PH * PW) * 4;
     auto kern = conv3x3_f32_mfma_kernel<STRIDE, CO_T, PT>;
     static std::atomic<unsigned long long> attr_done{0};
@@ -165,35 +163,18 @@ int launch_fm(const float* x, long long xbs, const float* w, const float* bias, 
 
 }  // namespace
 
-// The MFMA form takes a layer when the GEMM dimensions are whole tiles: Cin a multiple of the 8-channel chunk (>= 16), Cout a
-// multiple of 32, stride 1 | 2 with exact halving, and an output map that splits into 128-pixel (8x8 maps: 64-pixel) tiles.
-int dc_conv_f32_mfma_wanted(int Cin, int H, int W, int Cout, int stride)
-{
-    if ((stride != 1 && stride != 2) || Cin < 16 || Cin % FM_CK || Cout % 32) return 0;
-    if (stride == 2 && ((H | W) & 1)) return 0;
-    const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
-    const int pt = Ho * Wo >= 128 ? 128 : 64;
-    if (Ho * Wo < 64 || (pt == 64 && Cout % 64)) return 0;   // the 64-pixel tile exists for 64-channel tiles only
-    const int cols_t = Wo < pt ? Wo : pt;
-    if (pt % cols_t || Wo % cols_t || Ho % (pt / cols_t)) return 0;
-    const int rows_t = pt / cols_t;
-    if (FM_CK * ((rows_t - 1) * stride + 3) * ((cols_t - 1) * stride + 3) > FM_MAXE * 256) return 0;
-    return 1;
-}
-
+// The tile rule itself (which layers are GEMM-shaped, which tile they get) is dc_conv_f32_route_of, dc_conv_f32_route.h.
 int dc_conv_f32_mfma_launch(const float* x, long long xbs, const float* w, const float* bias, float* y, int N, int Cin, int H, int W,
-                            int Cout, int stride, int silu, hipStream_t st)
+                            int Cout, const dc_f32_route& r, int silu, hipStream_t st)
 {
-    const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
-    const bool small = Ho * Wo < 128, co64 = Cout % 64 == 0;
-#define FM_GO(S, C, P) return launch_fm<S, C, P>(x, xbs, w, bias, y, N, Cin, H, W, Cout, Ho, Wo, silu, st)
-    if (stride == 1) {
-        if (small) FM_GO(1, 64, 64);
-        if (co64) FM_GO(1, 64, 128);
-        FM_GO(1, 32, 128);
-    }
-    if (small) FM_GO(2, 64, 64);
-    if (co64) FM_GO(2, 64, 128);
+#define FM_GO(S, C, P) \
+    if (r.stride == S && r.co_t == C && r.pt == P) return launch_fm<S, C, P>(x, xbs, w, bias, y, N, Cin, H, W, Cout, r.cols_t, r.rows_t, silu, st)
+    FM_GO(1, 64, 64);
+    FM_GO(1, 64, 128);
+    FM_GO(1, 32, 128);
+    FM_GO(2, 64, 64);
+    FM_GO(2, 64, 128);
     FM_GO(2, 32, 128);
 #undef FM_GO
+    return DC_ERR_INVALID;
 }

@@ -36,6 +36,7 @@ SIGNATURES = {
     "dc_flow_resize_divide_f32": [vp, i64, vp, i32, i32, i32, i32, i32, f32, f32, vp],
     "dc_fuse_warped_f32": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
     "dc_conv3x3_nchw_f32": [vp, i64, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
+    "dc_conv3x3_f32_route": [i32, i32, i32, i32, i32, POINTER(i32)],
     "dc_nchw_f32_to_nhwc_bf16": [vp, vp, i32, i32, i32, i32, vp],
     "dc_nhwc_bf16_to_nchw_f32": [vp, vp, i32, i32, i32, i32, vp],
     "dc_nhwc_f32_to_nchw_f32": [vp, vp, i32, i32, i32, i32, vp],

@@ -2,6 +2,7 @@
 
 Activations are NHWC bf16 tensors of shape [N,H,W,C] (a [B,L,C] token sequence is the same memory with H=1, W=L).
 No arithmetic happens in torch on this path; every function below ends in exactly one or more `lib.call`s."""
+import collections
 import ctypes
 import math
 
@@ -371,6 +372,21 @@ def linear(x, pc, **kw):
     shp = x.shape
     y = conv(x.reshape(1, 1, -1, shp[-1]), pc, **kw)
     return y.reshape(*shp[:-1], y.shape[-1])
+
+
+F32CONV_FORMS = {1: "mfma", 2: "blk", 3: "direct"}
+F32ConvRoute = collections.namedtuple("F32ConvRoute", "form stride co_tile pixel_tile cols_t rows_t")
+
+
+def conv3x3_f32_route(cin, h, w, cout, stride):
+    """The kernel instance `conv3x3_nchw_f32` launches for Cin x H x W -> Cout at `stride`, without launching (host code only:
+    needs the library, not a GPU): form 'mfma' | 'blk' | 'direct', its STRIDE, its output channels and pixels per workgroup and
+    the pixel tile's columns x rows (dc_conv3x3_f32_route).  Raises HipLaunchError for a shape the launch would refuse."""
+    info = (ctypes.c_int * 6)()
+    rc = lib.load().dc_conv3x3_f32_route(int(cin), int(h), int(w), int(cout), int(stride), info)
+    if rc != 0:
+        raise lib.HipLaunchError(f"dc_conv3x3_f32_route returned {rc} (invalid argument)")
+    return F32ConvRoute(F32CONV_FORMS[info[0]], *info[1:])
 
 
 def conv3x3_nchw_f32(x, pc, stride=1, silu=False):

@@ -60,6 +60,21 @@ int dc_fuse_warped_f32(const float* warped_first, const float* warped_last, cons
  * control_utils.py:43-47.  x [N,Cin,H,W] (batch stride given, for channel-sliced views), w OIHW fp32. */
 int dc_conv3x3_nchw_f32(const float* x, long long x_batch_stride, const float* w, const float* bias, float* y,
                         int N, int Cin, int H, int W, int Cout, int stride, int silu, void* stream);
+/* The kernel instance dc_conv3x3_nchw_f32 launches for a shape, without launching anything (host code; the same routing function
+ * the launch switches on).  Returns 0, or DC_ERR_INVALID for a shape the launch would refuse (stride not in {1,2,4}, a dimension
+ * <= 0), and fills info[DC_F32CONV_ROUTE_INFO_INTS]:
+ *   info[0] form: one of DC_F32CONV_* — MFMA conv3x3_f32_mfma_kernel<STRIDE, CO_T, PT> (exact fp32 matrix instruction),
+ *           BLK conv3x3_nchw_f32_blk_kernel<STRIDE, 16, 4, 4, 8> (register-blocked VALU: four pixels x 16 channels per thread),
+ *           DIRECT conv3x3_nchw_f32_kernel<STRIDE, 8 | 2> (one pixel x 16 channels per thread; every stride-4 launch);
+ *   info[1] STRIDE;
+ *   info[2] output channels per workgroup: CO_T 64 | 32 (MFMA), 64 (BLK), 16 (DIRECT);
+ *   info[3] output pixels per workgroup: PT 128 | 64 (MFMA), 256 (the VALU forms' 16 x 16 tile);
+ *   info[4] columns and info[5] rows of that pixel tile (MFMA: min(Wo, PT) columns, whole tiles only; VALU: 16 x 16, ragged). */
+#define DC_F32CONV_ROUTE_INFO_INTS 6
+#define DC_F32CONV_MFMA 1
+#define DC_F32CONV_BLK 2
+#define DC_F32CONV_DIRECT 3
+int dc_conv3x3_f32_route(int Cin, int H, int W, int Cout, int stride, int* info);
 
 /* ------------------------------------------------------------------ layout / dtype */
 int dc_nchw_f32_to_nhwc_bf16(const float* src, void* dst, int N, int C, int H, int W, void* stream);

@@ -495,6 +495,73 @@ def freeu_lowfreq_ref(x, s, rows):
     return torch.cat(out_r), torch.cat(out_s)
 
 
+# ------------------------------------------------------------------------------------------ loop-state kernels (fp32)
+def _f32_chain(n, a):
+    """S-equivalent of an fp32 evaluation of n roundings whose running values stay below A = sum of the absolute terms: as in
+    conv3x3_nchw_f32_ref, independent roundings of at most 2^-24 A each stay below 2^-24 sqrt(n) A."""
+    return a * (2.0 ** -24 * math.sqrt(n) / U)
+
+
+def _nhwc_to_nchw(t):
+    return t.to(F64).permute(0, 3, 1, 2)
+
+
+def cfg_ddim_step_ref(eps, lat, coef_row, guidance, cfg, B):
+    """dc_cfg_ddim_step's new latents: eps NHWC fp32 [(2 if cfg else 1) * B, H, W, C] (CFG: unconditional half first), lat NCHW
+    fp32 [B, C, H, W] (the state BEFORE the launch), coef_row the four fp32 values (sqrt(1-a_t), sqrt(a_t), sqrt(a_prev),
+    sqrt(1-a_prev)) of the step's table row as stored, guidance as the launch receives it (fp32) -> (r, S) [B, C, H, W]:
+        e = eu + g (et - eu)  (cfg)  |  eps;      r = sap (x - s1mat e) / sat + s1map e.
+    The kernel is fp32 throughout.  Its roundings, counted from cfg_ddim_kernel: et - eu, g *, eu + (3, CFG only), s1mat * e,
+    x -, / sat, sap *, and the final multiply-add (5): n = 8 with CFG, 5 without (a contracted fma only removes roundings).  Every
+    intermediate is bounded by the sum of the absolute terms
+        A = |sap / sat| (|x| + |s1mat| Ae) + |s1map| Ae,      Ae = |eu| + |g| (|et| + |eu|)   (|eps| without CFG),
+    which also carries the cancellation between sap s1mat / sat and s1map at small steps."""
+    s1mat, sat, sap, s1map = (float(v) for v in torch.as_tensor(coef_row, dtype=torch.float32).reshape(4).to(F64).tolist())
+    g = float(torch.tensor(float(guidance), dtype=torch.float32).to(F64))
+    x = lat.to(F64)
+    e_all = _nhwc_to_nchw(eps)
+    if cfg:
+        eu, et = e_all[:B], e_all[B:2 * B]
+        e = eu + g * (et - eu)
+        ae = eu.abs() + abs(g) * (et.abs() + eu.abs())
+        n = 8
+    else:
+        e = e_all[:B]
+        ae = e.abs()
+        n = 5
+    r = sap * (x - s1mat * e) / sat + s1map * e
+    a = abs(sap / sat) * (x.abs() + abs(s1mat) * ae) + abs(s1map) * ae
+    return r, _f32_chain(n, a)
+
+
+VAE_LOGVAR_MIN, VAE_LOGVAR_MAX = -30.0, 20.0
+
+
+def vae_sample_latents_ref(moments, noise, scale):
+    """dc_vae_sample_latents (diffusers DiagonalGaussianDistribution.sample, times the scaling factor): moments NHWC fp32
+    [N, H, W, 2C] = (mean | log-variance), noise NCHW fp32 [N, C, H, W] -> (r, S) [N, C, H, W]:
+        r = (mean + exp(0.5 clamp(lv, -30, 20)) z) scale.
+    Roundings: 0.5 lv is exact; expf, * z, mean +, * scale: n = 4.  expf evaluates to a couple of ulps and amplifies the rounding
+    of its argument by |0.5 lv|, so the noise term t = exp(.) z enters with the weight 2 + |0.5 lv|:
+        A = (|mean| + |t| (2 + |0.5 lv|)) |scale|."""
+    c = noise.shape[1]
+    mean, lv = _nhwc_to_nchw(moments[..., :c]), _nhwc_to_nchw(moments[..., c:])
+    sc = float(torch.tensor(float(scale), dtype=torch.float32).to(F64))
+    half = 0.5 * lv.clamp(VAE_LOGVAR_MIN, VAE_LOGVAR_MAX)
+    t = torch.exp(half) * noise.to(F64)
+    r = (mean + t) * sc
+    a = (mean.abs() + t.abs() * (2 + half.abs())) * abs(sc)
+    return r, _f32_chain(4, a)
+
+
+def latents_to_model_input_ref(lat, mul, rep=1):
+    """dc_latents_to_model_input: lat NCHW fp32 [B, C, H, W] -> (r, S) [rep * B, H, W, C], the bf16 NHWC model input lat * mul
+    repeated `rep` times along the batch.  One fp32 product, then the output rounding (e_out): S = |r| 2^-24 / U."""
+    m = float(torch.tensor(float(mul), dtype=torch.float32).to(F64))
+    r = (lat.to(F64) * m).permute(0, 2, 3, 1).repeat(rep, 1, 1, 1)
+    return r, r.abs() * (2.0 ** -24 / U)
+
+
 def timestep_embedding_ref(t, n, dim):
     """[n, dim] fp32 = [cos(t f_k), sin(t f_k)], f_k = exp(-ln(10^4) k / half).  The kernel forms the argument in fp32: S covers
     4 ulps of the argument (|t f_k| 2^-22) plus the fp32 rounding of f_k itself."""

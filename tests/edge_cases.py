@@ -8,9 +8,10 @@ Plain module (imported by tests/test_edge_coverage.py on the CPU and tests/test_
   holds the pattern, compared as integers.
 * `conv_key` / `attention_key`: the kernel instance a launch runs, from the dispatcher's own queries (dc_conv_route and
   dc_conv_instance, dc_attention_route).
-* `CONV_CASES`, `ATTN_CASES`, `NORM_CASES`: the tables.  Every conv / attention case declares the instance it targets;
-  tests/test_edge_coverage.py proves that every instance the dispatcher can reach has a case and that every case routes where it
-  says."""
+* `f32_conv_key`: the same for the fp32 extractor conv (dc_conv3x3_f32_route).
+* `CONV_CASES`, `ATTN_CASES`, `NORM_CASES`, `F32_CONV_CASES`: the tables.  Every conv / attention case declares the instance it
+  targets; tests/test_edge_coverage.py proves that every instance the dispatcher can reach has a case and that every case routes
+  where it says."""
 import math
 from dataclasses import dataclass
 
@@ -557,3 +558,173 @@ SMALL_CASES = [
     SmallCase("small_cin", 2, 8, 12, 3, 16, stride=2, pad=1),   # Cin 3
 ] + [SmallCase("small_cout", n, 7, 9, 64, co, k=k, gn=gn, out_f32=f32)  # M = 63 or 189: a partial last 4-pixel workgroup
      for co in (3, 4, 8) for (n, k, gn, f32) in ((1, 3, False, False), (3, 3, True, False), (1, 1, False, True), (3, 3, True, True))]
+
+
+# ------------------------------------------------------------------------------------------ fp32 extractor conv instances
+@dataclass(frozen=True)
+class F32ConvCase:
+    """One dc_conv3x3_nchw_f32 launch (fp32 NCHW, 3x3, padding 1).  key = ("f32conv", form, STRIDE, output channels per workgroup,
+    output pixels per workgroup): the instance it targets (f32_conv_key)."""
+    key: tuple
+    n: int
+    cin: int
+    h: int
+    w: int
+    cout: int
+    stride: int
+    note: str = ""
+
+    @property
+    def ho(self):
+        return (self.h + 2 - 3) // self.stride + 1
+
+    @property
+    def wo(self):
+        return (self.w + 2 - 3) // self.stride + 1
+
+    @property
+    def m(self):
+        return self.n * self.ho * self.wo
+
+    @property
+    def last_row_read(self):
+        """the last output row's taps reach input row H - 1 (not so at stride 4 with H = 0 or 3 mod 4)"""
+        return (self.ho - 1) * self.stride + 1 >= self.h - 1
+
+    def label(self):
+        return f"{self.n}x{self.cin}x{self.h}x{self.w}->{self.cout} s{self.stride}"
+
+
+def f32_conv_route(cin, h, w, cout, stride):
+    from diffcodec_amd import ops
+    return ops.conv3x3_f32_route(cin, h, w, cout, stride)
+
+
+def f32_conv_key(cin, h, w, cout, stride):
+    """Instance key of one dc_conv3x3_nchw_f32 launch, from the launcher's own query (dc_conv3x3_f32_route)"""
+    r = f32_conv_route(cin, h, w, cout, stride)
+    return ("f32conv", r.form, r.stride, r.co_tile, r.pixel_tile)
+
+
+def _f32(form, stride, co=None, pt=256):
+    return ("f32conv", form, stride, co if co is not None else {"blk": 64, "direct": 16}[form], pt)
+
+
+def _f32_cases(key, shapes, notes=()):
+    """cases of one instance: N = 2, and N = 3 (an odd batch) for the first"""
+    return [F32ConvCase(key, 3 if i == 0 else 2, *s, note=notes[i] if i < len(notes) else "") for i, s in enumerate(shapes)]
+
+
+# (Cin, H, W, Cout, stride) per instance
+F32_CONV_CASES = (
+    # ---------------------------------------------------------------- conv3x3_f32_mfma_kernel<STRIDE, CO_T, PT>
+    _f32_cases(_f32("mfma", 1, 64, 64), [(16, 8, 8, 64, 1), (24, 4, 16, 128, 1), (16, 64, 1, 64, 1)],
+               ["8x8 map, 2 chunks", "4x16 map, 3 chunks, 2 channel tiles", "64x1 map: one-column tile"])
+    + _f32_cases(_f32("mfma", 2, 64, 64), [(16, 16, 16, 64, 2), (24, 8, 32, 64, 2)], ["output 8x8", "output 4x16"])
+    + _f32_cases(_f32("mfma", 1, 64, 128), [(16, 2, 256, 64, 1), (24, 16, 8, 64, 1), (16, 6, 64, 128, 1), (40, 128, 1, 64, 1),
+                                            (16, 2, 256, 128, 1)],
+                 ["cols_t 128, 2 tiles across x 2 down", "8 x 16 tile", "3 tile rows x 2 channel tiles", "one-column tile, 5 chunks",
+                  "2 x 2 pixel tiles x 2 channel tiles"])
+    + _f32_cases(_f32("mfma", 2, 64, 128), [(16, 4, 512, 64, 2), (24, 32, 16, 64, 2), (16, 256, 2, 64, 2), (16, 24, 128, 64, 2)],
+                 ["widest patch 3 x 257", "cols_t 8", "tallest patch 257 x 3 (one-column tile)", "cols_t 64"])
+    + _f32_cases(_f32("mfma", 1, 32, 128), [(16, 2, 256, 32, 1), (24, 12, 32, 96, 1)], ["1 channel tile", "3 channel tiles, 3 tile rows"])
+    + _f32_cases(_f32("mfma", 2, 32, 128), [(16, 4, 512, 32, 2), (24, 24, 64, 96, 2)])
+    # ---------------------------------------------------------------- conv3x3_nchw_f32_blk_kernel<STRIDE, 16, 4, 4, 8>
+    + _f32_cases(_f32("blk", 1), [(3, 17, 66, 64, 1), (9, 5, 64, 80, 1), (17, 3, 35, 160, 1), (8, 16, 64, 64, 1),
+                                  (4, 3, 67, 70, 1)],
+                 ["Wo % 4 != 0: scalar-store arm, Cin 3", "ragged 16-channel group, Cin 9", "32-wide / 160-channel entry rule, Cin 17",
+                  "exact tiles, vector stores", "Cout % 16 != 0: six channels in the second tile"])
+    + _f32_cases(_f32("blk", 2), [(5, 9, 131, 65, 2), (8, 7, 66, 160, 2), (16, 33, 128, 64, 2), (16, 7, 130, 64, 2)],
+                 ["output 5x66, one channel in the second tile", "output 4x33", "output 17x64: odd H refused by the MFMA rule",
+                  "output 4x65"])
+    # ---------------------------------------------------------------- conv3x3_nchw_f32_kernel<STRIDE, 8 | 2>
+    + _f32_cases(_f32("direct", 1), [(1, 5, 7, 1, 1), (3, 17, 33, 17, 1), (9, 16, 16, 16, 1), (16, 8, 8, 48, 1)],
+                 ["Cin 1, Cout 1", "ragged tiles, Cout 17", "exact tile", "Cout % 32 != 0 keeps a GEMM-shaped layer here"])
+    + _f32_cases(_f32("direct", 2), [(1, 9, 6, 3, 2), (11, 33, 18, 20, 2)])
+    + _f32_cases(_f32("direct", 4), [(3, 8, 8, 16, 4), (5, 66, 35, 33, 4), (2, 130, 9, 8, 4), (16, 64, 64, 64, 4)],
+                 ["output 2x2", "output 17x9, H = 2 mod 4: the last input row is read", "output 33x3", "output 16x16"])
+)
+
+# route-only: the extractor pyramid at its true map sizes (tests/test_gpu_ops.py::test_conv3x3_nchw_f32_mfma_form launches them):
+# (Cin, Cout, H = W, stride) -> instance key, cols_t x rows_t
+F32_CONV_PYRAMID = [
+    ((16, 32, 512, 2), _f32("mfma", 2, 32, 128), (128, 1)),    # 256-wide output: 1 x 128 pixel tiles, the widest stride-2 patch
+    ((32, 32, 256, 1), _f32("mfma", 1, 32, 128), (128, 1)),
+    ((32, 64, 64, 2), _f32("mfma", 2, 64, 128), (32, 4)),      # 32-wide output: 4 x 32 tiles
+    ((64, 64, 128, 1), _f32("mfma", 1, 64, 128), (128, 1)),
+    ((64, 160, 128, 2), _f32("mfma", 2, 32, 128), (64, 2)),    # Cout = 160: 32-channel tiles
+    ((160, 160, 64, 2), _f32("mfma", 2, 32, 128), (32, 4)),
+    ((160, 320, 64, 1), _f32("mfma", 1, 64, 128), (64, 2)),    # 2 x 64 tiles
+    ((160, 320, 32, 1), _f32("mfma", 1, 64, 128), (32, 4)),
+    ((160, 320, 32, 2), _f32("mfma", 2, 64, 128), (16, 8)),    # 16-wide output: 8 x 16 tiles
+    ((320, 640, 16, 2), _f32("mfma", 2, 64, 64), (8, 8)),      # 8x8 output: the 64-pixel tile
+    ((640, 1280, 8, 1), _f32("mfma", 1, 64, 64), (8, 8)),
+    ((640, 64, 8, 1), _f32("mfma", 1, 64, 64), (8, 8)),
+    ((320, 64, 16, 1), _f32("mfma", 1, 64, 128), (16, 8)),
+    ((24, 96, 16, 1), _f32("mfma", 1, 32, 128), (16, 8)),      # Cin not a multiple of 16 (three 8-channel chunks)
+]
+
+F32_CONV_INSTANCES = 11
+
+
+def enumerate_f32_conv_keys():
+    """Every instance key dc_conv3x3_f32_route yields over Cin x H x W x Cout x stride: channel counts below / at / off the 8-channel
+    chunk and the 16 / 32 / 64-channel tiles, power-of-two maps from 1 to 512 plus every odd and ragged size of the table.
+    -> {key: example (Cin, H, W, Cout, stride)}"""
+    sizes = sorted({1, 2, 4, 8, 16, 32, 64, 128, 256, 512} | {c.h for c in F32_CONV_CASES} | {c.w for c in F32_CONV_CASES})
+    keys = {}
+    for stride in (1, 2, 4):
+        for cin in (1, 3, 8, 9, 16, 24, 40):
+            for cout in (1, 3, 16, 17, 32, 48, 64, 65, 80, 96, 128, 160):
+                for h in sizes:
+                    for w in sizes:
+                        keys.setdefault(f32_conv_key(cin, h, w, cout, stride), (cin, h, w, cout, stride))
+    return keys
+
+
+def f32_conv_inputs(c, i):
+    """fp32 (x [N, Cin, H, W], w [Cout, Cin, 3, 3], bias [Cout]) of case i of F32_CONV_CASES (CPU; seed 2000 + i)"""
+    gen = torch.Generator().manual_seed(2000 + i)
+    x = torch.randn(c.n, c.cin, c.h, c.w, generator=gen) + 0.3
+    w = torch.randn(c.cout, c.cin, 3, 3, generator=gen) / math.sqrt(c.cin * 9)
+    b = torch.randn(c.cout, generator=gen) * 0.1
+    return x, w, b
+
+
+# ------------------------------------------------------------------------------------------ loop-state kernels
+# (B, C, H, W): odd sizes inside one trip of the grid-stride loops, and the smallest latent-shaped state above their cap of
+# 8192 workgroups x 256 threads (2,097,152 elements): 33 x 4 x 128 x 128 = 2,162,688 enters the second trip
+STATE_SHAPES = [(3, 4, 5, 7), (33, 4, 128, 128)]
+STATE_GUIDANCE = 3.7                              # 1 - g and g itself are not exact in fp32
+DDIM_TABLE_STEPS = 100                            # timesteps 991, 981, ... 1: holds the rows the CPU tests use
+DDIM_ROWS_T = (981, 951, 501, 1)
+
+
+def ddim_table():
+    """(timesteps list, coefficient table [steps, 4] fp32) of the SD-1.5 scaled-linear DDIM schedule at DDIM_TABLE_STEPS steps"""
+    from diffcodec_amd.scheduler import DDIMScheduler
+    s = DDIMScheduler()
+    s.set_timesteps(DDIM_TABLE_STEPS)
+    return s.timesteps.tolist(), s.coefficients()
+
+
+def ddim_inputs(shape, cfg, seed):
+    """fp32 (eps NHWC [(2 if cfg else 1) B, H, W, C], latents NCHW [B, C, H, W]) on the CPU"""
+    b, c, h, w = shape
+    gen = torch.Generator().manual_seed(seed)
+    return torch.randn((2 if cfg else 1) * b, h, w, c, generator=gen), torch.randn(b, c, h, w, generator=gen)
+
+
+def vae_inputs(shape, seed):
+    """fp32 (moments NHWC [N, H, W, 2C], noise NCHW [N, C, H, W]) on the CPU.  Log-variances ~ N(-2, 3^2), and by flat index:
+    exactly on the clamps (-30 every 7th, 20 every 11th) and beyond them (-45 every 13th, 33 every 17th).  Where the log-variance
+    lies below the lower clamp the mean is 0, so that exp(-15) z is the whole result and a missing clamp is not hidden under it."""
+    n, c, h, w = shape
+    gen = torch.Generator().manual_seed(seed)
+    mean = torch.randn(n, h, w, c, generator=gen)
+    lv = (3 * torch.randn(n, h, w, c, generator=gen) - 2).reshape(-1)
+    for step, v in ((7, -30.0), (11, 20.0), (13, -45.0), (17, 33.0)):
+        lv[step - 1::step] = v
+    lv = lv.reshape(n, h, w, c)
+    mean = torch.where(lv < -30.0, torch.zeros_like(mean), mean)
+    return torch.cat([mean, lv], 3).contiguous(), torch.randn(n, c, h, w, generator=gen)

@@ -234,3 +234,145 @@ def test_peaked_family_rejects_a_stale_running_max(nk):
     assert L.check(r.to(torch.bfloat16), r, s, torch.bfloat16)["ok"]
     wrong = _attention_no_rescale(q, k, v, heads).to(torch.bfloat16)
     assert not L.check(wrong, r, s, torch.bfloat16)["ok"]
+
+
+# ------------------------------------------------------------------------------------------ fp32 extractor conv routes
+@pytest.fixture(scope="module")
+def f32_keys(lib):
+    return E.enumerate_f32_conv_keys()
+
+
+def test_f32_conv_grid_finds_exactly_the_eleven_instances(f32_keys):
+    want = {("f32conv", "mfma", s, co, pt) for s in (1, 2) for co, pt in ((64, 64), (64, 128), (32, 128))}
+    want |= {("f32conv", "blk", s, 64, 256) for s in (1, 2)} | {("f32conv", "direct", s, 16, 256) for s in (1, 2, 4)}
+    assert len(want) == E.F32_CONV_INSTANCES and set(f32_keys) == want, sorted(set(f32_keys) ^ want)
+
+
+def test_every_f32_conv_instance_has_a_case(f32_keys):
+    missing = uncovered(f32_keys, E.F32_CONV_CASES)
+    assert not missing, "fp32 conv instances without an edge case:\n" + "\n".join(missing)
+    extra = sorted({E.key_str(c.key) for c in E.F32_CONV_CASES if c.key not in f32_keys})
+    assert not extra, "table instances the grid does not reach:\n" + "\n".join(extra)
+
+
+@pytest.mark.parametrize("i", range(len(E.F32_CONV_CASES)), ids=[c.label() for c in E.F32_CONV_CASES])
+def test_f32_conv_case_routes_where_it_declares(lib, i):
+    c = E.F32_CONV_CASES[i]
+    got = E.f32_conv_key(c.cin, c.h, c.w, c.cout, c.stride)
+    assert got == c.key, f"{c.label()}: declared {E.key_str(c.key)}, routes to {E.key_str(got)}"
+
+
+@pytest.mark.parametrize("shape,key,tile", E.F32_CONV_PYRAMID, ids=[str(p[0]) for p in E.F32_CONV_PYRAMID])
+def test_f32_conv_pyramid_layers_keep_their_mfma_tiles(lib, shape, key, tile):
+    """the extractor pyramid of a 512x512 frame: every many-channel layer stays on the MFMA form, on the tile its comment names"""
+    cin, cout, hw, stride = shape
+    r = E.f32_conv_route(cin, hw, hw, cout, stride)
+    assert E.f32_conv_key(cin, hw, hw, cout, stride) == key and (r.cols_t, r.rows_t) == tile, (shape, r)
+
+
+def _f32_route_restated(cin, h, w, cout, stride):
+    """the routing rule of dc_conv3x3_nchw_f32 restated: (form, stride, co_tile, pixel_tile, cols_t, rows_t)"""
+    ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+    if stride in (1, 2) and cin >= 16 and cin % 8 == 0 and cout % 32 == 0 and not (stride == 2 and (h % 2 or w % 2)) and ho * wo >= 64:
+        pt = 128 if ho * wo >= 128 else 64
+        cols = min(wo, pt)
+        if not (pt == 64 and cout % 64) and pt % cols == 0 and wo % cols == 0 and ho % (pt // cols) == 0:
+            rows = pt // cols
+            if 8 * ((rows - 1) * stride + 3) * ((cols - 1) * stride + 3) <= 26 * 256:
+                return ("mfma", stride, 64 if (pt == 64 or cout % 64 == 0) else 32, pt, cols, rows)
+    if stride != 4 and cout >= 64 and (wo >= 64 or (wo >= 32 and cout >= 160)):
+        return ("blk", stride, 64, 256, 16, 16)
+    return ("direct", stride, 16, 256, 16, 16)
+
+
+def test_f32_conv_route_equals_the_restated_rule(lib):
+    """routing did not move: over every table shape, the pyramid and a grid of ragged sizes the query returns what the rule of the
+    launcher before the routing function existed (restated above) gives"""
+    shapes = [(c.cin, c.h, c.w, c.cout, c.stride) for c in E.F32_CONV_CASES]
+    shapes += [(ci, hw, hw, co, s) for (ci, co, hw, s), _, _ in E.F32_CONV_PYRAMID]
+    # a 960x512 frame's pyramid levels and tile sizes that are not powers of two
+    shapes += [(ci, h, w, co, s) for ci in (3, 16, 24, 160) for co in (32, 64, 160, 320) for s in (1, 2, 4)
+               for (h, w) in ((512, 960), (256, 480), (128, 240), (64, 120), (32, 60), (16, 30), (8, 15), (96, 96), (48, 80), (1, 128),
+                              (128, 1), (7, 9), (2, 32), (1, 1))]
+    for sh in shapes:
+        assert tuple(E.f32_conv_route(*sh)) == _f32_route_restated(*sh), sh
+
+
+def test_removing_a_sole_f32_conv_case_names_its_instance(f32_keys):
+    for key in f32_keys:
+        cases = [c for c in E.F32_CONV_CASES if c.key != key]
+        assert uncovered(f32_keys, cases) == [E.key_str(key)]
+    count = {}
+    for c in E.F32_CONV_CASES:
+        count[c.key] = count.get(c.key, 0) + 1
+    for i, c in enumerate(E.F32_CONV_CASES):
+        if count[c.key] == 1:
+            assert uncovered(f32_keys, E.F32_CONV_CASES[:i] + E.F32_CONV_CASES[i + 1:]) == [E.key_str(c.key)]
+
+
+def test_f32_conv_route_refuses_what_the_launch_refuses(lib):
+    from diffcodec_amd import ops
+    for bad in ((16, 8, 8, 64, 3), (16, 8, 8, 64, 0), (0, 8, 8, 64, 1), (-8, 8, 8, 64, 1), (16, 0, 8, 64, 1), (16, 8, 0, 64, 2),
+                (16, 8, 8, 0, 4), (16, 8, 8, 64, 8)):
+        with pytest.raises(lib.HipLaunchError):
+            ops.conv3x3_f32_route(*bad)
+        # the launch: its own operand checks pass (non-null pointers, N = 1), the shape is refused before anything is launched
+        assert lib.load().dc_conv3x3_nchw_f32(16, 0, 16, 16, 16, 1, *bad[:5], 0, None) == -1, bad
+    assert ops.conv3x3_f32_route(16, 8, 8, 64, 1).form == "mfma"
+
+
+def test_f32_conv_table_spans_the_tile_and_store_edges(lib):
+    """the table still holds: MFMA tiles of 1, 8, 16, 64 and 128 columns; an MFMA grid with more than one tile in x, in y and in
+    channels at once; blocked cases on the scalar-store arm (Wo % 4 != 0) and with a ragged 16-channel group; Cin off the
+    8-channel staging step on the VALU forms; a stride-4 case whose last input row is read; an odd batch per instance"""
+    mfma = [(c, E.f32_conv_route(c.cin, c.h, c.w, c.cout, c.stride)) for c in E.F32_CONV_CASES if c.key[1] == "mfma"]
+    assert {r.cols_t for _, r in mfma} >= {1, 8, 16, 64, 128}
+    assert {(r.cols_t, r.rows_t) for _, r in mfma} >= {(1, 64), (1, 128), (128, 1), (8, 16), (16, 4), (8, 8)}
+    assert any(c.wo // r.cols_t > 1 and c.ho // r.rows_t > 1 and c.cout // r.co_tile > 1 for c, r in mfma)
+    for s in (1, 2):
+        assert any(c.cin // 8 >= 3 for c, r in mfma if c.stride == s)                       # more than the prologue + one chunk
+    blk = [c for c in E.F32_CONV_CASES if c.key[1] == "blk"]
+    for s in (1, 2):
+        b = [c for c in blk if c.stride == s]
+        assert any(c.wo % 4 for c in b) and any(c.wo % 4 == 0 for c in b) and any(c.cout % 16 for c in b)
+        assert any(c.cin % 8 for c in b) and any(c.wo % 16 or c.ho % 16 for c in b)
+    direct = [c for c in E.F32_CONV_CASES if c.key[1] == "direct"]
+    assert any(c.cin == 1 for c in direct) and any(c.cout == 1 for c in direct) and any(c.cout % 16 for c in direct)
+    s4 = [c for c in direct if c.stride == 4]
+    assert s4 and any(c.last_row_read for c in s4) and sum(not c.last_row_read for c in s4) == 2 and any(c.cin % 2 for c in s4)
+    assert all(c.last_row_read for c in E.F32_CONV_CASES if c.stride != 4)
+    for key in {c.key for c in E.F32_CONV_CASES}:
+        assert {c.n for c in E.F32_CONV_CASES if c.key == key} == {2, 3}, key
+    assert max(c.m * c.cout for c in E.F32_CONV_CASES) * 4 <= 9 << 20                       # the largest operand stays below 9 MB
+
+
+# ------------------------------------------------------------------------------------------ fp32 conv: the bound is sharp
+def _trunc10(t):
+    """fp32 values truncated to 10 mantissa bits (a reduced-precision matrix path)"""
+    return (t.view(torch.int32) & ~0x1FFF).view(torch.float32)
+
+
+@pytest.mark.parametrize("i", range(len(E.F32_CONV_CASES)), ids=[c.label() for c in E.F32_CONV_CASES])
+def test_f32_conv_bound_passes_torch_and_rejects_faults(i):
+    """the check the GPU edge test applies (L.conv3x3_nchw_f32_ref + L.check over every output pixel) on this case's own inputs:
+    torch's fp32 conv (another accumulation order) passes, and a kernel that truncates its operands to 10 mantissa bits, drops the
+    bias, skips the last input channel or skips the last input row fails"""
+    import torch.nn.functional as F
+    c = E.F32_CONV_CASES[i]
+    x, w, b = E.f32_conv_inputs(c, i)
+    rows = torch.arange(c.m)
+    flat = lambda y: y.permute(0, 2, 3, 1).reshape(c.m, c.cout)
+    xc, xr = x.clone(), x.clone()
+    xc[:, -1] = 0
+    xr[:, :, -1] = 0
+    faults = {"10-bit operands": (_trunc10(x), _trunc10(w), b), "no bias": (x, w, None), "last channel skipped": (xc, w, b)}
+    if c.last_row_read:
+        faults["last row skipped"] = (xr, w, b)
+    for silu in (True, False):
+        act = F.silu if silu else (lambda t: t)
+        r, s = L.conv3x3_nchw_f32_ref(x, w, b, rows, stride=c.stride, silu=silu)
+        v = L.check(flat(act(F.conv2d(x, w, b, stride=c.stride, padding=1))), r, s, torch.float32)
+        assert v["ok"], (c.label(), silu, v)
+        for name, (fx, fw, fb) in faults.items():
+            bad = flat(act(F.conv2d(fx, fw, fb, stride=c.stride, padding=1)))
+            assert not L.check(bad, r, s, torch.float32)["ok"], (c.label(), silu, name)

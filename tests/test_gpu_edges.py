@@ -1,5 +1,5 @@
-"""GPU: every case of tests/edge_cases.py — each conv / linear and attention kernel instance the dispatchers can reach, and the
-normalisation kernels at their template and chunking edges — launched on guarded operands and outputs, its route asserted first,
+"""GPU: every case of tests/edge_cases.py — each conv / linear, fp32 extractor conv and attention kernel instance the dispatchers can
+reach, the normalisation kernels at their template and chunking edges, and the fused loop's state kernels — launched on guarded operands and outputs, its route asserted first,
 its output held to the fp64 reference of oracle/launch_ref.py with L.check, its guards checked bit for bit, and a second launch
 into a second guarded output required to be bitwise equal.  Worst err/tol per instance goes to `record`."""
 import math
@@ -182,6 +182,175 @@ def test_small_conv_edge(ops, record, i):
     r, s = L.conv_ref(x.view, pc, rows, gn_ab=None if gab is None else gab.view, gn_silu=c.gn, stride=c.stride, pad=c.pad)
     key = (c.kind, "strip" if c.strip_kernel else f"cout={c.cout}" if c.kind == "small_cout" else "pixel")
     _note(record, key, L.check(outs[0].view.reshape(m, c.cout), r, s, outs[0].dtype), c.label())
+
+
+# ------------------------------------------------------------------------------------------ fp32 extractor conv
+@pytest.mark.parametrize("i", range(len(E.F32_CONV_CASES)), ids=[c.label() for c in E.F32_CONV_CASES])
+def test_f32_conv_edge(ops, record, i):
+    """dc_conv3x3_nchw_f32 on a channel-slice view whose neighbouring channel planes, like every guard, hold the NaN pattern: an
+    over-read of x, w or bias makes the output non-finite.  With bias and SiLU, then without either."""
+    from diffcodec_amd import lib
+    c = E.F32_CONV_CASES[i]
+    assert E.f32_conv_key(c.cin, c.h, c.w, c.cout, c.stride) == c.key, c.label()
+    x, w, b = E.f32_conv_inputs(c, i)
+    gx = E.Guarded((c.n, c.cin + 2, c.h, c.w), F32, DEV)
+    xv = gx.view[:, 1:c.cin + 1]
+    xv.copy_(x.to(DEV))
+    gw, gb = _g(tuple(w.shape), F32, w.to(DEV)), _g(tuple(b.shape), F32, b.to(DEV))
+    ho, wo, m = c.ho, c.wo, c.m
+    rows = L.sample_rows(m, spatial=(c.n, ho, wo)) if m > 4096 else torch.arange(m)
+    pat = E._signed(E.NAN_BITS[F32], F32)
+    for bias, silu in ((True, True), (False, False)):
+        what = f"{c.label()} bias={int(bias)} silu={int(silu)}"
+        outs = []
+        for rep in range(2):
+            go = _g((c.n, c.cout, ho, wo), F32)
+            lib.call("dc_conv3x3_nchw_f32", xv.data_ptr(), xv.stride(0), gw.view.data_ptr(), gb.view.data_ptr() if bias else 0,
+                     go.view.data_ptr(), c.n, c.cin, c.h, c.w, c.cout, c.stride, int(silu), torch.cuda.current_stream().cuda_stream)
+            torch.cuda.synchronize()
+            outs.append(go)
+        for name, g in (("x", gx), ("w", gw), ("bias", gb), ("out", outs[0]), ("out (second launch)", outs[1])):
+            g.assert_intact(f"{what} {name}")
+        planes = gx.view[:, [0, c.cin + 1]].contiguous().view(torch.int32)
+        assert bool((planes == pat).all()), f"{what}: a neighbouring channel plane of x was written"
+        assert outs[0].unwritten() == 0, f"{what}: {outs[0].unwritten()} output elements never written"
+        assert bool(torch.isfinite(outs[0].view).all()), f"{what}: non-finite output (a poisoned operand element was read)"
+        assert _same_bits(outs[0].view, outs[1].view), f"{what}: launch-to-launch difference"
+        r, s = L.conv3x3_nchw_f32_ref(xv, gw.view, gb.view if bias else None, rows, stride=c.stride, silu=silu)
+        y = outs[0].view.permute(0, 2, 3, 1).reshape(m, c.cout)[rows.to(DEV)]
+        _note(record, c.key, L.check(y, r, s, F32), what)
+
+
+# ------------------------------------------------------------------------------------------ loop-state kernels
+_SHAPE_IDS = ["x".join(str(v) for v in s) for s in E.STATE_SHAPES]
+
+
+@pytest.mark.parametrize("cfg", [True, False], ids=["cfg", "nocfg"])
+@pytest.mark.parametrize("shape,t", [(E.STATE_SHAPES[0], t) for t in E.DDIM_ROWS_T] + [(E.STATE_SHAPES[1], 501), (E.STATE_SHAPES[1], 1)])
+def test_cfg_ddim_step_edge(ops, record, shape, t, cfg):
+    """dc_cfg_ddim_step (the default scheduler step of the fused loop): a three-row coefficient table whose rows 0 and 2 hold the NaN
+    pattern and a step counter that starts at 1, so that any other row index poisons the latents."""
+    b, c, h, w = shape
+    ts, table = E.ddim_table()
+    row = table[ts.index(t)]
+    eps, lat = E.ddim_inputs(shape, cfg, 9300 + t)
+    g = E.STATE_GUIDANCE if cfg else 1.0
+    geps = _g(tuple(eps.shape), F32, eps.to(DEV))
+    gcoef = E.Guarded((3, 4), F32, DEV)
+    gcoef.view[1] = row.to(DEV)
+    pat = E._signed(E.NAN_BITS[F32], F32)
+    runs = []
+    for rep in range(2):
+        glat = _g(shape, F32, lat.to(DEV))
+        gin = _g((2 * b, h, w, c), BF)
+        step = torch.tensor([-7, 1, -7], dtype=torch.int32, device=DEV)
+        ops.cfg_ddim_step(geps.view, glat.view, gin.view, gcoef.view, step[1:2], g, cfg)
+        torch.cuda.synchronize()
+        runs.append((glat, gin, step))
+    what = f"cfg_ddim_step {shape} t={t} cfg={int(cfg)}"
+    geps.assert_intact(f"{what} eps")
+    gcoef.assert_intact(f"{what} coef")
+    assert torch.equal(geps.view.cpu(), eps), f"{what}: eps written"
+    assert bool((gcoef.view[[0, 2]].contiguous().view(torch.int32) == pat).all()) and torch.equal(gcoef.view[1].cpu(), row)
+    for glat, gin, step in runs:
+        glat.assert_intact(f"{what} latents")
+        gin.assert_intact(f"{what} model_in")
+        assert step.tolist() == [-7, 2, -7], f"{what}: step counter {step.tolist()}"
+    glat, gin, _ = runs[0]
+    assert _same_bits(glat.view, runs[1][0].view) and _same_bits(gin.view, runs[1][1].view), f"{what}: launch-to-launch difference"
+    r, s = L.cfg_ddim_step_ref(geps.view, lat.to(DEV), row, g, cfg, b)
+    _note(record, ("cfg_ddim_step", "cfg" if cfg else "nocfg"), L.check(glat.view, r, s, F32), what)
+    want_in = glat.view.permute(0, 2, 3, 1).to(BF)
+    assert _same_bits(gin.view[:b], want_in), f"{what}: model_in is not bf16(new latents) in NHWC"
+    if cfg:
+        assert _same_bits(gin.view[b:], want_in), f"{what}: the CFG half of model_in differs"
+        assert gin.unwritten() == 0
+    else:
+        assert gin.unwritten() == b * h * w * c, f"{what}: the second half of a 2B-sized model_in was written"
+        assert bool((gin.view[b:].contiguous().view(torch.int16) == E._signed(E.NAN_BITS[BF], BF)).all())
+
+
+@pytest.mark.parametrize("cfg", [True, False], ids=["cfg", "nocfg"])
+def test_cfg_unipc_step_large_state_is_bit_identical_with_the_generic_step(ops, cfg):
+    """tests/test_gpu_round3.py::test_fused_unipc_step_is_bit_identical_with_the_generic_scheduler_step at the state size that
+    enters the second trip of the kernel's grid-stride loop, over a three-step schedule (order warm-up, corrector, lower-order
+    final step)."""
+    import numpy as np
+    from diffcodec_amd.scheduler import UniPCMultistepScheduler
+    b, c, h, w = E.STATE_SHAPES[1]
+    guidance, n = E.STATE_GUIDANCE, 3
+    sg, sf = UniPCMultistepScheduler(), UniPCMultistepScheduler()
+    sg.set_timesteps(n)
+    sf.set_timesteps(n)
+    coef, _ = sf.device_tables(DEV)
+    g = torch.Generator().manual_seed(9400)
+    x0 = torch.randn(b, c, h, w, generator=g)
+    lat_g, lat_f = x0.to(DEV), x0.to(DEV).clone()
+    ms = [torch.full((b, c, h, w), float("nan"), device=DEV) for _ in range(3)]        # never read before they are written
+    gin = _g(((2 if cfg else 1) * b, h, w, c), BF)
+    step = torch.zeros(1, device=DEV, dtype=torch.int32)
+    for i, t in enumerate(sg.timesteps.tolist()):
+        eps = torch.randn((2 if cfg else 1) * b, h, w, c, generator=g).to(DEV)
+        e = eps.permute(0, 3, 1, 2).contiguous()
+        if cfg:
+            nu, nt = (v.contiguous() for v in e.chunk(2))
+            g32 = np.float32(guidance)
+            e = ops.lincomb([(float(np.float32(1.0) - g32), nu), (float(g32), nt)])
+        lat_g = sg.step(e, t, lat_g, return_dict=False)[0]
+        ops.cfg_unipc_step(eps, lat_f, ms[0], ms[1], ms[2], gin.view, coef, step, guidance if cfg else 1.0, cfg)
+        assert torch.equal(lat_f, lat_g), i
+        assert bool(torch.isfinite(lat_f).all())
+        want_in = lat_f.permute(0, 2, 3, 1).to(BF)
+        assert torch.equal(gin.view[:b], want_in) and (not cfg or torch.equal(gin.view[b:], want_in))
+        gin.assert_intact(f"cfg_unipc_step model_in, step {i}")
+    assert int(step.item()) == n
+
+
+@pytest.mark.parametrize("mul", [1.0, 1.0 / 0.18215], ids=["mul1", "unscale"])
+@pytest.mark.parametrize("rep", [1, 2])
+@pytest.mark.parametrize("shape", E.STATE_SHAPES, ids=_SHAPE_IDS)
+def test_latents_to_model_input_edge(ops, record, shape, rep, mul):
+    b, c, h, w = shape
+    lat = torch.randn(shape, generator=torch.Generator().manual_seed(9500 + rep))
+    glat = _g(shape, F32, lat.to(DEV))
+    outs = []
+    for k in range(2):
+        go = _g((rep * b, h, w, c), BF)
+        assert ops.latents_to_model_input(glat.view, mul, rep, out=go.view) is go.view
+        torch.cuda.synchronize()
+        outs.append(go)
+    what = f"latents_to_model_input {shape} rep={rep} mul={mul:.4f}"
+    for g in [glat] + outs:
+        g.assert_intact(what)
+    assert torch.equal(glat.view.cpu(), lat)
+    assert outs[0].unwritten() == 0 and _same_bits(outs[0].view, outs[1].view)
+    if rep == 2:
+        assert _same_bits(outs[0].view[:b], outs[0].view[b:]), f"{what}: the two copies differ"
+    r, s = L.latents_to_model_input_ref(glat.view, mul, rep)
+    _note(record, ("latents_to_model_input",), L.check(outs[0].view, r, s, BF), what)
+
+
+@pytest.mark.parametrize("scale", [0.18215, 1.0])
+@pytest.mark.parametrize("shape", E.STATE_SHAPES, ids=_SHAPE_IDS)
+def test_vae_sample_latents_edge(ops, record, shape, scale):
+    from diffcodec_amd import lib
+    n, c, h, w = shape
+    mom, noise = E.vae_inputs(shape, 9600)
+    gm, gz = _g(tuple(mom.shape), F32, mom.to(DEV)), _g(shape, F32, noise.to(DEV))
+    outs = []
+    for k in range(2):
+        go = _g(shape, F32)
+        lib.call("dc_vae_sample_latents", gm.view.data_ptr(), gz.view.data_ptr(), go.view.data_ptr(), float(scale), n, c, h, w,
+                 torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        outs.append(go)
+    what = f"vae_sample_latents {shape} scale={scale}"
+    for g in [gm, gz] + outs:
+        g.assert_intact(what)
+    assert outs[0].unwritten() == 0 and bool(torch.isfinite(outs[0].view).all()) and _same_bits(outs[0].view, outs[1].view)
+    r, s = L.vae_sample_latents_ref(gm.view, gz.view, scale)
+    _note(record, ("vae_sample_latents",), L.check(outs[0].view, r, s, F32), what)
+    assert torch.equal(ops.vae_sample_latents(gm.view, gz.view, scale), outs[0].view)      # the wrapper launches the same
 
 
 # ------------------------------------------------------------------------------------------ attention

@@ -348,3 +348,87 @@ def test_conv3x3_nchw_f32_ref_equals_torch(stride, silu):
     bad = y.clone()
     bad[3, 2] *= 1 + 2 ** -12                                    # a bf16-class error is far outside an fp32 launch's bound
     assert not L.check(bad, r, s, torch.float32)["ok"]
+
+
+# ------------------------------------------------------------------------------------------ loop-state kernels
+def _ddim_f32(eps, lat, row, guidance, cfg, B):
+    """the kernel's arithmetic restated in fp32 (torch on the CPU: every operation rounds to fp32)"""
+    s1mat, sat, sap, s1map = row.to(torch.float32)
+    e = eps.permute(0, 3, 1, 2)
+    if cfg:
+        eu, et = e[:B], e[B:]
+        e = eu + torch.tensor(guidance, dtype=torch.float32) * (et - eu)
+    x0 = (lat - s1mat * e) / sat
+    return sap * x0 + s1map * e
+
+
+@pytest.mark.parametrize("cfg", [True, False])
+@pytest.mark.parametrize("t", [981, 951, 501, 1])
+def test_cfg_ddim_step_ref_passes_fp32_and_rejects_faults(t, cfg):
+    """cfg_ddim_step_ref on the rows t = 981, 951, 501 and 1 of the scaled-linear table: the fp32 restatement passes; a neighbouring
+    coefficient row, swapped CFG halves, ignored guidance and an epsilon rounded to bf16 fail"""
+    import edge_cases as E
+    ts, table = E.ddim_table()
+    i = ts.index(t)
+    shape = E.STATE_SHAPES[0]
+    B = shape[0]
+    eps, lat = E.ddim_inputs(shape, cfg, 9000 + t)
+    g = E.STATE_GUIDANCE if cfg else 1.0
+    r, s = L.cfg_ddim_step_ref(eps, lat, table[i], g, cfg, B)
+    assert r.shape == lat.shape and r.dtype == torch.float64
+    v = L.check(_ddim_f32(eps, lat, table[i], g, cfg, B), r, s, torch.float32)
+    assert v["ok"], v
+    faults = {"next row": _ddim_f32(eps, lat, table[i + 1 if i + 1 < len(ts) else i - 1], g, cfg, B),
+              "previous row": _ddim_f32(eps, lat, table[i - 1], g, cfg, B),
+              "bf16 eps": _ddim_f32(eps.to(BF).float(), lat, table[i], g, cfg, B)}
+    if cfg:
+        faults["swapped halves"] = _ddim_f32(torch.cat([eps[B:], eps[:B]]), lat, table[i], g, cfg, B)
+        faults["guidance ignored"] = _ddim_f32(eps, lat, table[i], 1.0, cfg, B)
+    for name, bad in faults.items():
+        assert not L.check(bad, r, s, torch.float32)["ok"], (t, cfg, name)
+
+
+def _vae_f32(mom, noise, scale, lo=-30.0, hi=20.0, half=0.5, swap=False):
+    c = noise.shape[1]
+    mean, lv = mom[..., :c].permute(0, 3, 1, 2), mom[..., c:].permute(0, 3, 1, 2)
+    if swap:
+        mean, lv = lv, mean
+    return (mean + torch.exp(torch.tensor(half) * lv.clamp(lo, hi)) * noise) * torch.tensor(scale, dtype=torch.float32)
+
+
+def test_vae_sample_latents_ref_passes_fp32_and_rejects_faults():
+    import edge_cases as E
+    mom, noise = E.vae_inputs(E.STATE_SHAPES[0], 9100)
+    c = noise.shape[1]
+    lv = mom[..., c:]
+    for v in (-45.0, -30.0, 20.0, 33.0):                          # beyond both clamps and exactly on them
+        assert int((lv == v).sum()) >= 4, v
+    scale = 0.18215
+    r, s = L.vae_sample_latents_ref(mom, noise, scale)
+    ok = L.check(_vae_f32(mom, noise, scale), r, s, torch.float32)
+    assert ok["ok"], ok
+    inf = float("inf")
+    faults = {"no upper clamp": _vae_f32(mom, noise, scale, hi=inf), "no lower clamp": _vae_f32(mom, noise, scale, lo=-inf),
+              "no scale": _vae_f32(mom, noise, 1.0), "exp(lv)": _vae_f32(mom, noise, scale, half=1.0),
+              "mean and log-variance swapped": _vae_f32(mom, noise, scale, swap=True)}
+    for name, bad in faults.items():
+        assert not L.check(bad, r, s, torch.float32)["ok"], name
+    # scale 1 (the encoder path of vae.py) is held by the same bound
+    r1, s1 = L.vae_sample_latents_ref(mom, noise, 1.0)
+    assert L.check(_vae_f32(mom, noise, 1.0), r1, s1, torch.float32)["ok"]
+
+
+@pytest.mark.parametrize("mul,rep", [(1.0, 1), (1.0, 2), (1.0 / 0.18215, 1), (1.0 / 0.18215, 2)])
+def test_latents_to_model_input_ref_passes_fp32_and_rejects_faults(mul, rep):
+    g = torch.Generator().manual_seed(9200)
+    lat = torch.randn(3, 4, 5, 7, generator=g)
+    r, s = L.latents_to_model_input_ref(lat, mul, rep)
+    assert r.shape == (3 * rep, 5, 7, 4)
+    good = (lat * torch.tensor(mul, dtype=torch.float32)).to(BF).permute(0, 2, 3, 1).repeat(rep, 1, 1, 1)
+    assert L.check(good, r, s, BF)["ok"]
+    nchw = (lat * torch.tensor(mul, dtype=torch.float32)).to(BF).reshape(3, 5, 7, 4).repeat(rep, 1, 1, 1)      # layout not changed
+    assert not L.check(nchw, r, s, BF)["ok"]
+    trunc = ((lat * torch.tensor(mul, dtype=torch.float32)).view(torch.int32) & ~0xFFFF).view(torch.float32)   # truncated, not rounded
+    assert not L.check(trunc.permute(0, 2, 3, 1).repeat(rep, 1, 1, 1), r, s, BF)["ok"]
+    if mul != 1.0:
+        assert not L.check(lat.to(BF).permute(0, 2, 3, 1).repeat(rep, 1, 1, 1), r, s, BF)["ok"]
