@@ -262,13 +262,15 @@ def blend_frames(unit_u8, units, height, width, overlap=64):
 
 
 def _score_frames(frames, source, lpips=None, fid=None):
-    """(scores, {frame: (decoded [64], truth [64])} fp32 FID feature rows on the host, empty without `fid`)"""
+    """(scores, {frame: (decoded [64], truth [64])} fp32 FID feature rows on the host, empty without `fid`, {frame: ground truth on
+    the frame's device})"""
     from . import metrics
-    scores, rows = {}, {}
+    scores, rows, truth = {}, {}, {}
     for f, pred in sorted(frames.items()):
         gt = source.ground_truth(f).to(pred.device)
         if gt.shape != pred.shape:
             raise ValueError(f"ground truth of frame {f} has shape {tuple(gt.shape)}, the decoded frame {tuple(pred.shape)}")
+        truth[f] = gt
         x, y = pred.unsqueeze(0), gt.unsqueeze(0)
         scores[f] = dict(psnr=float(metrics.psnr(x, y, data_range=255.0)[0]), ms_ssim=float(metrics.ms_ssim(x, y, data_range=255)))
         if lpips is not None:
@@ -276,7 +278,7 @@ def _score_frames(frames, source, lpips=None, fid=None):
         if fid is not None and not scores[f]["psnr"] > 1000:
             r = fid.features(torch.cat([x, y])).cpu()
             rows[f] = (r[0], r[1])
-    return scores, rows
+    return scores, rows, truth
 
 
 def fid_update_rows(fid, rows):
@@ -293,6 +295,23 @@ def _fid_value(fid):
     return fid.compute() if min(float(real[0]), float(fake[0])) >= 2 else float("nan")
 
 
+def fvd_of_frames(fvd, frames, truth, scores):
+    """The clip's FVD as test_utils.py:45-70 forms it: the decoded video is the scored frames in ascending order (frames whose PSNR
+    exceeds 1000 dB left out, as for FID), the truth video the same frames of ground truth; each is ONE video, which the reference
+    stacks twice (`repeat(2, ...)`, test_utils.py:69-70).  The features are computed once and the row is added twice: with two
+    identical rows the covariance is exactly zero and the value is |f_decoded - f_truth|^2.  NaN with fewer than 9 such frames.
+    `fvd` (a `metrics.FrechetVideoDistance` with weights loaded) is reset first."""
+    from . import metrics
+    keep = [f for f in sorted(frames) if not scores[f]["psnr"] > 1000]
+    fvd.reset()
+    if len(keep) < metrics.FVD_MIN_FRAMES:
+        return float("nan")
+    rows = fvd.features(torch.stack([torch.stack([frames[f] for f in keep]), torch.stack([truth[f] for f in keep])]))
+    fvd.update_features(rows[0:1].expand(2, -1), real=False)
+    fvd.update_features(rows[1:2].expand(2, -1), real=True)
+    return fvd.compute()
+
+
 def score_frames(frames, source, lpips=None, fid=None):
     """{frame: uint8 [H,W,3] tensor} -> {frame: {"psnr": dB, "ms_ssim": value}} against `source.ground_truth(frame)`, with L = 255
     (test_utils.py:23-24, :55; validation.py:147-150 on x / 255 gives the same values), on the device of the frames.
@@ -303,7 +322,7 @@ def score_frames(frames, source, lpips=None, fid=None):
     (real side) in ascending frame order, as test_utils.py:62-63 does; it is not reset here, `fid.compute()` gives the value.  FID is
     a statistic of the set, so the per-frame dicts do not change.  test_utils.py:51-52 `continue`s past identical frames before the
     update: a frame whose PSNR exceeds 1000 dB is left out."""
-    scores, rows = _score_frames(frames, source, lpips, fid)
+    scores, rows, _ = _score_frames(frames, source, lpips, fid)
     if fid is not None:
         fid_update_rows(fid, rows)
     return scores
@@ -364,7 +383,7 @@ def gather_fid_rows(rows, units, rank, world, dst=0):
 @torch.no_grad()
 def decode_clip(pipe, source, num_frames, gop_size, height, width, prompt_embeds, negative_prompt_embeds=None, *, tile=512,
                 overlap=64, batch=16, seed=0, rank=None, world=None, shard_mode="unit", gather=True, score=False, lpips=None,
-                fid=None, **pipe_kwargs):
+                fid=None, fvd=None, **pipe_kwargs):
     """Whole pipeline for one clip on this rank.  Returns dict(units=all units, mine=this rank's, images=this rank's fp32 unit
     images, frames={frame: uint8 HxWx3} on the gathering rank (or for locally complete frames when gather=False)).
     score=True adds scores={frame: {"psnr": dB, "ms_ssim": value}}: each blended frame against `source.ground_truth(frame)` on
@@ -375,11 +394,19 @@ def decode_clip(pipe, source, num_frames, gop_size, height, width, prompt_embeds
     fid_features={frame: (decoded [64], truth [64])} (fp32 rows on the host; frames whose PSNR exceeds 1000 dB are left out, as
     test_utils.py:51-52 skips them) and, on the rank that holds the scores, fid = the value (NaN with fewer than two frames): the
     model is reset, then updated in ascending frame order.  With gather=False and world > 1 one more gather brings the feature rows
-    (not the sums) to rank 0, which accumulates them in frame order: the value has the bits of a single-rank run."""
+    (not the sums) to rank 0, which accumulates them in frame order: the value has the bits of a single-rank run.
+    `fvd=` (a `metrics.FrechetVideoDistance` with weights loaded) adds fvd = the clip's FVD on the rank that holds the scores
+    (`fvd_of_frames`: the scored frames as one decoded and one truth video, each row added twice; NaN with fewer than 9 scored
+    frames).  The frames enter at the decode size; the reference first resizes its PIL frames to 512 x 512, which is the identity
+    for a 512 x 512 decode and is not done here.  With gather=False and world > 1 no rank holds the whole video: ValueError, raised
+    before anything is decoded.  With lpips=, fid= and fvd= one call returns the reference's five numbers."""
     if rank is None or world is None:
         ini = torch.distributed.is_available() and torch.distributed.is_initialized()
         rank = torch.distributed.get_rank() if ini else 0
         world = torch.distributed.get_world_size() if ini else 1
+    have_fvd = score and fvd is not None
+    if have_fvd and not gather and world > 1:
+        raise ValueError("fvd= scores the clip as one video: with gather=False and world > 1 no rank holds all its frames")
     units = plan_units(num_frames, gop_size, height, width, tile, overlap)
     mine = shard(units, rank, world, shard_mode)
     unit_hw = (min(height, tile), min(width, tile))            # a frame smaller than the tile is one frame-sized unit (ranks with an empty
@@ -395,11 +422,15 @@ def decode_clip(pipe, source, num_frames, gop_size, height, width, prompt_embeds
         fid.reset()
     holds_scores = rank == 0 or not (gather and world > 1)      # whether this rank's result carries the clip's (or its own) scores
 
+    fvd_value = None
+
     def blend(unit_u8, us):
-        nonlocal scores, rows
+        nonlocal scores, rows, fvd_value
         dev = _blend_frame_tensors(unit_u8, us, height, width, overlap)
         if score:
-            scores, rows = _score_frames(dev, source, lpips, fid)
+            scores, rows, truth = _score_frames(dev, source, lpips, fid)
+            if have_fvd:
+                fvd_value = fvd_of_frames(fvd, dev, truth, scores)
         return {f: t.cpu().numpy() for f, t in dev.items()}
 
     if gather and world > 1:
@@ -433,4 +464,6 @@ def decode_clip(pipe, source, num_frames, gop_size, height, width, prompt_embeds
         if holds_scores:
             fid_update_rows(fid, rows)
             out["fid"] = _fid_value(fid)
+    if have_fvd and holds_scores:
+        out["fvd"] = fvd_value if fvd_value is not None else float("nan")
     return out

@@ -96,6 +96,13 @@ SIGNATURES = {
     "dc_fid_maps": [vp, i32, POINTER(i64), i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
     "dc_fid_conv": [i32, vp, i32, vp, vp, vp],
     "dc_fid_accumulate": [vp, i32, vp, vp],
+    "dc_fvd_weight_floats": [],
+    "dc_fvd_ws_bytes": [i32, i32, i32, i32],
+    "dc_fvd_features": [vp, i32, i32, POINTER(i64), i32, i32, i32, i32, i32, i32, vp, vp, vp, vp],
+    "dc_fvd_endpoints": [vp, i32, i32, POINTER(i64), i32, i32, i32, i32, i32, i32, vp, vp, POINTER(vp), vp, vp],
+    "dc_fvd_preprocess": [vp, i32, i32, POINTER(i64), i32, i32, i32, i32, i32, i32, vp, vp],
+    "dc_fvd_conv": [vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, vp, i32, i32, vp],
+    "dc_fvd_maxpool": [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp],
 }
 
 _lib = None

@@ -1,5 +1,5 @@
-"""Frame quality metrics on the device: PSNR, SSIM and MS-SSIM (csrc/metrics.hip), LPIPS (csrc/lpips.hip, `class LPIPS` below) and
-FID (csrc/fid.hip, `class FrechetInceptionDistance` below).
+"""Frame quality metrics on the device: PSNR, SSIM and MS-SSIM (csrc/metrics.hip), LPIPS (csrc/lpips.hip, `class LPIPS` below),
+FID (csrc/fid.hip, `class FrechetInceptionDistance` below) and FVD (csrc/fvd.hip, `class FrechetVideoDistance` below).
 
 The reference harness scores every decoded frame against its ground truth: validation.py:120-155 (`ms_ssim(pred, gt,
 data_range=1.0)`, `10*log10(1/mse)`) and test_utils.py:23-55 (`psnr`, `ms_ssim(..., data_range=255)`), both through
@@ -188,12 +188,12 @@ def psnr(X, Y, data_range=255.0):
     return out.cpu() if host else out
 
 
-def summarize(scores, fid=None):
+def summarize(scores, fid=None, fvd=None):
     """Means over frames of {frame: {"psnr": dB, "ms_ssim": value[, "lpips": value]}} (decode_clip(score=True)), following
     test_utils.py:49-55: a frame whose PSNR exceeds 1000 dB (identical images) is left out of the means.  Returns dict(psnr,
     ms_ssim, frames = the number averaged, identical = the number left out) and, when the scores carry it, lpips; the means are
     NaN when no frame is left.  `fid` (decode_clip's out["fid"], a statistic of the clip and not a mean over frames) is passed
-    through as "fid" when given."""
+    through as "fid" when given, and `fvd` (out["fvd"]) as "fvd"."""
     kept = [s for _, s in sorted(scores.items()) if not s["psnr"] > 1000]
     m = len(kept)
     out = dict(psnr=sum(s["psnr"] for s in kept) / m if m else float("nan"),
@@ -203,6 +203,8 @@ def summarize(scores, fid=None):
         out["lpips"] = sum(s["lpips"] for s in kept) / m if m else float("nan")
     if fid is not None:
         out["fid"] = float(fid)
+    if fvd is not None:
+        out["fvd"] = float(fvd)
     return out
 
 
@@ -419,6 +421,15 @@ def pack_fid_weights(state_dict):
     return torch.cat(parts).contiguous()
 
 
+def _frechet_value(mu_r, cov_r, mu_f, cov_f):
+    """|mu_r - mu_f|^2 + tr cov_r + tr cov_f - 2 tr (cov_r cov_f)^(1/2) from fp64 means [d] and covariances [d,d] of any dimension
+    (FID: 64, FVD: 400), the last term as the singular values of cov_r^(1/2) cov_f^(1/2) (see `frechet_distance`)."""
+    d = mu_r - mu_f
+    (a_r, u_r), (a_f, u_f) = torch.linalg.eigh(cov_r), torch.linalg.eigh(cov_f)
+    c = torch.linalg.svdvals((u_r * a_r.clamp_min(0).sqrt()).t() @ (u_f * a_f.clamp_min(0).sqrt())).sum()
+    return float((d * d).sum() + cov_r.trace() + cov_f.trace() - 2 * c)
+
+
 def frechet_distance(state_real, state_fake):
     """The value from two fp64 state vectors [1 + 64 + 4096] (n, sum f, sum f f^T), on the host in fp64:
     mu = sum / n, cov = (sumsq - n mu mu^T) / (n - 1), |mu_r - mu_f|^2 + tr cov_r + tr cov_f - 2 sum sqrt(eigvals(cov_r cov_f)).real.
@@ -438,10 +449,7 @@ def frechet_distance(state_real, state_fake):
         sq = st[1 + FID_FEATURES:].view(FID_FEATURES, FID_FEATURES)
         stats.append((mu, (sq - n * torch.outer(mu, mu)) / (n - 1)))
     (mu_r, cov_r), (mu_f, cov_f) = stats
-    d = mu_r - mu_f
-    (a_r, u_r), (a_f, u_f) = torch.linalg.eigh(cov_r), torch.linalg.eigh(cov_f)
-    c = torch.linalg.svdvals((u_r * a_r.clamp_min(0).sqrt()).t() @ (u_f * a_f.clamp_min(0).sqrt())).sum()
-    return float((d * d).sum() + cov_r.trace() + cov_f.trace() - 2 * c)
+    return _frechet_value(mu_r, cov_r, mu_f, cov_f)
 
 
 class FrechetInceptionDistance:
@@ -616,3 +624,329 @@ class FrechetInceptionDistance:
     def compute(self):
         """The Frechet distance of the two accumulated sets as a Python float (synchronises: the state is copied to the host)."""
         return frechet_distance(self._state[True], self._state[False])
+
+
+# ------------------------------------------------------------------------------------------------------------- FVD
+FVD_FEATURES = 400
+FVD_SIZE = 224
+FVD_MIN_FRAMES = 9                                   # the head's [2,7,7] mean needs two time slices of Mixed_5c
+FVD_CHUNK_BYTES = 1 << 30                            # scratch bound of one launch sequence (about 100 MB of maps per 16-frame video)
+FVD_BN_EPS = 1e-5
+FVD_MAX_FRAMES, FVD_MAX_SIDE = 4096, 16384           # the limits of dc_fvd_ws_bytes
+# The network in endpoint order.  ("conv", Cin, Cout, kernel, stride): a Unit3D (conv3d without bias, eval BatchNorm, ReLU), kernel
+# and stride the same on (t, h, w); ("pool", kernel (t, h, w), stride (t, h, w)): a SAME-padded max-pool whose padding is zeros
+# that enter the max; ("mixed", Cin, (b0, b1a, b1b, b2a, b2b, b3b)): the six-unit module of FVD_BRANCHES.
+FVD_NET = (
+    ("Conv3d_1a_7x7", "conv", 3, 64, 7, 2),
+    ("MaxPool3d_2a_3x3", "pool", (1, 3, 3), (1, 2, 2)),
+    ("Conv3d_2b_1x1", "conv", 64, 64, 1, 1),
+    ("Conv3d_2c_3x3", "conv", 64, 192, 3, 1),
+    ("MaxPool3d_3a_3x3", "pool", (1, 3, 3), (1, 2, 2)),
+    ("Mixed_3b", "mixed", 192, (64, 96, 128, 16, 32, 32)),
+    ("Mixed_3c", "mixed", 256, (128, 128, 192, 32, 96, 64)),
+    ("MaxPool3d_4a_3x3", "pool", (3, 3, 3), (2, 2, 2)),
+    ("Mixed_4b", "mixed", 480, (192, 96, 208, 16, 48, 64)),
+    ("Mixed_4c", "mixed", 512, (160, 112, 224, 24, 64, 64)),
+    ("Mixed_4d", "mixed", 512, (128, 128, 256, 24, 64, 64)),
+    ("Mixed_4e", "mixed", 512, (112, 144, 288, 32, 64, 64)),
+    ("Mixed_4f", "mixed", 528, (256, 160, 320, 32, 128, 128)),
+    ("MaxPool3d_5a_2x2", "pool", (2, 2, 2), (2, 2, 2)),
+    ("Mixed_5b", "mixed", 832, (256, 160, 320, 32, 128, 128)),
+    ("Mixed_5c", "mixed", 832, (384, 192, 384, 48, 128, 128)),
+)
+# A module's units in state-dict order: (name, kernel, input = "x" the module's input / the unit it follows / "pool" = the 3x3x3
+# stride-1 max-pool of the input).  The output is cat(b0, b1b, b2b, b3b) along the channels.
+FVD_BRANCHES = (("b0", 1, "x"), ("b1a", 1, "x"), ("b1b", 3, "b1a"), ("b2a", 1, "x"), ("b2b", 3, "b2a"), ("b3b", 1, "pool"))
+FVD_ENDPOINTS = tuple(row[0] for row in FVD_NET)
+
+
+def fvd_units():
+    """[(state-dict prefix, Cin, Cout, kernel, stride)] of the 57 Unit3D with BatchNorm, in state-dict order (the logits conv,
+    1024 -> 400 with a bias and no BatchNorm, follows them)."""
+    units = []
+    for name, kind, *rest in FVD_NET:
+        if kind == "conv":
+            units.append((name,) + tuple(rest))
+        elif kind == "mixed":
+            cin, ch = rest
+            src = {"x": cin, "pool": cin}
+            for (b, k, inp), co in zip(FVD_BRANCHES, ch):
+                units.append((f"{name}.{b}", src[inp], co, k, 1))
+                src[b] = co
+    return units
+
+
+def fvd_same_pad(size, k, s):
+    """TF "SAME" on one axis: (output size, front padding, back padding)."""
+    pad = max(k - s, 0) if size % s == 0 else max(k - size % s, 0)
+    return -(-size // s), pad // 2, pad - pad // 2
+
+
+def fvd_endpoint_shapes(t):
+    """[(C, T', S, S)] of the 16 endpoint maps for a t-frame video (after the 224 x 224 preprocess)."""
+    shapes, c, s = [], 3, FVD_SIZE
+    for name, kind, *rest in FVD_NET:
+        if kind == "conv":
+            _, c, k, st = rest
+            t, s = fvd_same_pad(t, k, st)[0], fvd_same_pad(s, k, st)[0]
+        elif kind == "pool":
+            k, st = rest
+            t, s = fvd_same_pad(t, k[0], st[0])[0], fvd_same_pad(s, k[1], st[1])[0]
+        else:
+            ch = rest[1]
+            c = ch[0] + ch[2] + ch[4] + ch[5]
+        shapes.append((c, t, s, s))
+    return shapes
+
+
+def fvd_resized_size(h, w):
+    """(RH, RW) of fvd.py:176-180: the shorter side becomes 224, the other ceil(side * scale) with scale = 224 / min(h, w) as
+    Python floats (the same expression, so the same integer)."""
+    scale = FVD_SIZE / min(h, w)
+    return (FVD_SIZE, math.ceil(w * scale)) if h < w else (math.ceil(h * scale), FVD_SIZE)
+
+
+def _fvd_tensor(sd, key, shape):
+    if key not in sd:
+        raise ValueError(f"FVD state dict: missing key {key!r}")
+    t = sd[key]
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"FVD state dict: {key!r} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+    return t.detach().to("cpu", torch.float32)
+
+
+def pack_fvd_unit(w, s, t):
+    """One Unit3D in the layout dc_fvd_conv reads: the K-major matrix [(ci, kt, kh, kw)][Cout rounded up to 32] with the zero rows
+    of its kernel class (7: one after the 49 taps of every (ci, kt); 3: up to a multiple of 4 input channels; 1: up to a multiple of
+    32 input channels), then s and t (y = s * conv + t), zero in the padded columns."""
+    co, ci, k = w.shape[0], w.shape[1], w.shape[2]
+    if tuple(w.shape[2:]) != (k, k, k) or k not in (1, 3, 7):
+        raise ValueError(f"FVD conv kernels are 1x1x1, 3x3x3 or 7x7x7, got {tuple(w.shape[2:])}")
+    w = w.detach().to("cpu", torch.float32)
+    if k == 7:
+        m = w.reshape(co, ci * 7, 49).permute(1, 2, 0)
+        m = torch.cat([m, torch.zeros(ci * 7, 1, co)], 1).reshape(ci * 7 * 50, co)
+        rows = ci * 7 * 50
+    else:
+        m = w.reshape(co, ci * k ** 3).t()
+        rows = -(-ci // 4) * 108 if k == 3 else -(-ci // 32) * 32
+    out = torch.zeros(rows + 2, -(-co // 32) * 32)
+    out[:m.shape[0], :co] = m
+    out[rows, :co] = s.float()
+    out[rows + 1, :co] = t.float()
+    return out.reshape(-1)
+
+
+def pack_fvd_weights(state_dict, bn_eps=FVD_BN_EPS):
+    """One fp32 CPU vector in the layout dc_fvd_features reads: `pack_fvd_unit` of the 57 units of `fvd_units()` with
+    s = bn.weight / sqrt(running_var + bn_eps), t = bn.bias - running_mean * s (fp64, rounded to fp32), then of the logits conv
+    with s = 1, t = its bias."""
+    parts = []
+    for name, ci, co, k, _ in fvd_units():
+        w = _fvd_tensor(state_dict, f"{name}.conv3d.weight", (co, ci, k, k, k))
+        g, b, m, v = (_fvd_tensor(state_dict, f"{name}.bn.{q}", (co,)).double() for q in ("weight", "bias", "running_mean", "running_var"))
+        s = g / torch.sqrt(v + bn_eps)
+        parts.append(pack_fvd_unit(w, s, b - m * s))
+    w = _fvd_tensor(state_dict, "logits.conv3d.weight", (FVD_FEATURES, 1024, 1, 1, 1))
+    b = _fvd_tensor(state_dict, "logits.conv3d.bias", (FVD_FEATURES,))
+    parts.append(pack_fvd_unit(w, torch.ones(FVD_FEATURES), b))
+    return torch.cat(parts).contiguous()
+
+
+def _fvd_stats(rows):
+    rows = rows.detach().to("cpu", torch.float64)
+    n = rows.shape[0]
+    mu = rows.mean(0)
+    c = rows - mu
+    return mu, c.t() @ c / (n - 1)
+
+
+class FrechetVideoDistance:
+    """The FVD of the reference's clip scoring (test_utils.py:45-70, fvd_utils/models/fvd) on the device in exact fp32
+    (csrc/fvd.hip): the Inception-v1 I3D network of pytorch_i3d.py, 400 logits per video, and the Frechet distance of two sets of
+    such rows.
+
+        input       videos of T >= 9 frames: uint8 [N,T,H,W,3] (taken as x / 255, the documented [0,1] contract of fvd.py; with
+                    byte_range=True the raw 0..255 values, which is what test_utils.py:45-70 actually feeds, kept for comparable
+                    numbers as the LPIPS [0,1] quirk is) or floating [N,T,3,H,W] with any strides, taken as they are
+        preprocess  fvd.py:166-192 per frame: bilinear resize (align_corners=False, no antialias) of the shorter side to 224, the
+                    other to ceil(side * 224 / min(h, w)); centre crop to 224 x 224 from (size - 224) // 2; (v - 0.5) * 2; no clamping
+        network     FVD_NET / FVD_BRANCHES: Unit3D = conv3d + eval BatchNorm (eps = bn_eps; pytorch_i3d.py:69 says 1e-5, the TF
+                    original 1e-3; folded at pack time to one fma per channel) + ReLU, TF "SAME" padding (`fvd_same_pad`); the
+                    max-pools pad by the same rule with zeros that enter the max
+        head        mean over [2,7,7] windows of Mixed_5c, logits conv 1024 -> 400 with bias, mean over the remaining time positions
+        value       mu and cov (n - 1) of the rows of each side on the host in fp64, then `_frechet_value`
+
+    No weights ship with the package and none are downloaded: `load_state_dict` / `from_state_dict` take the InceptionI3d state
+    dict of pytorch_i3d.py (`<endpoint>.conv3d.weight`, `<endpoint>.bn.{weight,bias,running_mean,running_var}`,
+    `Mixed_xx.{b0,b1a,b1b,b2a,b2b,b3b}.conv3d|bn...`, `logits.conv3d.{weight,bias}`; `num_batches_tracked` and unknown keys are
+    ignored), the layout the reference's commented-out loader reads (fvd.py:15-26).  The reference loads a TorchScript detector
+    (`i3d_torchscript.pt`) at run time instead; equivalence of this class with that file is unpinned (the file is not available to
+    the tests).  tests/fvd_ref.py restates the rules above in fp64; tests/golden/fvd_i3d.npz pins that restatement against
+    pytorch_i3d.py and fvd.py with seeded weights, and the device results are checked against the restatement.
+
+    Placement: device tensors give device rows on the current stream with no host synchronisation (graph-capturable once the
+    weights are on the device: `model.to(device)` or a first call); CPU tensors are copied to the current GPU and the rows come
+    back on the CPU.  Batches run in chunks that bound the scratch; a video's row does not depend on its position or on the batch
+    size, bit for bit.  The rows are kept as a list (one per video) and the statistics are formed at `compute()`."""
+
+    def __init__(self, bn_eps=FVD_BN_EPS, byte_range=False):
+        self.bn_eps = float(bn_eps)
+        self.byte_range = bool(byte_range)
+        self.packed = None
+        self._on_device = {}
+        self._rows = {True: [], False: []}
+
+    @classmethod
+    def from_state_dict(cls, state_dict, **kwargs):
+        m = cls(**kwargs)
+        m.load_state_dict(state_dict)
+        return m
+
+    def load_state_dict(self, state_dict):
+        packed = pack_fvd_weights(state_dict, self.bn_eps)
+        want = lib.load().dc_fvd_weight_floats()
+        if packed.numel() != want:
+            raise RuntimeError(f"packed FVD weights hold {packed.numel()} floats, the library expects {want}")
+        self.packed = packed
+        self._on_device = {}
+        return self
+
+    def to(self, device):
+        self._weights(torch.device(device))
+        return self
+
+    def _weights(self, device):
+        if self.packed is None:
+            raise RuntimeError("FrechetVideoDistance has no weights: call load_state_dict / from_state_dict (nothing is downloaded)")
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        w = self._on_device.get(device)
+        if w is None:
+            w = self._on_device[device] = self.packed.to(device)
+        return w
+
+    @staticmethod
+    def _check(videos, min_frames=FVD_MIN_FRAMES):
+        """(n, t, h, w), element strides (n, t, c, h, w) of a uint8 NTHWC or floating NTCHW batch"""
+        if videos.dim() != 5:
+            raise ValueError(f"FVD takes 5-d video batches, got {tuple(videos.shape)}")
+        if videos.dtype == torch.uint8:
+            n, t, h, w, c = videos.shape
+            sn, st, sh, sw, sc = videos.stride()
+        elif videos.dtype.is_floating_point:
+            n, t, c, h, w = videos.shape
+            sn, st, sc, sh, sw = videos.stride()
+        else:
+            raise ValueError(f"FVD videos should be uint8 (NTHWC) or floating point (NTCHW), got {videos.dtype}")
+        if c != 3:
+            raise ValueError(f"FVD takes 3-channel videos, got {c} channels")
+        if t < min_frames:
+            raise ValueError(f"FVD needs at least {min_frames} frames per video, got {t}")
+        if n < 1 or h < 1 or w < 1:
+            raise ValueError(f"FVD needs N, H, W >= 1, got {tuple(videos.shape)}")
+        return (n, t, h, w), (sn, st, sc, sh, sw)
+
+    def _operand(self, videos, min_frames=FVD_MIN_FRAMES):
+        dims, _ = self._check(videos, min_frames)
+        X, _, host = _to_device(videos, videos)
+        if X.dtype != torch.uint8 and X.dtype != torch.float32:
+            X = X.float()
+        return X, host, dims
+
+    def _chunks(self, n, t, h, w):
+        one = lib.load().dc_fvd_ws_bytes(1, t, h, w)
+        if one < 0:
+            raise ValueError(f"FVD takes videos of at most {FVD_MAX_FRAMES} frames of at most {FVD_MAX_SIDE} x {FVD_MAX_SIDE}, got {t} x {h} x {w}")
+        return max(1, min(n, FVD_CHUNK_BYTES // max(1, one)))
+
+    def _call_args(self, xs, t, h, w):
+        (m, _, _, _), strides = self._check(xs, 1)
+        rh, rw = fvd_resized_size(h, w)
+        u8 = xs.dtype == torch.uint8
+        return (xs.data_ptr(), int(u8), int(u8 and not self.byte_range), (ctypes.c_longlong * 5)(*strides), m, t, h, w, rh, rw)
+
+    def features(self, videos):
+        """fp32 [N,400]: the logits of `videos` (uint8 [N,T,H,W,3] or floating [N,T,3,H,W])."""
+        X, host, (n, t, h, w) = self._operand(videos)
+        wts = self._weights(X.device)
+        L = lib.load()
+        out = torch.empty((n, FVD_FEATURES), dtype=torch.float32, device=X.device)
+        step = self._chunks(n, t, h, w)
+        with torch.cuda.device(X.device):
+            stream = torch.cuda.current_stream().cuda_stream
+            for i in range(0, n, step):
+                xs = X[i:i + step]
+                scratch = torch.empty(L.dc_fvd_ws_bytes(xs.shape[0], t, h, w), dtype=torch.uint8, device=X.device)
+                lib.call("dc_fvd_features", *self._call_args(xs, t, h, w), wts.data_ptr(), scratch.data_ptr(), out[i:i + step].data_ptr(),
+                         stream)
+        return out.cpu() if host else out
+
+    def endpoints(self, videos):
+        """The 16 endpoint maps (FVD_ENDPOINTS order), contiguous fp32 [N,C,T',S,S] (the test seam; `features` keeps them in scratch)."""
+        X, host, (n, t, h, w) = self._operand(videos)
+        wts = self._weights(X.device)
+        L = lib.load()
+        outs = [torch.empty((n,) + s, dtype=torch.float32, device=X.device) for s in fvd_endpoint_shapes(t)]
+        feat = torch.empty((n, FVD_FEATURES), dtype=torch.float32, device=X.device)
+        step = self._chunks(n, t, h, w)
+        with torch.cuda.device(X.device):
+            stream = torch.cuda.current_stream().cuda_stream
+            for i in range(0, n, step):
+                xs = X[i:i + step]
+                scratch = torch.empty(L.dc_fvd_ws_bytes(xs.shape[0], t, h, w), dtype=torch.uint8, device=X.device)
+                maps = (ctypes.c_void_p * len(outs))(*[o[i:i + step].data_ptr() for o in outs])
+                lib.call("dc_fvd_endpoints", *self._call_args(xs, t, h, w), wts.data_ptr(), scratch.data_ptr(), maps,
+                         feat[i:i + step].data_ptr(), stream)
+        return [o.cpu() for o in outs] if host else outs
+
+    def preprocess(self, videos):
+        """fp32 [N,3,T,224,224]: the network's input for `videos` (the test seam; any T >= 1)."""
+        X, host, (n, t, h, w) = self._operand(videos, 1)
+        out = torch.empty((n, 3, t, FVD_SIZE, FVD_SIZE), dtype=torch.float32, device=X.device)
+        with torch.cuda.device(X.device):
+            lib.call("dc_fvd_preprocess", *self._call_args(X, t, h, w), out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        return out.cpu() if host else out
+
+    def update_features(self, rows, real):
+        """Add feature rows [N,400] (computed by `features`, here or on another rank) to the real or the fake side, in row order."""
+        if rows.dim() != 2 or rows.shape[1] != FVD_FEATURES:
+            raise ValueError(f"FVD feature rows should be [N,{FVD_FEATURES}], got {tuple(rows.shape)}")
+        if rows.shape[0]:
+            self._rows[bool(real)].append(rows.detach().float())
+
+    def update(self, videos, real):
+        """Add the videos' rows to the real (real=True) or the fake side."""
+        self.update_features(self.features(videos), real)
+
+    def reset(self):
+        self._rows = {True: [], False: []}
+
+    def count(self, real):
+        return sum(r.shape[0] for r in self._rows[bool(real)])
+
+    def compute(self):
+        """The Frechet distance of the two sets as a Python float (synchronises: the rows are copied to the host)."""
+        stats = []
+        for side in (True, False):
+            if self.count(side) < 2:
+                raise RuntimeError("More than one sample is required for both the real and fake distributed to compute FID")
+            stats.append(_fvd_stats(torch.cat([r.to("cpu", torch.float64) for r in self._rows[side]])))
+        (mu_r, cov_r), (mu_f, cov_f) = stats
+        return _frechet_value(mu_r, cov_r, mu_f, cov_f)
+
+
+def calculate_fvd(videos1, videos2, model):
+    """fvd_utils/my_utils.py:10-29 with `model` (a `FrechetVideoDistance` with weights loaded) in place of the detector it loads:
+    two floating batches [B,T,C,H,W] of the same shape, grey (C = 1) repeated to 3 channels; videos1 is the generated side.  The
+    model's accumulated rows are reset."""
+    if videos1.shape != videos2.shape:
+        raise ValueError(f"the two batches should have the same shape, got {tuple(videos1.shape)} and {tuple(videos2.shape)}")
+    if videos1.dim() != 5 or not videos1.dtype.is_floating_point or not videos2.dtype.is_floating_point:
+        raise ValueError(f"calculate_fvd takes floating [B,T,C,H,W] batches, got {tuple(videos1.shape)} {videos1.dtype}")
+    if videos1.shape[2] == 1:
+        videos1, videos2 = videos1.expand(-1, -1, 3, -1, -1), videos2.expand(-1, -1, 3, -1, -1)
+    model.reset()
+    model.update(videos1, real=False)
+    model.update(videos2, real=True)
+    return model.compute()

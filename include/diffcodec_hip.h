@@ -373,6 +373,43 @@ int dc_fid_conv(int layer, const float* x, int N, const float* weights, float* y
  * in batch order: two calls leave the bits of one call on the concatenation. */
 int dc_fid_accumulate(const float* features, int N, double* state, void* stream);
 
+/* FVD features (test_utils.py:45-70; fvd_utils/models/fvd): the Inception-v1 I3D network, 400 logits per video, exact fp32 on the
+ * fp32 matrix instruction, sums in a fixed order (bitwise reproducible, independent of a video's position in the batch and of the
+ * batch size, no float atomics).  Operand: N videos of T >= 9 frames, logical [N][T][3][H][W], uint8 (x_u8 = 1) or fp32, read
+ * through the five element strides (n, t, c, h, w) of `strides` (host array), so uint8 NTHWC frames need no copy; div255 = 1
+ * divides every tap by 255 first.  Per frame: bilinear resize (align_corners = False, no antialias) to RH x RW, where the shorter
+ * side is 224 and the other the caller's ceil(side * 224 / min(H, W)), centre crop to 224 x 224 from (size - 224) / 2, (v - 0.5) * 2,
+ * no clamping.  Then the I3D chain: every Unit3D is conv3d with TF "SAME" padding (per axis pad = max(k - s, 0) when
+ * size % s == 0, else max(k - size % s, 0); front = pad / 2; output ceil(size / s)), eval BatchNorm as one fma per channel, ReLU;
+ * the max-pools pad by the same rule with zeros that enter the max; the head is the [2,7,7] mean of Mixed_5c, the logits conv
+ * with bias, and the mean over the remaining time positions.
+ * weights (device, fp32, 16-byte aligned, dc_fvd_weight_floats() elements): the 58 units in state-dict order (Conv3d_1a_7x7,
+ * Conv3d_2b_1x1, Conv3d_2c_3x3; per Mixed_* module b0, b1a, b1b, b2a, b2b, b3b; logits), each as dc_fvd_conv's `packed`.
+ * ws: dc_fvd_ws_bytes(N, T, H, W) bytes (-1 when T < 9 or a size is out of range).  out (device, fp32) [N][400]. */
+int dc_fvd_weight_floats(void);
+long long dc_fvd_ws_bytes(int N, int T, int H, int W);
+int dc_fvd_features(const void* x, int x_u8, int div255, const long long* strides, int N, int T, int H, int W, int RH, int RW,
+                    const float* weights, void* ws, float* out, void* stream);
+/* The same with the 16 endpoint maps (Conv3d_1a_7x7 .. Mixed_5c, contiguous fp32 [N][C][T'][S][S]) written to the caller's tensors:
+ * maps = host array of 16 device pointers. */
+int dc_fvd_endpoints(const void* x, int x_u8, int div255, const long long* strides, int N, int T, int H, int W, int RH, int RW,
+                     const float* weights, void* ws, float* const* maps, float* out, void* stream);
+/* The preprocess on its own: y = contiguous fp32 [N][3][T][224][224]. */
+int dc_fvd_preprocess(const void* x, int x_u8, int div255, const long long* strides, int N, int T, int H, int W, int RH, int RW,
+                      float* y, void* stream);
+/* One Unit3D on caller-given shapes: x contiguous fp32 [N][Cin][T][H][W]; (k, stride) is (7, 2), (3, 1) or (1, 1) on all three axes;
+ * y [N][Ctot][To][Ho][Wo], of which channels c_off .. c_off + Cout are written (the others are left alone); relu = 0 leaves the
+ * fma's value.  packed (device, fp32, 16-byte aligned): the K-major matrix [rows][CoP], CoP = Cout rounded up to 32 (zero
+ * columns), rows in (ci, kt, kh, kw) order and zero-padded per chunk: k = 7 one zero row after the 49 taps of every (ci, kt);
+ * k = 3 up to a multiple of 4 input channels (108 rows); k = 1 up to a multiple of 32 input channels; then s [CoP], t [CoP] with
+ * y = s * conv + t (BatchNorm folded; s = 1, t = bias for a plain conv). */
+int dc_fvd_conv(const float* x, int N, int Cin, int T, int H, int W, int k, int stride, const float* packed, int Cout, int relu,
+                float* y, int Ctot, int c_off, void* stream);
+/* SAME-padded max-pool of a contiguous fp32 [N][C][T][H][W] map, kernel (kt, kh, kw), stride (st, sh, sw); the padded positions
+ * are zeros that enter the max.  y [N][C][ceil(T / st)][ceil(H / sh)][ceil(W / sw)]. */
+int dc_fvd_maxpool(const float* x, int N, int C, int T, int H, int W, int kt, int kh, int kw, int st, int sh, int sw, float* y,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

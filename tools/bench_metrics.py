@@ -10,7 +10,10 @@ FID leg (csrc/fid.hip, seeded random weights): 16 images and 1 image of 512x512,
 call and per image), `features` alone, the accumulate launch alone and, per conv block, the time of the block's kernel alone
 (dc_fid_conv, back-to-back launches between two events) with its TFLOP/s; resize + pool + host is the remainder of `features`.
 
-    python tools/bench_metrics.py [--batch 16] [--iters 20] [--no-lpips] [--no-fid]"""
+FVD leg (csrc/fvd.hip, seeded random weights): `features` of one 16 x 512 x 512 uint8 video and of a batch of 8, one JSON line each
+with the milliseconds per call and per video and the TFLOP/s over the convolutions' 27.8 G multiply-adds per 16-frame video.
+
+    python tools/bench_metrics.py [--batch 16] [--iters 20] [--no-lpips] [--no-fid] [--no-fvd] [--only-fvd]"""
 import argparse
 import json
 import os
@@ -121,15 +124,54 @@ def fid_leg(iters):
                               accumulate_us=round(t_acc * 1e3, 1), **layers)), flush=True)
 
 
+def fvd_leg(iters):
+    from diffcodec_amd import metrics as M
+    g = torch.Generator().manual_seed(0)
+    sd = {}
+    for name, ci, co, k, _ in M.fvd_units():
+        sd[f"{name}.conv3d.weight"] = torch.randn(co, ci, k, k, k, generator=g) * (2.0 / (ci * k ** 3)) ** 0.5
+        sd[f"{name}.bn.weight"] = 0.5 + torch.rand(co, generator=g)
+        sd[f"{name}.bn.bias"] = 0.2 * torch.randn(co, generator=g)
+        sd[f"{name}.bn.running_mean"] = 0.2 * torch.randn(co, generator=g)
+        sd[f"{name}.bn.running_var"] = 0.5 + torch.rand(co, generator=g)
+    sd["logits.conv3d.weight"] = torch.randn(400, 1024, 1, 1, 1, generator=g) / 32
+    sd["logits.conv3d.bias"] = 0.1 * torch.randn(400, generator=g)
+    model = M.FrechetVideoDistance.from_state_dict(sd).to("cuda")
+    # multiply-adds of the Unit3D convolutions for one 16-frame video
+    macs, shapes, cin = 0.0, M.fvd_endpoint_shapes(16), {}
+    vol = {row[0]: sh[1] * sh[2] * sh[3] for row, sh in zip(M.FVD_NET, shapes)}
+    for name, ci, co, k, _ in M.fvd_units():
+        macs += float(vol[name.split(".")[0]]) * ci * co * k ** 3
+    macs += 1024 * 400
+    gd = torch.Generator(device="cuda").manual_seed(0)
+    for n in (1, 8):
+        x = torch.randint(0, 256, (n, 16, 512, 512, 3), dtype=torch.uint8, device="cuda", generator=gd)
+        for _ in range(2):
+            model.features(x)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            model.features(x)
+        e1.record()
+        torch.cuda.synchronize()
+        ms = e0.elapsed_time(e1) / iters
+        print(json.dumps(dict(fvd="16x512x512", videos=n, features_ms=round(ms, 3), ms_per_video=round(ms / n, 3),
+                              gmac_per_video=round(macs / 1e9, 1), tflops=round(2 * macs * n / (ms * 1e-3) / 1e12, 1))), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--no-lpips", action="store_true")
     ap.add_argument("--no-fid", action="store_true")
+    ap.add_argument("--no-fvd", action="store_true")
+    ap.add_argument("--only-fvd", action="store_true")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_metrics needs the GPU"
     from diffcodec_amd import metrics as M
+    if a.only_fvd:
+        return fvd_leg(a.iters)
     g = torch.Generator(device="cuda").manual_seed(0)
     for h, w in ((512, 512), (1080, 1920)):
         x = torch.randint(0, 256, (a.batch, h, w, 3), dtype=torch.uint8, device="cuda", generator=g)
@@ -154,6 +196,8 @@ def main():
         lpips_leg(a.iters)
     if not a.no_fid:
         fid_leg(a.iters)
+    if not a.no_fvd:
+        fvd_leg(a.iters)
 
 
 if __name__ == "__main__":
