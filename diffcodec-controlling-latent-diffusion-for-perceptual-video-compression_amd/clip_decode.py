@@ -72,9 +72,13 @@ def shard(units, rank, world, mode="unit"):
 class DirectorySource:
     """Controls of one inter frame from the reference's on-disk layout (validation.py:85-93)."""
 
-    def __init__(self, root, video, gop_size, size, device="cuda", flow_dir="optical_flow", flow_bwd_dir="optical_flow_bwd"):
+    def __init__(self, root, video, gop_size, size, device="cuda", flow_dir="optical_flow", flow_bwd_dir="optical_flow_bwd",
+                 device_resize=False):
+        """device_resize: with a GPU `device`, the PNG bytes are uploaded at their native size and the BICUBIC resize to `size` runs
+        on the device (`io_utils._load_rgb_u8_device`): the same bytes without Pillow's pass over every frame on the host."""
         self.root, self.video, self.gop, self.size, self.device = root, video, gop_size, tuple(size), device
         self.flow_dir, self.flow_bwd_dir = flow_dir, flow_bwd_dir
+        self.device_resize = device_resize
 
     def paths(self, frame, prev, nxt):
         base = os.path.join(self.root, self.video)
@@ -85,13 +89,16 @@ class DirectorySource:
 
     def controls(self, frame, prev, nxt):
         from .io_utils import load_controls_and_flows
-        return load_controls_and_flows(*self.paths(frame, prev, nxt), size=self.size, device=self.device)
+        return load_controls_and_flows(*self.paths(frame, prev, nxt), size=self.size, device=self.device,
+                                       device_resize=self.device_resize)
 
     def ground_truth(self, frame):
         """The original frame <root>/<video>/images/frame_%04d.png as uint8 [H,W,3] on `device`, loaded like the anchors
         (BICUBIC resize to `size`, also Pillow's default behind validation.py:120's `.resize((512, 512))`)."""
-        from .io_utils import _load_rgb_u8
+        from .io_utils import _load_rgb_u8, _load_rgb_u8_device
         path = os.path.join(self.root, self.video, "images", f"frame_{frame:04d}.png")
+        if self.device_resize and torch.device(self.device).type == "cuda":
+            return _load_rgb_u8_device(path, self.size, self.device)
         return torch.from_numpy(_load_rgb_u8(path, self.size)).to(self.device)
 
 
@@ -261,9 +268,18 @@ def blend_frames(unit_u8, units, height, width, overlap=64):
     return {f: t.cpu().numpy() for f, t in _blend_frame_tensors(unit_u8, units, height, width, overlap).items()}
 
 
-def _score_frames(frames, source, lpips=None, fid=None):
+def _to_score_size(x, score_size):
+    """uint8 [..., H, W, 3] -> the operand the scores see: resized as test_utils.py:17-21 resizes its PIL frames (Pillow's
+    antialiased BILINEAR, on the device, the same bytes) when `score_size` is given and differs from (H, W); `x` itself otherwise."""
+    if score_size is None or tuple(x.shape[-3:-1]) == tuple(score_size):
+        return x
+    from .resample import resize_u8
+    return resize_u8(x.reshape((-1,) + tuple(x.shape[-3:])), score_size, "bilinear").reshape(tuple(x.shape[:-3]) + tuple(score_size) + (x.shape[-1],))
+
+
+def _score_frames(frames, source, lpips=None, fid=None, score_size=None):
     """(scores, {frame: (decoded [64], truth [64])} fp32 FID feature rows on the host, empty without `fid`, {frame: ground truth on
-    the frame's device})"""
+    the frame's device, at the frame's size})"""
     from . import metrics
     scores, rows, truth = {}, {}, {}
     for f, pred in sorted(frames.items()):
@@ -271,7 +287,7 @@ def _score_frames(frames, source, lpips=None, fid=None):
         if gt.shape != pred.shape:
             raise ValueError(f"ground truth of frame {f} has shape {tuple(gt.shape)}, the decoded frame {tuple(pred.shape)}")
         truth[f] = gt
-        x, y = pred.unsqueeze(0), gt.unsqueeze(0)
+        x, y = _to_score_size(pred.unsqueeze(0), score_size), _to_score_size(gt.unsqueeze(0), score_size)
         scores[f] = dict(psnr=float(metrics.psnr(x, y, data_range=255.0)[0]), ms_ssim=float(metrics.ms_ssim(x, y, data_range=255)))
         if lpips is not None:
             scores[f]["lpips"] = float(lpips(x, y, normalize=False).reshape(-1)[0])
@@ -295,24 +311,26 @@ def _fid_value(fid):
     return fid.compute() if min(float(real[0]), float(fake[0])) >= 2 else float("nan")
 
 
-def fvd_of_frames(fvd, frames, truth, scores):
+def fvd_of_frames(fvd, frames, truth, scores, score_size=None):
     """The clip's FVD as test_utils.py:45-70 forms it: the decoded video is the scored frames in ascending order (frames whose PSNR
     exceeds 1000 dB left out, as for FID), the truth video the same frames of ground truth; each is ONE video, which the reference
     stacks twice (`repeat(2, ...)`, test_utils.py:69-70).  The features are computed once and the row is added twice: with two
     identical rows the covariance is exactly zero and the value is |f_decoded - f_truth|^2.  NaN with fewer than 9 such frames.
-    `fvd` (a `metrics.FrechetVideoDistance` with weights loaded) is reset first."""
+    `fvd` (a `metrics.FrechetVideoDistance` with weights loaded) is reset first.  `score_size`: the two stacked videos are resized
+    to it first (`score_frames`)."""
     from . import metrics
     keep = [f for f in sorted(frames) if not scores[f]["psnr"] > 1000]
     fvd.reset()
     if len(keep) < metrics.FVD_MIN_FRAMES:
         return float("nan")
-    rows = fvd.features(torch.stack([torch.stack([frames[f] for f in keep]), torch.stack([truth[f] for f in keep])]))
+    rows = fvd.features(_to_score_size(torch.stack([torch.stack([frames[f] for f in keep]), torch.stack([truth[f] for f in keep])]),
+                                       score_size))
     fvd.update_features(rows[0:1].expand(2, -1), real=False)
     fvd.update_features(rows[1:2].expand(2, -1), real=True)
     return fvd.compute()
 
 
-def score_frames(frames, source, lpips=None, fid=None):
+def score_frames(frames, source, lpips=None, fid=None, score_size=None):
     """{frame: uint8 [H,W,3] tensor} -> {frame: {"psnr": dB, "ms_ssim": value}} against `source.ground_truth(frame)`, with L = 255
     (test_utils.py:23-24, :55; validation.py:147-150 on x / 255 gives the same values), on the device of the frames.
     `lpips` (a `metrics.LPIPS` with weights loaded) adds "lpips": as test_utils.py:58 computes it, on frame / 255 with
@@ -321,8 +339,12 @@ def score_frames(frames, source, lpips=None, fid=None):
     `fid` (a `metrics.FrechetInceptionDistance` with weights loaded) is updated with every frame (fake side) and its ground truth
     (real side) in ascending frame order, as test_utils.py:62-63 does; it is not reset here, `fid.compute()` gives the value.  FID is
     a statistic of the set, so the per-frame dicts do not change.  test_utils.py:51-52 `continue`s past identical frames before the
-    update: a frame whose PSNR exceeds 1000 dB is left out."""
-    scores, rows, _ = _score_frames(frames, source, lpips, fid)
+    update: a frame whose PSNR exceeds 1000 dB is left out.
+    `score_size=(h, w)`: every frame and its ground truth are first resized to it on the device (`resample.resize_u8`, "bilinear":
+    the bytes of the reference's `transforms.Resize((512, 512))` on its PIL frames, test_utils.py:17-21, :45-46) and all scores,
+    the PSNR behind the 1000 dB rule and the FID rows come from the resized pair; a frame already of that size is scored as it is.
+    The ground truth must still have the decoded frame's shape.  None scores the frames at their own size."""
+    scores, rows, _ = _score_frames(frames, source, lpips, fid, score_size)
     if fid is not None:
         fid_update_rows(fid, rows)
     return scores
@@ -383,7 +405,7 @@ def gather_fid_rows(rows, units, rank, world, dst=0):
 @torch.no_grad()
 def decode_clip(pipe, source, num_frames, gop_size, height, width, prompt_embeds, negative_prompt_embeds=None, *, tile=512,
                 overlap=64, batch=16, seed=0, rank=None, world=None, shard_mode="unit", gather=True, score=False, lpips=None,
-                fid=None, fvd=None, **pipe_kwargs):
+                fid=None, fvd=None, score_size=None, **pipe_kwargs):
     """Whole pipeline for one clip on this rank.  Returns dict(units=all units, mine=this rank's, images=this rank's fp32 unit
     images, frames={frame: uint8 HxWx3} on the gathering rank (or for locally complete frames when gather=False)).
     score=True adds scores={frame: {"psnr": dB, "ms_ssim": value}}: each blended frame against `source.ground_truth(frame)` on
@@ -397,9 +419,12 @@ def decode_clip(pipe, source, num_frames, gop_size, height, width, prompt_embeds
     (not the sums) to rank 0, which accumulates them in frame order: the value has the bits of a single-rank run.
     `fvd=` (a `metrics.FrechetVideoDistance` with weights loaded) adds fvd = the clip's FVD on the rank that holds the scores
     (`fvd_of_frames`: the scored frames as one decoded and one truth video, each row added twice; NaN with fewer than 9 scored
-    frames).  The frames enter at the decode size; the reference first resizes its PIL frames to 512 x 512, which is the identity
-    for a 512 x 512 decode and is not done here.  With gather=False and world > 1 no rank holds the whole video: ValueError, raised
-    before anything is decoded.  With lpips=, fid= and fvd= one call returns the reference's five numbers."""
+    frames).  With gather=False and world > 1 no rank holds the whole video: ValueError, raised before anything is decoded.
+    `score_size=(h, w)`: the reference first resizes its PIL frames to 512 x 512 (test_utils.py:17-21); with score_size=(512, 512)
+    every decoded frame and its ground truth are resized the same way on the device before all five scores (`score_frames`; the
+    stacked videos for FVD), fid_features come from the resized frames and `frames` stay at the decode size.  None (the default)
+    scores at the decode size, which is the same thing for a 512 x 512 decode.  With lpips=, fid=, fvd= and score_size=(512, 512)
+    one call returns the reference's five numbers for a decode of any size."""
     if rank is None or world is None:
         ini = torch.distributed.is_available() and torch.distributed.is_initialized()
         rank = torch.distributed.get_rank() if ini else 0
@@ -428,9 +453,9 @@ def decode_clip(pipe, source, num_frames, gop_size, height, width, prompt_embeds
         nonlocal scores, rows, fvd_value
         dev = _blend_frame_tensors(unit_u8, us, height, width, overlap)
         if score:
-            scores, rows, truth = _score_frames(dev, source, lpips, fid)
+            scores, rows, truth = _score_frames(dev, source, lpips, fid, score_size)
             if have_fvd:
-                fvd_value = fvd_of_frames(fvd, dev, truth, scores)
+                fvd_value = fvd_of_frames(fvd, dev, truth, scores, score_size)
         return {f: t.cpu().numpy() for f, t in dev.items()}
 
     if gather and world > 1:

@@ -6,7 +6,8 @@
     load_pair_to_sixch        utils.py:30-39   two RGB images (PIL, BICUBIC resize) -> [1,6,H,W] in [0,1]
     load_controls_and_flows   utils.py:41-52   -> (controlnet_cond [1,6,H,W], flow_cond [1,4,H,W]) on `device`
 
-File I/O and the PIL resize stay on the host, as in the reference.  With a GPU `device`, `load_controls_and_flows` uploads
+File I/O and the PIL resize stay on the host, as in the reference (`device_resize=True` moves the resize to the GPU: the same
+bytes, `resample.resize_u8`).  With a GPU `device`, `load_controls_and_flows` uploads
 the raw bytes (uint8 images, the .flo payload) and does the float conversion, 6-channel packing, flow resize and vector
 rescale as C-ABI launches; with `device="cpu"` it is the reference's host arithmetic.  The only
 dependency dropped is torchvision (`TF.to_tensor` is restated: HWC uint8 -> CHW float32 / 255)."""
@@ -59,17 +60,27 @@ def _load_rgb_u8(p, size):
     return np.array(img, dtype=np.uint8)
 
 
+def _load_rgb_u8_device(p, size, device):
+    """`_load_rgb_u8` with the resize on the GPU: the decoded bytes are uploaded at their native size and `resize_u8(..., "bicubic")`
+    gives the bytes of `img.resize(size, Image.BICUBIC)`.  Pillow's `size` is (w, h), the order `_load_rgb_u8` passes through."""
+    from .resample import resize_u8
+    img = torch.from_numpy(_load_rgb_u8(p, None)).to(device, non_blocking=True)
+    return img if size is None else resize_u8(img, (size[1], size[0]), "bicubic")
+
+
 def load_pair_to_sixch(path0, path1, size=(512, 512)) -> torch.Tensor:
     return torch.cat([_to_tensor(_load_rgb_u8(path0, size)), _to_tensor(_load_rgb_u8(path1, size))], dim=0).unsqueeze(0)
 
 
 def load_controls_and_flows(img0_path, img1_path, fwd_flo_path, bwd_flo_path, size=(512, 512), device="cuda",
-                            dtype=torch.float32):
+                            dtype=torch.float32, device_resize=False):
+    """device_resize (GPU `device` only): the anchors' BICUBIC resize runs on the device instead of in Pillow; the same bytes."""
     h, w = size
     if torch.device(device).type == "cuda":
         from . import ops
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device, non_blocking=True)
-        sixch = ops.pack_sixch(up(_load_rgb_u8(img0_path, size)), up(_load_rgb_u8(img1_path, size)))
+        rgb = (lambda p: _load_rgb_u8_device(p, size, device)) if device_resize else (lambda p: up(_load_rgb_u8(p, size)))
+        sixch = ops.pack_sixch(rgb(img0_path), rgb(img1_path))
         flow4 = torch.empty((1, 4, h, w), device=device, dtype=torch.float32)
         ops.flow_hw2_resize_scale(up(read_flo(fwd_flo_path)), h, w, out=flow4[0, :2])
         ops.flow_hw2_resize_scale(up(read_flo(bwd_flo_path)), h, w, out=flow4[0, 2:])

@@ -103,6 +103,8 @@ SIGNATURES = {
     "dc_fvd_preprocess": [vp, i32, i32, POINTER(i64), i32, i32, i32, i32, i32, i32, vp, vp],
     "dc_fvd_conv": [vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, vp, i32, i32, vp],
     "dc_fvd_maxpool": [vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp],
+    "dc_resample_ws_bytes": [i32, i32, i32, i32],
+    "dc_resample_u8": [vp, POINTER(i64), i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp],
 }
 
 _lib = None

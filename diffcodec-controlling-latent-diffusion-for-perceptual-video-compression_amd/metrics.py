@@ -208,6 +208,47 @@ def summarize(scores, fid=None, fvd=None):
     return out
 
 
+class _TruthFrames:
+    """`source.ground_truth(frame)` over a batch of original frames"""
+
+    def __init__(self, frames):
+        self.frames = frames
+
+    def ground_truth(self, frame):
+        return self.frames[frame]
+
+
+def calculate_metrics_batch(original, pred, lpips=None, fid=None, fvd=None, size=(512, 512)):
+    """test_utils.py:27-82 on uint8 frames: `original` and `pred` are [N,H,W,3] tensors or lists of [H,W,3] (PIL images as arrays),
+    on the device or on the host.  Both frames of a pair are resized to `size` as the reference's `transforms.Resize` does
+    (`resample.resize_u8`, "bilinear"; None scores them as they are), then scored.  Returns {"PSNR", "MS-SSIM"} and, for every
+    model given (`LPIPS`, `FrechetInceptionDistance`, `FrechetVideoDistance` with weights loaded), "LPIPS", "FID", "FVD": the means
+    over the pairs whose PSNR does not exceed 1000 dB (test_utils.py:51-52), the FID of those pairs (the model is reset first) and
+    the FVD of the two videos they form, each stacked twice (`clip_decode.fvd_of_frames`).  The scoring is `clip_decode`'s: the
+    same calls on the same bytes as `decode_clip(score=True, score_size=size)`."""
+    from . import clip_decode
+    if len(original) != len(pred):
+        raise ValueError(f"calculate_metrics_batch takes as many original as predicted frames, got {len(original)} and {len(pred)}")
+    if not len(pred):
+        raise ValueError("calculate_metrics_batch needs at least one pair of frames")
+    dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None
+    up = lambda t: t if t.is_cuda or dev is None else t.to(dev)
+    frames = {i: up(pred[i]) for i in range(len(pred))}
+    truth_src = _TruthFrames([up(original[i]) for i in range(len(original))])
+    scores, rows, truth = clip_decode._score_frames(frames, truth_src, lpips, fid, size)
+    mean = summarize(scores)
+    out = {"PSNR": mean["psnr"], "MS-SSIM": mean["ms_ssim"]}
+    if lpips is not None:
+        out["LPIPS"] = mean["lpips"]
+    if fid is not None:
+        fid.reset()
+        clip_decode.fid_update_rows(fid, rows)
+        out["FID"] = clip_decode._fid_value(fid)
+    if fvd is not None:
+        out["FVD"] = clip_decode.fvd_of_frames(fvd, frames, truth, scores, size)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------------------- LPIPS
 LPIPS_CHANNELS = (64, 192, 384, 256, 256)
 LPIPS_CIN = (3, 64, 192, 384, 256)

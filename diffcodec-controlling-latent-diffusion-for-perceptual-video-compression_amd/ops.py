@@ -816,3 +816,24 @@ def blend_tiles_ramp(tiles_nchw, coords, full_hw, feather, scale=255.0):
     lib.call("dc_blend_tiles_ramp_u8", tiles_nchw.data_ptr(), coords_d.data_ptr(), t, c, th, tw, ramp_d.data_ptr(), f,
              out.data_ptr(), h, w, float(scale), _stream())
     return out
+
+
+def resample_u8(x, h, w, table_h, table_v):
+    """Pillow's 8-bit resize (csrc/resample.hip): uint8 [N,H,W,C] on the device, any strides -> contiguous uint8 [N,h,w,C].
+    table_h / table_v = (bounds, K, ksize) of `resample.coeffs` on the device of `x` for the width / height axis, None for an axis
+    whose sizes agree (that pass is skipped)."""
+    if not x.is_cuda or x.dtype != torch.uint8 or x.dim() != 4:
+        raise ValueError("x: expected a device uint8 [N,H,W,C] tensor (the HIP path has no CPU fallback)")
+    n, hi, wi, c = x.shape
+    sn, sh, sw, sc = x.stride()
+    strides = (ctypes.c_longlong * 4)(sn, sc, sh, sw)
+    out = torch.empty((n, h, w, c), device=x.device, dtype=torch.uint8)
+    scratch = None
+    if table_h is not None and table_v is not None:
+        scratch = torch.empty(lib.load().dc_resample_ws_bytes(n, hi, w, c), device=x.device, dtype=torch.uint8)
+    bh, kh, nh = table_h if table_h is not None else (None, None, 0)
+    bv, kv, nv = table_v if table_v is not None else (None, None, 0)
+    with torch.cuda.device(x.device):
+        lib.call("dc_resample_u8", x.data_ptr(), strides, n, hi, wi, c, h, w, _ptr(kh), _ptr(bh), nh, _ptr(kv), _ptr(bv), nv,
+                 _ptr(scratch), out.data_ptr(), _stream())
+    return out

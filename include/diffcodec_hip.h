@@ -410,6 +410,22 @@ int dc_fvd_conv(const float* x, int N, int Cin, int T, int H, int W, int k, int 
 int dc_fvd_maxpool(const float* x, int N, int C, int T, int H, int W, int kt, int kh, int kw, int st, int sh, int sw, float* y,
                    void* stream);
 
+/* Pillow's 8-bit antialiased resize (Image.resize with BILINEAR, BICUBIC or LANCZOS; no box=, no reducing_gap=), bit for bit.
+ * in: uint8 [N][H_in][W_in][C], C in 1..4, read through element strides (n, c, h, w) in dc_psnr's order (a cropped window of a
+ * frame is an operand).  out: contiguous uint8 [N][H_out][W_out][C].  Per axis whose sizes differ the caller passes the table
+ * Pillow's precompute_coeffs + normalize_coeffs_8bpc build (device, int32): k [out][ksize] = the float64 filter values,
+ * normalised, times 2^22, rounded half away from zero; bounds [out][2] = (first input sample, tap count <= ksize); ksize =
+ * ceil(support * max(in / out, 1)) * 2 + 1.  One output sample is clip(((1 << 21) + sum_x k[x] * in[first + x]) >> 22, 0, 255) in
+ * int32.  The horizontal pass runs first, into `scratch` (dc_resample_ws_bytes(N, H_in, W_out, C) bytes, any contents; only read
+ * when both passes run), as bytes rounded and clipped like the result; then the vertical pass.  Null tables for an axis mean
+ * "sizes agree, pass skipped" and are an error otherwise; equal sizes on both axes are an error (copy instead).  Errors (a size
+ * < 1, C outside 1..4, a null pointer, a ksize that is not one of the three filters' for the axis sizes) are returned before
+ * anything is launched.  No allocation, no synchronisation. */
+long long dc_resample_ws_bytes(int N, int H_in, int W_out, int C);
+int dc_resample_u8(const void* in, const long long* strides, int N, int H_in, int W_in, int C, int H_out, int W_out, const int* k_h,
+                   const int* bounds_h, int ksize_h, const int* k_v, const int* bounds_v, int ksize_v, void* scratch, void* out,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif
