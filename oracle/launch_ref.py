@@ -572,3 +572,203 @@ def timestep_embedding_ref(t, n, dim):
     r = torch.cat([torch.cos(a), torch.sin(a)])[None].expand(n, dim)
     s = (a.abs() * 2.0 ** -20 / (K_TOL * U)).repeat(2)[None].expand(n, dim)
     return r, s
+
+
+# ------------------------------------------------------------------------------------------ control stage (fp32 NCHW)
+EPS_SPLAT = float(np.float32(0.0000001))           # the constants as the kernels hold them (fp32)
+EPS_FUSE = float(np.float32(1e-6))
+OCC_THRESHOLD = float(np.float32(0.3))
+F32_TINY = 2.0 ** -126                             # smallest normal fp32: below it a reciprocal is flushed to zero
+
+
+def _splat_accumulate(planes, flow):
+    """Forward (summation) splat in fp64 of `planes` [N, C, H, W] (fp64) along flow [N, 2, H, W] (fp32) -> (sum, count k of the
+    sources that reach each target [N, 1, H, W]).  The landing point (x + fx, y + fy) is formed in fp32, as the kernel and the
+    reference kernel form it (in fp64 its floor could name another cell); everything after it is fp64.  Non-finite landing
+    points are skipped; the corner weights are those of softsplat.py:315-318."""
+    n, c, h, w = planes.shape
+    dev = planes.device
+    gy, gx = torch.meshgrid(torch.arange(h, dtype=torch.float32, device=dev), torch.arange(w, dtype=torch.float32, device=dev),
+                            indexing="ij")
+    fx = gx[None] + flow[:, 0].to(torch.float32)
+    fy = gy[None] + flow[:, 1].to(torch.float32)
+    fin = torch.isfinite(fx) & torch.isfinite(fy)
+    fx = torch.where(fin, fx, torch.zeros_like(fx)).to(F64)
+    fy = torch.where(fin, fy, torch.zeros_like(fy)).to(F64)
+    x0, y0 = torch.floor(fx), torch.floor(fy)
+    out = torch.zeros((n, c, h * w), dtype=F64, device=dev)
+    cnt = torch.zeros((n, 1, h * w), dtype=F64, device=dev)
+    src = planes.reshape(n, c, h * w)
+    for dx, dy in ((0, 0), (1, 0), (0, 1), (1, 1)):
+        cx, cy = x0 + dx, y0 + dy
+        wx = (x0 + 1 - fx) if dx == 0 else (fx - x0)
+        wy = (y0 + 1 - fy) if dy == 0 else (fy - y0)
+        ok = fin & (cx >= 0) & (cx < w) & (cy >= 0) & (cy < h)
+        wgt = torch.where(ok, wx * wy, torch.zeros_like(wx)).reshape(n, 1, h * w)
+        idx = torch.where(ok, cy * w + cx, torch.zeros_like(cx)).long().reshape(n, 1, h * w)
+        out.scatter_add_(2, idx.expand(n, c, h * w), src * wgt)
+        cnt.scatter_add_(2, idx, ok.reshape(n, 1, h * w).to(F64))
+    return out.reshape(n, c, h, w), cnt.reshape(n, 1, h, w)
+
+
+def splat_sum_ref(x, flow):
+    """dc_splat_sum_f32: out = sum over sources of in * w -> (r, S, k).  Per target k products in * w (the weight itself carries
+    the roundings of its two factors and of their product) and k additions: n = 3 k + 1, A = sum |in * w|."""
+    xx = x.to(F64)
+    r, k = _splat_accumulate(xx, flow)
+    a, _ = _splat_accumulate(xx.abs(), flow)
+    return r, a * (2.0 ** -24 / U) * torch.sqrt(3 * k + 1), k
+
+
+def splat_soft_ref(x, flow, metric, mask=None):
+    """dc_splat_soft_f32 (softsplat 'soft' mode + FeatureWarperSoftsplat's mask multiply) -> (r, S, k):
+        r = sum in e w / (sum e w + 1e-7) [* (1 - mask)],      e = exp(metric) of the source.
+    Roundings per target with k sources, counted from splat_gather_kernel<1>: in * e, * w and the addition per term of the
+    numerator (3 k), e * w and the addition per term of the denominator (2 k, they enter through |r| den below), then + 1e-7, the
+    divide, 1 - mask and the mask product (4); expf is good to 2 ulp per term, which the factor K_TOL of the check covers.  The
+    running values of numerator and denominator stay below their sums of absolute terms, so the error of the quotient stays below
+        2^-24 sqrt(3 k + 4) A,      A = (sum |in e w| + |r| den) / (den + 1e-7)."""
+    xx, e = x.to(F64), torch.exp(metric.to(F64))
+    n, c = xx.shape[:2]
+    acc, k = _splat_accumulate(torch.cat([xx * e, e, xx.abs() * e], 1), flow)
+    num, den, anum = acc[:, :c], acc[:, c:c + 1], acc[:, c + 1:]
+    r = num / (den + EPS_SPLAT)
+    a = (anum + r.abs() * den) / (den + EPS_SPLAT)
+    if mask is not None:
+        keep = 1.0 - mask.to(F64)
+        r, a = r * keep, a * keep.abs()
+    return r, a * (2.0 ** -24 / U) * torch.sqrt(3 * k + 4), k
+
+
+def occlusion_mask_ref(flow_a, flow_b):
+    """dc_occlusion_mask_f32 (compute_mask, control_utils.py:11-17) -> dict(norm, mask, delta), each [N, 1, H, W]:
+        norm = || b + splat_soft(a, b, ones) ||_2 in fp64,   mask = norm > 0.3 (the threshold as fp32 holds it),
+    delta = the bound on the fp32 kernel's own norm: the bound of each splat component (the gradient of the norm has length <= 1, so
+    they add) plus the five roundings of b + ., the squares, their sum and the root, each below 2^-24 of |b| + |r|.  A device mask
+    may differ from `mask` only where |norm - 0.3| <= delta (check_occlusion_mask)."""
+    r, s, _ = splat_soft_ref(flow_a, flow_b, torch.ones_like(flow_b[:, :1]))
+    b = flow_b.to(F64)
+    d = b + r
+    norm = torch.sqrt((d * d).sum(1, keepdim=True))
+    t = E_OUT_F32 * r.abs() + K_TOL * U * s
+    delta = t.sum(1, keepdim=True) + K_TOL * 2.0 ** -24 * math.sqrt(5) * (b.abs() + r.abs()).sum(1, keepdim=True)
+    return dict(norm=norm, mask=(norm > OCC_THRESHOLD).to(F64), delta=delta)
+
+
+def check_occlusion_mask(y, ref):
+    """y: the launch's mask [N, 1, H, W].  Every value must be exactly 0.0 or 1.0; outside the band |norm - 0.3| <= delta it must equal
+    the reference mask; inside the band either value passes.  -> dict(ok, flips, not_binary, band = share of pixels inside the band,
+    ones = share of reference pixels that are 1)."""
+    yy = y.to(F64)
+    binary = (yy == 0.0) | (yy == 1.0)
+    band = (ref["norm"] - OCC_THRESHOLD).abs() <= ref["delta"]
+    flips = int(((yy != ref["mask"]) & ~band).sum())
+    not_binary = int((~binary).sum())
+    return dict(ok=flips == 0 and not_binary == 0, flips=flips, not_binary=not_binary, band=float(band.to(F64).mean()),
+                ones=float(ref["mask"].mean()))
+
+
+def flow_resize_ref(flow2, h, w, div_x, div_y):
+    """dc_flow_resize_normalize_f32 (div = ((w - 1) / 2, (h - 1) / 2)) and dc_flow_resize_divide_f32: F.interpolate(bilinear,
+    align_corners=False) of flow2 [N, 2, H, W] (any batch stride) to (h, w), the source index clamped at 0, component 0 divided by
+    div_x and component 1 by div_y -> (r, S) [N, 2, h, w].
+    The kernel forms the source coordinate f = (H / h) (o + 0.5) - 0.5 in fp32 (the ratio, the product and the difference: three
+    roundings of at most 2^-24 (|f| + 0.5) each), which moves the interpolation weight; the interpolant is continuous and piecewise
+    linear, so that moves the value by at most the coordinate error times the local slope.  The value path has 12 roundings (1 - l
+    twice, four products and two sums inside, two products and a sum outside, the divide):
+        A = (sum |w_ij s_ij| + 3 (|fy| + 0.5) |slope_y| + 3 (|fx| + 0.5) |slope_x|) / |div|."""
+    n, _, hh, ww = flow2.shape
+    dev = flow2.device
+    s = flow2.to(F64)
+
+    def axis(size_in, size_out):
+        f = (size_in / size_out) * (torch.arange(size_out, dtype=F64, device=dev) + 0.5) - 0.5
+        f = f.clamp_min(0.0)
+        i0 = torch.floor(f).long().clamp_max(size_in - 1)
+        i1 = (i0 + 1).clamp_max(size_in - 1)
+        return f, i0, i1, f - i0
+
+    fy, y0, y1, ly = axis(hh, h)
+    fx, x0, x1, lx = axis(ww, w)
+    ly, lx = ly[:, None], lx[None, :]
+    hy, hx = 1 - ly, 1 - lx
+    s00, s01 = s[:, :, y0][:, :, :, x0], s[:, :, y0][:, :, :, x1]
+    s10, s11 = s[:, :, y1][:, :, :, x0], s[:, :, y1][:, :, :, x1]
+    div = torch.tensor([float(np.float32(div_x)), float(np.float32(div_y))], dtype=F64, device=dev).reshape(1, 2, 1, 1)
+    r = (hy * (hx * s00 + lx * s01) + ly * (hx * s10 + lx * s11)) / div
+    a = hy * (hx * s00.abs() + lx * s01.abs()) + ly * (hx * s10.abs() + lx * s11.abs())
+    slope_y = hx * (s10 - s00).abs() + lx * (s11 - s01).abs()
+    slope_x = hy * (s01 - s00).abs() + ly * (s11 - s10).abs()
+    a = a + 3 * (fy[:, None] + 0.5) * slope_y + 3 * (fx[None, :] + 0.5) * slope_x
+    return r, _f32_chain(12, a / div.abs())
+
+
+def fuse_warped_ref(wf, wl, cf, cb, of=None, ob=None):
+    """dc_fuse_warped_f32 (extractors.py:297-310): a = max(cf, 0), b = max(cb, 0), fused = a / (a + b + 1e-6) wf + b / (a + b + 1e-6) wl,
+    and 0.5 (wf + wl) where of + ob > 1.5 -> (r, S) [N, C, H, W].  Seven roundings (two sums in the denominator, two divides, two
+    products, the sum), A = (a |wf| + b |wl|) / (a + b + 1e-6); in a hole A = 0.5 (|wf| + |wl|)."""
+    f, l = wf.to(F64), wl.to(F64)
+    a, b = cf.to(F64).clamp_min(0.0), cb.to(F64).clamp_min(0.0)
+    ws = a + b + EPS_FUSE
+    r = a / ws * f + b / ws * l
+    aa = a / ws * f.abs() + b / ws * l.abs()
+    if of is not None:
+        hole = (of.to(F64) + ob.to(F64)) > 1.5
+        r = torch.where(hole, 0.5 * (f + l), r)
+        aa = torch.where(hole, 0.5 * (f.abs() + l.abs()), aa)
+    return r, _f32_chain(7, aa)
+
+
+def silu_f32_ref(x):
+    """dc_silu_f32: y = x / (1 + exp(-x)) as x * rcp(1 + exp2(-x log2 e)).  Roundings: the argument product, exp2, 1 +, the reciprocal,
+    the product: n = 5.  The rounding of the exponent's argument (2^-24 |x|) and the 2 ulp of the exponential move e = exp(-x)
+    by a relative (2 + |x|) 2^-24, and the result by e / (1 + e) = 1 - sigmoid(x) of that:
+        A = |y| (1 + (1 - sigmoid(x)) (2 + |x|)),
+    plus |x| 2^-126 for a reciprocal below the smallest normal number, which the hardware flushes to zero."""
+    z = x.to(F64)
+    sg = torch.sigmoid(z)
+    r = z * sg
+    a = r.abs() * (1 + (1 - sg) * (2 + z.abs()))
+    return r, _f32_chain(5, a) + z.abs() * (F32_TINY / (K_TOL * U))
+
+
+def add_f32_ref(a, b):
+    """dc_add_f32: one correctly rounded sum, A = |r|."""
+    r = a.to(F64) + b.to(F64)
+    return r, _f32_chain(1, r.abs())
+
+
+def lincomb_ref(terms):
+    """dc_lincomb4_f32: [(coef, tensor)] of 1 to 4 terms, coefficients as fp32 holds them: v = c0 x0, then one fused multiply-add
+    per further term, in term order: one rounding per term, A = sum |c_i x_i|."""
+    assert 1 <= len(terms) <= 4
+    r, a = 0.0, 0.0
+    for c, t in terms:
+        c = float(np.float32(c))
+        r = r + c * t.to(F64)
+        a = a + abs(c) * t.to(F64).abs()
+    return r, _f32_chain(len(terms), a)
+
+
+def postprocess_image_ref(x):
+    """dc_postprocess_image's fp32 output: x NHWC fp32 [N, H, W, C] (any pixel stride) -> (r, S) NCHW: clamp(x / 2 + 0.5, 0, 1).  The
+    halving is exact; one rounding in the sum, A = |x| / 2 + 0.5.  (The uint8 output is round-half-even(255 o32) of the launch's
+    own fp32 output, compared exactly by the tests.)"""
+    z = x.to(F64).permute(0, 3, 1, 2)
+    return (z / 2 + 0.5).clamp(0.0, 1.0), _f32_chain(1, z.abs() / 2 + 0.5)
+
+
+def nchw_f32_to_nhwc_bf16_ref(x):
+    """exact: the permutation and one round-to-nearest-even to bf16 (compare bit for bit)"""
+    return x.permute(0, 2, 3, 1).to(torch.bfloat16)
+
+
+def nhwc_to_nchw_f32_ref(x):
+    """exact: the permutation (bf16 -> fp32 widens exactly)"""
+    return x.permute(0, 3, 1, 2).to(torch.float32)
+
+
+def embed_tokens_ref(ids, tok_emb, pos_emb):
+    """exact: the fp32 sum of two bf16 values, rounded once to bf16 (in-range ids only)"""
+    t = ids.shape[1]
+    return (tok_emb[ids].to(torch.float32) + pos_emb[:t].to(torch.float32)[None]).to(torch.bfloat16)

@@ -5,10 +5,13 @@ Plain module (imported by tests/test_edge_coverage.py on the CPU and tests/test_
 * `Guarded`: a tensor view inside a larger allocation whose guard elements (before, after, and in the gap between rows of a
   pitched view) hold a NaN with a distinctive payload.  An output view is pre-filled with the same pattern, so an element the
   kernel never writes stays non-finite (L.check treats it as infinitely wrong); `bad()` lists every guard element that no longer
-  holds the pattern, compared as integers.
+  holds the pattern, compared as integers.  A uint8 buffer holds the byte 0xA5 instead: a legitimate output value, so `unwritten()`
+  means nothing for it and such an output is compared in full.
 * `conv_key` / `attention_key`: the kernel instance a launch runs, from the dispatcher's own queries (dc_conv_route and
   dc_conv_instance, dc_attention_route).
 * `f32_conv_key`: the same for the fp32 extractor conv (dc_conv3x3_f32_route).
+* `SPLAT_CASES`, `OCCLUSION_CASES`, `FLOW_RESIZE_CASES`, `FUSE_CASES`, `ELEMENTWISE_CASES`: the control stage (splat, occlusion
+  mask, flow resize, fusion) and the plain elementwise launchers, with the generators of their inputs.
 * `CONV_CASES`, `ATTN_CASES`, `NORM_CASES`, `F32_CONV_CASES`: the tables.  Every conv / attention case declares the instance it
   targets; tests/test_edge_coverage.py proves that every instance the dispatcher can reach has a case and that every case routes
   where it says."""
@@ -18,8 +21,8 @@ from dataclasses import dataclass
 import torch
 
 GUARD = 256                                   # guard elements on each side of a view
-NAN_BITS = {torch.bfloat16: 0x7FA5, torch.float32: 0x7FA5A5A5}
-_INT = {torch.bfloat16: torch.int16, torch.float32: torch.int32}
+NAN_BITS = {torch.bfloat16: 0x7FA5, torch.float32: 0x7FA5A5A5, torch.uint8: 0xA5}    # uint8 has no NaN: the byte 0xA5 stands in
+_INT = {torch.bfloat16: torch.int16, torch.float32: torch.int32, torch.uint8: torch.uint8}
 
 
 # ------------------------------------------------------------------------------------------ guarded buffers
@@ -73,6 +76,8 @@ class Guarded:
 
 
 def _signed(bits, dtype):
+    if dtype == torch.uint8:
+        return bits
     w = 16 if dtype == torch.bfloat16 else 32
     return bits - (1 << w) if bits >= 1 << (w - 1) else bits
 
@@ -728,3 +733,152 @@ def vae_inputs(shape, seed):
     lv = lv.reshape(n, h, w, c)
     mean = torch.where(lv < -30.0, torch.zeros_like(mean), mean)
     return torch.cat([mean, lv], 3).contiguous(), torch.randn(n, c, h, w, generator=gen)
+
+
+# ------------------------------------------------------------------------------------------ control stage: splat
+GRID_ELEMS = 8192 * 256                           # elements one trip of a grid-stride loop covers (8192 workgroups x 256 threads)
+SPLAT_SHAPES = [(1, 1, 1, 1), (3, 5, 1, 13), (2, 3, 17, 1), (3, 7, 7, 9), (2, 5, 24, 40)]          # (n, c, h, w)
+FLOW_FAMILIES = ("smooth", "collapse", "border", "away", "nonfinite")
+METRIC_FAMILIES = ("normal", "wide")
+SPLAT_LARGE = (1, 1, 1450, 1450, "smooth", "normal")      # N H W = 2,102,500 > GRID_ELEMS: every bin kernel and the gather take a
+#                                                           second trip.  Smooth only: the rank pass is quadratic in the collisions.
+SPLAT_CASES = [s + (f, m) for s in SPLAT_SHAPES for f in FLOW_FAMILIES for m in METRIC_FAMILIES] + [SPLAT_LARGE]
+
+
+def splat_label(c):
+    return "x".join(str(v) for v in c[:4]) + f"-{c[4]}-{c[5]}"
+
+
+def splat_flow(family, n, h, w, gen):
+    """fp32 flow [n, 2, h, w] (u = x displacement, v = y displacement) of a family:
+      smooth     sigma = 1.5 px;
+      collapse   every source lands on one fractional interior point (0.37 (w - 1), 0.61 (h - 1));
+      border     landing coordinates exactly -1, 0, w - 1, w and -1, 0, h - 1, h, every pair: the weights are exactly 0 or 1;
+      away       every source leaves the map, except source 0 of each image, which lands exactly on the last pixel;
+      nonfinite  smooth with +inf, -inf, NaN and 1e30 components (every 13th flat element each)."""
+    gy, gx = torch.meshgrid(torch.arange(h, dtype=torch.float32), torch.arange(w, dtype=torch.float32), indexing="ij")
+    if family in ("smooth", "nonfinite"):
+        f = 1.5 * torch.randn(n, 2, h, w, generator=gen)
+        if family == "nonfinite":
+            flat = f.reshape(-1)
+            for off, v in ((0, math.inf), (4, -math.inf), (8, math.nan), (12, 1e30)):
+                flat[off::13] = v
+        return f
+    if family == "collapse":
+        return torch.stack([0.37 * (w - 1) - gx, 0.61 * (h - 1) - gy])[None].repeat(n, 1, 1, 1).contiguous()
+    i = torch.arange(h * w).reshape(h, w)
+    if family == "border":
+        tx = torch.tensor([-1.0, 0.0, w - 1.0, float(w)])[i % 4]
+        ty = torch.tensor([-1.0, 0.0, h - 1.0, float(h)])[(i // 4) % 4]
+        f = torch.stack([tx - gx, ty - gy])[None].repeat(n, 1, 1, 1)
+        f[1::2] = torch.stack([tx - gx, torch.tensor([-1.0, 0.0, h - 1.0, float(h)])[(i // 4 + 1) % 4] - gy])   # odd images: shifted pairs
+        return f.contiguous()
+    assert family == "away", family
+    f = torch.full((n, 2, h, w), float(w + h + 3))
+    f[:, 0, 0, 0], f[:, 1, 0, 0] = w - 1.0, h - 1.0
+    return f
+
+
+def splat_inputs(case, seed):
+    """fp32 (x [n, c, h, w], flow, metric [n, 1, h, w], mask [n, 1, h, w] of zeros and ones) of a SPLAT_CASES entry, on the CPU"""
+    n, c, h, w, family, mfam = case
+    gen = torch.Generator().manual_seed(seed)
+    x = torch.randn(n, c, h, w, generator=gen) + 0.3
+    flow = splat_flow(family, n, h, w, gen)
+    if mfam == "normal":
+        metric = torch.randn(n, 1, h, w, generator=gen)
+    else:                                                  # exp(metric) down to 2e-9: the 1e-7 of the normaliser decides the quotient
+        metric = torch.rand(n, 1, h, w, generator=gen) * 32 - 20
+    mask = (torch.rand(n, 1, h, w, generator=gen) < 0.3).float()
+    return x, flow, metric, mask
+
+
+def splat_seed(i):
+    return 11000 + i
+
+
+# ------------------------------------------------------------------------------------------ control stage: occlusion mask
+# (n, h, w, seed): fa ~ 0.6 N(0, 1), fb = -fa + 0.25 N(0, 1): the forward-backward residual straddles the 0.3 threshold.  Seeds are
+# chosen (tests/test_launch_ref.py asserts it) so that the reference's own band |norm - 0.3| <= delta holds at most 0.5 % of the
+# pixels (none below 200 pixels) and each mask value covers at least 5 %.
+OCCLUSION_CASES = [(2, 24, 40, 0), (3, 7, 9, 0), (3, 1, 13, 0), (2, 33, 5, 0), (1, 64, 64, 0), (3, 128, 96, 0), (2, 17, 1, 0)]
+
+
+def occlusion_inputs(case):
+    n, h, w, seed = case
+    gen = torch.Generator().manual_seed(12000 + seed)
+    fa = 0.6 * torch.randn(n, 2, h, w, generator=gen)
+    fb = -fa + 0.25 * torch.randn(n, 2, h, w, generator=gen)
+    return fa, fb
+
+
+# ------------------------------------------------------------------------------------------ control stage: flow resize, fusion
+FLOW_RESIZE_CASES = [(2, 128, 128, 16, 16), (3, 7, 9, 5, 3), (1, 5, 3, 7, 9), (2, 1, 1, 2, 2), (2, 64, 96, 2, 2)]   # (n, H, W, h, w)
+FLOW_RESIZE_DIVIDE_ONLY = [(1, 9, 7, 1, 1)]                        # the normalising launcher refuses h = 1 or w = 1 (a zero divisor)
+FLOW_DIVISORS = (8.0, 4.0)                                          # div_x != div_y
+
+
+def flow_resize_input(case, seed):
+    """fp32 [n, 6, H, W]; the launch reads planes 2:4"""
+    n, hh, ww, _, _ = case
+    return 3 * torch.randn(n, 6, hh, ww, generator=torch.Generator().manual_seed(13000 + seed)) + 0.5
+
+
+FUSE_CASES = [(3, 7, 5, 9), (1, 1, 1, 1), (2, 320, 8, 8)]          # (n, c, h, w)
+
+
+def fuse_inputs(case, seed):
+    """fp32 (wf, wl [n, c, h, w], cf, cb, of, ob [n, 1, h, w]).  Confidences ~ N(0.3, 1) and, by flat pixel index: both <= 0 (every
+    5th), one negative (every 7th), 1e4 (every 11th).  Occlusion pairs cycle (0,0) (1,0) (0,1) (1,1): sums of exactly 0, 1 and 2."""
+    n, c, h, w = case
+    gen = torch.Generator().manual_seed(14000 + seed)
+    wf, wl = torch.randn(n, c, h, w, generator=gen) + 0.2, torch.randn(n, c, h, w, generator=gen) - 0.1
+    cf, cb = (torch.randn(n * h * w, generator=gen) + 0.3 for _ in range(2))
+    cf[4::5], cb[4::5] = -0.5, 0.0
+    cf[6::7] = -2.0
+    cb[10::11] = 1e4
+    if n * h * w == 1:
+        cf[0], cb[0] = -0.5, 0.0
+    i = torch.arange(n * h * w) + (n * h * w == 1) * 3          # a single pixel: the (1, 1) pair
+    of, ob = (i % 2).float(), ((i // 2) % 2).float()
+    return (wf, wl) + tuple(t.reshape(n, 1, h, w).contiguous() for t in (cf, cb, of, ob))
+
+
+# ------------------------------------------------------------------------------------------ plain elementwise launchers
+SILU_SPECIALS = (104.0, -104.0, 88.7, -88.7, 20.0, -20.0, 1e-30, -1e-30, 0.0, -0.0)
+ELEMENTWISE_CASES = {
+    "silu_f32": [1, 255, 257, GRID_ELEMS + 1],
+    "add_f32": [1, 255, 257, GRID_ELEMS + 1],
+    "lincomb": [(n, t) for n in (1, 255, 257, GRID_ELEMS + 1) for t in (1, 2, 3, 4)],
+    "f32_to_bf16": [1, 255, 257, GRID_ELEMS + 1],
+    "add_bf16": [8, 2056, 8 * (GRID_ELEMS + 1)],
+    "nchw_f32_to_nhwc_bf16": [(3, 5, 7, 9), (1, 1, 1, 1), (2, 320, 3, 2), (1, 4, 725, 725)],          # (n, c, h, w)
+    "nhwc_bf16_to_nchw_f32": [(3, 5, 7, 9), (1, 1, 1, 1), (2, 320, 3, 2), (1, 4, 725, 725)],
+    "nhwc_f32_to_nchw_f32": [(3, 5, 7, 9), (1, 1, 1, 1), (2, 320, 3, 2), (1, 4, 725, 725)],
+    "transpose_bf16": [(3, 33, 31), (1, 1, 1), (2, 77, 40)],                                           # (b, r, c)
+    "freeu_lowfreq": [(2, 2, 2, 8), (2, 5, 16, 24)],                                                    # (n, h, w, c)
+    "freeu_backbone": [(3, 5, 16), (2, 7, 80)],                                                         # (n, pixels, c)
+    "timestep_embedding": [(3, 320, 2), (1, 6, 0)],                                                     # (n, dim, step index into 4)
+    "embed_tokens": [(2, 5, 8, 11), (3, 77, 1024, 49), (1, 77, 1032, 49)],                              # (b, t, c, vocab)
+    "postprocess_image": [(2, 3, 5, 7, xs, f32, u8) for xs in (3, 4) for f32, u8 in ((True, False), (False, True), (True, True))],
+}
+LINCOMB_COEFS = (0.7, -1.3, 0.21, 3.7)
+TIMESTEP_TABLE = (981.0, 501.0, 21.0, 1.0)
+
+
+def elementwise_input(n, seed, specials=()):
+    x = 3 * torch.randn(n, generator=torch.Generator().manual_seed(15000 + seed))
+    k = min(n, len(specials))
+    x[:k] = torch.tensor(specials[:k])
+    if n > len(specials) and specials:
+        x[-len(specials):] = torch.tensor(specials)        # ... and at the tail (the second trip of the large case)
+    return x
+
+
+def postprocess_input(n, c, h, w, xs):
+    """fp32 [n, h, w, xs] whose first c channels are the launch's input: ~ N(0, 1) with values below -1, above 1 and exactly +-1"""
+    x = torch.randn(n, h, w, xs, generator=torch.Generator().manual_seed(16000 + xs))
+    flat = x.reshape(-1)
+    for off, v in ((0, -1.0), (1, 1.0), (2, -1.5), (3, 2.0), (4, -1.0000001), (5, 0.99999994)):
+        flat[off::17] = v
+    return x

@@ -51,6 +51,7 @@ class LaunchShadow:
         self.prefix = prefix
         self._last_route = None
         self._stack = None
+        self.band = {}             # occlusion masks: (n, h, w) -> [launches, largest share of pixels inside the reference's own band]
 
     # ---------------------------------------------------------------- bookkeeping
     def _note(self, key, verdict, what):
@@ -69,6 +70,8 @@ class LaunchShadow:
         if self.record is not None:
             for key, (n, worst) in sorted(self.stats.items(), key=lambda kv: str(kv[0])):
                 self.record(f"{self.prefix}[{'/'.join(str(k) for k in key)}]", f"launches={n} worst_err_over_tol={worst:.4f}")
+            for shape, (n, share) in sorted(self.band.items()):
+                self.record(f"{self.prefix}[occlusion_mask/band/{'x'.join(str(v) for v in shape)}]", f"launches={n} band_share={share:.6f}")
         return self.stats
 
     def routes(self):
@@ -247,7 +250,85 @@ class LaunchShadow:
                           ("freeu_lowfreq", lowfreq), ("timestep_embedding", temb)):
             mp.set(ops, name, self._simple(name, getattr(ops, name), ref))
         mp.set(ops, "group_norm_ab", self._gn_ab(ops.group_norm_ab))
+
+        # ------------------------------------------------ control stage, layout conversions, loop entry / exit (fp32 and exact)
+        def sub(y, r, s):
+            """full maps up to 2^22 elements; above, the usual row sample over the map's rows of W elements"""
+            if r.numel() <= 1 << 22:
+                return y, r, s
+            w = r.shape[-1]
+            rows = L.sample_rows(r.numel() // w).to(r.device)
+            return tuple(t.reshape(-1, w)[rows] for t in (y, r, s))
+
+        def splat_soft(a, kw, y):
+            r, s, _ = L.splat_soft_ref(a[0], a[1], a[2], kw.get("mask", a[3] if len(a) > 3 else None))
+            return sub(y, r, s) + (y.dtype,)
+
+        def flow_norm(a, kw, y):
+            h, w = a[1], a[2]
+            return sub(y, *L.flow_resize_ref(a[0], h, w, (w - 1) / 2.0, (h - 1) / 2.0)) + (y.dtype,)
+
+        def flow_div(a, kw, y):
+            return sub(y, *L.flow_resize_ref(*a[:5])) + (y.dtype,)
+
+        def fuse(a, kw, y):
+            of = kw.get("of", a[4] if len(a) > 4 else None)
+            ob = kw.get("ob", a[5] if len(a) > 5 else None)
+            return sub(y, *L.fuse_warped_ref(*a[:4], of, ob)) + (y.dtype,)
+
+        def add_f32(a, kw, y):
+            return sub(y, *L.add_f32_ref(a[0], a[1])) + (y.dtype,)
+
+        def exact(ref):
+            def fn(a, kw, y):
+                r = ref(a[0]).to(L.F64)
+                return sub(y, r, torch.zeros_like(r)) + (torch.float32,)        # exact: e_out 2^-20 of |r| only, far below one bf16 ulp
+            return fn
+
+        def to_model_input(a, kw, y):
+            mul = kw.get("mul", a[1] if len(a) > 1 else 1.0)
+            rep = kw.get("rep", a[2] if len(a) > 2 else 1)
+            return sub(y, *L.latents_to_model_input_ref(a[0], mul, rep)) + (y.dtype,)
+
+        for name, ref in (("splat_soft", splat_soft), ("flow_resize_normalize", flow_norm), ("flow_resize_divide", flow_div),
+                          ("fuse_warped", fuse), ("add_f32", add_f32), ("latents_to_model_input", to_model_input),
+                          ("nchw_f32_to_nhwc_bf16", exact(L.nchw_f32_to_nhwc_bf16_ref)),
+                          ("nhwc_bf16_to_nchw_f32", exact(L.nhwc_to_nchw_f32_ref)), ("nhwc_f32_to_nchw_f32", exact(L.nhwc_to_nchw_f32_ref))):
+            mp.set(ops, name, self._simple(name, getattr(ops, name), ref))
+        mp.set(ops, "occlusion_mask", self._occlusion(ops.occlusion_mask))
+        mp.set(ops, "postprocess_image", self._postprocess(ops.postprocess_image))
         return self
+
+    def _occlusion(self, real):
+        def fn(flow_a, flow_b):
+            self.calls += 1
+            y = real(flow_a, flow_b)
+            torch.cuda.synchronize()
+            v = L.check_occlusion_mask(y, L.occlusion_mask_ref(flow_a, flow_b))
+            n, _, h, w = y.shape
+            b = self.band.setdefault((n, h, w), [0, 0.0])
+            b[0], b[1] = b[0] + 1, max(b[1], v["band"])
+            # the band condition of the edge cases holds for production masks too: at most 0.5 % of the pixels, none below 200 pixels
+            wide = v["band"] > 0.005 or (n * h * w < 200 and v["band"] > 0.0)
+            bad = v["flips"] + v["not_binary"] + int(wide)
+            self._note(("occlusion_mask", 0, False), dict(ratio=float(bad), ok=bad == 0, worst=(), err=float(v["flips"]), tol=0.0, rms=v["band"]),
+                       f"occlusion_mask {tuple(y.shape)}: {v['flips']} flips outside the band, {v['not_binary']} values not 0 / 1, band share {v['band']:.5f}")
+            return y
+        return fn
+
+    def _postprocess(self, real):
+        def fn(x, want_u8=False):
+            self.calls += 1
+            o32, o8 = real(x, want_u8=want_u8)
+            torch.cuda.synchronize()
+            r, s = L.postprocess_image_ref(x)
+            self._note(("postprocess_image", 0, False), L.check(o32, r, s, o32.dtype), f"postprocess_image {tuple(o32.shape)}")
+            if o8 is not None:
+                wrong = int((o8 != torch.round(o32 * 255.0).to(torch.uint8).permute(0, 2, 3, 1)).sum())
+                self._note(("postprocess_image", "u8", False), dict(ratio=float(wrong), ok=wrong == 0, worst=(), err=float(wrong), tol=0.0, rms=0.0),
+                           f"postprocess_image uint8: {wrong} values are not round-half-even(255 o32)")
+            return o32, o8
+        return fn
 
     def _gn_ab(self, real):
         def fn(x, gamma, beta, groups, eps, x2=None):

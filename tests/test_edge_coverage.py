@@ -376,3 +376,114 @@ def test_f32_conv_bound_passes_torch_and_rejects_faults(i):
         for name, (fx, fw, fb) in faults.items():
             bad = flat(act(F.conv2d(fx, fw, fb, stride=c.stride, padding=1)))
             assert not L.check(bad, r, s, torch.float32)["ok"], (c.label(), silu, name)
+
+
+# ------------------------------------------------------------------------------------------ control stage and elementwise tables
+CONTROL_LAUNCHERS = ("splat_soft", "splat_sum", "occlusion_mask", "flow_resize_normalize", "flow_resize_divide", "fuse_warped")
+ELEMENTWISE_LAUNCHERS = ("silu_f32", "add_f32", "lincomb", "f32_to_bf16", "add_bf16", "nchw_f32_to_nhwc_bf16", "nhwc_bf16_to_nchw_f32",
+                         "nhwc_f32_to_nchw_f32", "transpose_bf16", "freeu_lowfreq", "freeu_backbone", "timestep_embedding",
+                         "embed_tokens", "postprocess_image")
+GRID_STRIDE = ("silu_f32", "add_f32", "lincomb", "f32_to_bf16", "add_bf16", "nchw_f32_to_nhwc_bf16", "nhwc_bf16_to_nchw_f32",
+               "nhwc_f32_to_nchw_f32")                      # the elementwise kernels that loop over a capped grid
+
+
+def _elems(name, case):
+    if name == "lincomb":
+        return case[0]
+    if name == "add_bf16":
+        return case // 8                                     # eight elements per thread
+    return case if isinstance(case, int) else math.prod(case)
+
+
+def test_control_tables_span_the_shapes_and_families():
+    """the tables still hold: H = 1 and W = 1, h != w, an odd batch, every flow and metric family on every shape, one splat past a
+    single grid (smooth only, and nothing else that large); the occlusion, resize and fusion tables square and non-square"""
+    small = [c for c in E.SPLAT_CASES if c != E.SPLAT_LARGE]
+    assert E.SPLAT_LARGE in E.SPLAT_CASES
+    n, c, h, w, fam, _ = E.SPLAT_LARGE
+    assert n * h * w > E.GRID_ELEMS and fam == "smooth" and E.GRID_ELEMS == 8192 * 256
+    assert all(c[0] * c[2] * c[3] <= 4096 for c in small)                                  # collisions stay cheap everywhere else
+    for fam in E.FLOW_FAMILIES:
+        for mf in E.METRIC_FAMILIES:
+            cs = [c for c in small if c[4] == fam and c[5] == mf]
+            assert any(c[2] == 1 for c in cs) and any(c[3] == 1 for c in cs) and any(c[2] == c[3] == 1 for c in cs), (fam, mf)
+            assert any(c[2] != c[3] and c[2] > 1 and c[3] > 1 for c in cs) and any(c[0] == 3 for c in cs) and any(c[0] % 2 == 0 for c in cs)
+            assert any(c[0] * c[1] * c[2] * c[3] > 256 for c in cs), (fam, mf)             # more than one workgroup
+    occ = E.OCCLUSION_CASES
+    assert any(h == w for _, h, w, _ in occ) and any(h == 1 for _, h, w, _ in occ) and any(w == 1 for _, h, w, _ in occ)
+    assert any(h > w > 1 for _, h, w, _ in occ) and any(w > h > 1 for _, h, w, _ in occ) and any(n == 3 for n, _, _, _ in occ)
+    assert all(n * h * w <= E.GRID_ELEMS for n, h, w, _ in occ)
+    fr = E.FLOW_RESIZE_CASES
+    assert any(H != W for _, H, W, _, _ in fr) and any(h != w for _, _, _, h, w in fr) and any(n == 3 for n, *_ in fr)
+    assert any(H == W == 1 for _, H, W, _, _ in fr) and any(h > H for _, H, W, h, w in fr) and any(h < H for _, H, W, h, w in fr)
+    assert all(h > 1 and w > 1 for _, _, _, h, w in fr) and any(h == 1 and w == 1 for _, _, _, h, w in E.FLOW_RESIZE_DIVIDE_ONLY)
+    assert E.FLOW_DIVISORS[0] != E.FLOW_DIVISORS[1]
+    fu = E.FUSE_CASES
+    assert any(h != w for _, _, h, w in fu) and any(h * w == 1 for _, _, h, w in fu) and any(n == 3 for n, *_ in fu)
+    assert any(c == 320 for _, c, _, _ in fu)                                              # the production channel count
+
+
+def test_elementwise_table_names_every_launcher_and_passes_one_grid():
+    assert set(E.ELEMENTWISE_CASES) == set(ELEMENTWISE_LAUNCHERS)
+    for name in GRID_STRIDE:
+        sizes = [_elems(name, c) for c in E.ELEMENTWISE_CASES[name]]
+        assert max(sizes) > E.GRID_ELEMS, name                                             # the second trip of the loop
+        assert sum(s > E.GRID_ELEMS for s in sizes) <= (4 if name == "lincomb" else 1) and min(sizes) == 1, name   # large cases stay few
+    assert {t for _, t in E.ELEMENTWISE_CASES["lincomb"]} == {1, 2, 3, 4}
+    assert {t for n, t in E.ELEMENTWISE_CASES["lincomb"] if n > E.GRID_ELEMS} == {1, 2, 3, 4}
+    for n in (1, 255, 257):
+        for name in ("silu_f32", "add_f32", "f32_to_bf16"):
+            assert n in E.ELEMENTWISE_CASES[name], (name, n)
+    assert {-104.0, 104.0, 88.7, -88.7, 20.0, -20.0, 1e-30, -1e-30, 0.0} <= set(E.SILU_SPECIALS) and len(E.SILU_SPECIALS) == 10
+    for name in ("nchw_f32_to_nhwc_bf16", "nhwc_bf16_to_nchw_f32", "nhwc_f32_to_nchw_f32"):
+        cs = E.ELEMENTWISE_CASES[name]
+        assert any(h != w for _, _, h, w in cs) and any(n == 3 for n, *_ in cs) and (1, 1, 1, 1) in cs
+    assert any(r % 32 and c % 32 for _, r, c in E.ELEMENTWISE_CASES["transpose_bf16"])
+    assert any(h != w for _, h, w, _ in E.ELEMENTWISE_CASES["freeu_lowfreq"])
+    assert {c for _, _, c in E.ELEMENTWISE_CASES["freeu_backbone"]} == {16, 80}
+    assert any(s > 0 for _, _, s in E.ELEMENTWISE_CASES["timestep_embedding"]) and len(E.TIMESTEP_TABLE) == 4
+    emb = E.ELEMENTWISE_CASES["embed_tokens"]
+    assert any(c % (128 * 8) for _, _, c, _ in emb) and any(c > 128 * 8 for _, _, c, _ in emb) and any(b == 3 for b, *_ in emb)
+    pp = E.ELEMENTWISE_CASES["postprocess_image"]
+    assert {(xs, f, u) for *_, xs, f, u in pp} == {(xs, f, u) for xs in (3, 4) for f, u in ((True, False), (False, True), (True, True))}
+    x = E.postprocess_input(2, 3, 5, 7, 4)[..., :3]
+    assert bool((x < -1).any()) and bool((x > 1).any()) and bool((x == 1).any()) and bool((x == -1).any())
+
+
+def _lib_calls(path):
+    """C names that are the literal first argument of a `lib.call(...)` expression in a test module (from its syntax tree: a name
+    in a comment or in an unused string does not count)"""
+    import ast
+    names = set()
+    for node in ast.walk(ast.parse(open(path).read())):
+        if isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr == "call" and \
+                isinstance(node.func.value, ast.Name) and node.func.value.id == "lib" and node.args and \
+                isinstance(node.args[0], ast.Constant) and isinstance(node.args[0].value, str):
+            names.add(node.args[0].value)
+    return names
+
+
+def test_every_control_and_elementwise_launcher_has_an_edge_test():
+    """tests/test_gpu_edges.py holds a `lib.call` of every one of them by its C name"""
+    from diffcodec_amd import lib as l
+    called = _lib_calls(os.path.join(ROOT, "tests", "test_gpu_edges.py"))
+    c_name = {"splat_soft": "dc_splat_soft_f32", "splat_sum": "dc_splat_sum_f32", "occlusion_mask": "dc_occlusion_mask_f32",
+              "flow_resize_normalize": "dc_flow_resize_normalize_f32", "flow_resize_divide": "dc_flow_resize_divide_f32",
+              "fuse_warped": "dc_fuse_warped_f32", "lincomb": "dc_lincomb4_f32", "freeu_lowfreq": "dc_freeu_lowfreq_nhwc_bf16",
+              "freeu_backbone": "dc_freeu_backbone_nhwc_bf16", "timestep_embedding": "dc_timestep_embedding_f32",
+              "embed_tokens": "dc_embed_tokens_bf16", "postprocess_image": "dc_postprocess_image"}
+    for name in CONTROL_LAUNCHERS + ELEMENTWISE_LAUNCHERS:
+        cn = c_name.get(name, "dc_" + name)
+        assert cn in l.SIGNATURES, cn
+        assert cn in called, f"{cn}: no lib.call in tests/test_gpu_edges.py"
+
+
+def test_uint8_guard_flags_writes_outside_the_view():
+    g = E.Guarded((2, 5, 3), torch.uint8, "cpu")
+    assert g.bad() == [] and int((g.view == 0xA5).all())
+    g.view.copy_(torch.arange(30, dtype=torch.uint8).reshape(2, 5, 3))
+    assert g.bad() == []
+    g.base[g.guard + 30] = 7
+    assert g.bad() and g.bad()[0][0] == "after"
+    with pytest.raises(AssertionError):
+        g.assert_intact("u8")

@@ -1,5 +1,6 @@
 """GPU: every case of tests/edge_cases.py — each conv / linear, fp32 extractor conv and attention kernel instance the dispatchers can
-reach, the normalisation kernels at their template and chunking edges, and the fused loop's state kernels — launched on guarded operands and outputs, its route asserted first,
+reach, the normalisation kernels at their template and chunking edges, the fused loop's state kernels, the control stage (splat,
+occlusion mask, flow resize, fusion) and the plain elementwise launchers — launched on guarded operands and outputs, its route asserted first,
 its output held to the fp64 reference of oracle/launch_ref.py with L.check, its guards checked bit for bit, and a second launch
 into a second guarded output required to be bitwise equal.  Worst err/tol per instance goes to `record`."""
 import math
@@ -43,6 +44,8 @@ def _g(shape, dtype, data=None, pitch=None):
 
 
 def _same_bits(a, b):
+    if a.dtype == torch.uint8:
+        return torch.equal(a, b)
     it = torch.int16 if a.dtype == BF else torch.int32
     return torch.equal(a.contiguous().view(it), b.contiguous().view(it))
 
@@ -558,3 +561,377 @@ def test_softmax_rows_edge(ops, record, rows, cols):
     assert outs[0].unwritten() == 0 and _same_bits(outs[0].view, outs[1].view)
     r, s = L.softmax_rows_ref(sg.view, 0.125, torch.arange(rows))
     _note(record, ("softmax_rows",), L.check(outs[0].view, r, s, BF), f"softmax_rows {rows}x{cols}")
+
+
+# ------------------------------------------------------------------------------------------ control stage
+def _st():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _twice(launch, shape, dtype, operands, what):
+    """two launches into two guarded outputs: guards intact, every element written, bitwise equal -> the first output's Guarded"""
+    outs = []
+    for rep in range(2):
+        go = _g(shape, dtype)
+        launch(go.view)
+        torch.cuda.synchronize()
+        outs.append(go)
+    for k, g in enumerate(list(operands) + outs):
+        g.assert_intact(f"{what} buffer {k}")
+    if dtype != torch.uint8:
+        assert outs[0].unwritten() == 0, f"{what}: {outs[0].unwritten()} output elements never written"
+    assert _same_bits(outs[0].view, outs[1].view), f"{what}: launch-to-launch difference"
+    return outs[0]
+
+
+def _unchanged(g, t, what):
+    assert _same_bits(g.view, t.to(DEV)), f"{what}: an operand was written"
+
+
+def _splat_ws(lib, n, h, w):
+    """the workspace as a guarded buffer of exactly dc_splat_ws_bytes, interior zeroed (never the NaN pattern: an unwritten entry read
+    as an index must not become an out-of-range access)"""
+    nbytes = int(lib.load().dc_splat_ws_bytes(n, h, w))
+    assert nbytes > 0 and nbytes % 4 == 0
+    ws = E.Guarded((nbytes,), torch.uint8, DEV)
+    ws.view.zero_()
+    return ws
+
+
+@pytest.mark.parametrize("i", range(len(E.SPLAT_CASES)), ids=[E.splat_label(c) for c in E.SPLAT_CASES])
+def test_splat_soft_edge(ops, record, i):
+    """dc_splat_soft_f32 with and without the mask and dc_splat_sum_f32 (splat_sum: bit for bit the C oracle) on guarded operands, a
+    guarded workspace of exactly dc_splat_ws_bytes — zeroed for the first launch, left behind by a launch on another flow field
+    for the second — and guarded outputs."""
+    from diffcodec_amd import lib
+    from oracle import splat as OS
+    case = E.SPLAT_CASES[i]
+    n, c, h, w = case[:4]
+    what = E.splat_label(case)
+    x, flow, metric, mask = E.splat_inputs(case, E.splat_seed(i))
+    other = E.splat_flow("smooth", n, h, w, torch.Generator().manual_seed(77 + i))
+    gx, gf, gm, gk, gother = (_g(tuple(t.shape), F32, t.to(DEV)) for t in (x, flow, metric, mask, other))
+    ws = _splat_ws(lib, n, h, w)
+    ops_ = [gx, gf, gm, gk, gother, ws]
+
+    def soft(out, mk, fl=gf):
+        lib.call("dc_splat_soft_f32", gx.view.data_ptr(), fl.view.data_ptr(), gm.view.data_ptr(), mk.view.data_ptr() if mk else 0,
+                 out.data_ptr(), ws.view.data_ptr(), n, c, h, w, _st())
+
+    outs = []
+    for rep in range(2):
+        go = _g((n, c, h, w), F32)
+        soft(go.view, gk)
+        torch.cuda.synchronize()
+        outs.append(go)
+        if rep == 0:                                    # leave the workspace as a launch on another flow field leaves it
+            scratch = _g((n, c, h, w), F32)
+            soft(scratch.view, None, gother)
+            torch.cuda.synchronize()
+            scratch.assert_intact(f"{what} scratch out")
+    gnm = _g((n, c, h, w), F32)
+    soft(gnm.view, None)
+    gsum = _g((n, c, h, w), F32)
+    lib.call("dc_splat_sum_f32", gx.view.data_ptr(), gf.view.data_ptr(), gsum.view.data_ptr(), ws.view.data_ptr(), n, c, h, w, _st())
+    torch.cuda.synchronize()
+    for k, g in enumerate(ops_ + outs + [gnm, gsum]):
+        g.assert_intact(f"{what} buffer {k}")
+    for g, t in ((gx, x), (gf, flow), (gm, metric), (gk, mask)):
+        _unchanged(g, t, what)
+    for g in outs + [gnm, gsum]:
+        assert g.unwritten() == 0, f"{what}: {g.unwritten()} output elements never written"
+        assert bool(torch.isfinite(g.view).all()), f"{what}: non-finite output"
+    assert _same_bits(outs[0].view, outs[1].view), f"{what}: the output depends on what the workspace held"
+    r, s, _ = L.splat_soft_ref(gx.view, gf.view, gm.view, gk.view)
+    _note(record, ("splat_soft", "mask"), L.check(outs[0].view, r, s, F32), what)
+    r, s, _ = L.splat_soft_ref(gx.view, gf.view, gm.view)
+    _note(record, ("splat_soft",), L.check(gnm.view, r, s, F32), what)
+    r, s, _ = L.splat_sum_ref(gx.view, gf.view)
+    _note(record, ("splat_sum",), L.check(gsum.view, r, s, F32), what)
+    assert torch.equal(gsum.view.cpu(), OS.splat_sum(x, flow)), f"{what}: splat_sum is not bit for bit the C oracle"
+
+
+@pytest.mark.parametrize("case", E.OCCLUSION_CASES, ids=[f"{c[0]}x{c[1]}x{c[2]}" for c in E.OCCLUSION_CASES])
+def test_occlusion_mask_edge(ops, record, case):
+    from diffcodec_amd import lib
+    n, h, w, _ = case
+    what = f"occlusion_mask {n}x{h}x{w}"
+    fa, fb = E.occlusion_inputs(case)
+    other = E.splat_flow("smooth", n, h, w, torch.Generator().manual_seed(5))
+    ga, gb, gother = (_g(tuple(t.shape), F32, t.to(DEV)) for t in (fa, fb, other))
+    ws = _splat_ws(lib, n, h, w)
+
+    def launch(out, b=gb):
+        lib.call("dc_occlusion_mask_f32", ga.view.data_ptr(), b.view.data_ptr(), out.data_ptr(), ws.view.data_ptr(), n, h, w, _st())
+
+    outs = []
+    for rep in range(2):
+        go = _g((n, 1, h, w), F32)
+        launch(go.view)
+        torch.cuda.synchronize()
+        outs.append(go)
+        if rep == 0:
+            scratch = _g((n, 1, h, w), F32)
+            launch(scratch.view, gother)
+            torch.cuda.synchronize()
+            scratch.assert_intact(f"{what} scratch out")
+    for k, g in enumerate([ga, gb, gother, ws] + outs):
+        g.assert_intact(f"{what} buffer {k}")
+    _unchanged(ga, fa, what)
+    _unchanged(gb, fb, what)
+    assert outs[0].unwritten() == 0 and _same_bits(outs[0].view, outs[1].view), what
+    v = L.check_occlusion_mask(outs[0].view, L.occlusion_mask_ref(ga.view, gb.view))
+    record("edge[occlusion_mask]", f"{what} band_share={v['band']:.5f} flips_outside={v['flips']} ones={v['ones']:.3f}")
+    assert v["ok"], (what, v)
+
+
+def _flow_cases():
+    return [(c, False) for c in E.FLOW_RESIZE_CASES] + [(c, True) for c in E.FLOW_RESIZE_CASES + E.FLOW_RESIZE_DIVIDE_ONLY]
+
+
+@pytest.mark.parametrize("case,divide", _flow_cases(), ids=[("divide-" if d else "normalize-") + "x".join(map(str, c)) for c, d in _flow_cases()])
+def test_flow_resize_edge(ops, record, case, divide):
+    """dc_flow_resize_normalize_f32 / dc_flow_resize_divide_f32 reading planes 2:4 of a guarded [n, 6, H, W] tensor whose other planes
+    hold the NaN pattern"""
+    from diffcodec_amd import lib
+    n, hh, ww, h, w = case
+    name = "flow_resize_divide" if divide else "flow_resize_normalize"
+    what = f"{name} {case}"
+    full = E.flow_resize_input(case, 0)
+    g6 = E.Guarded((n, 6, hh, ww), F32, DEV)
+    src = g6.view[:, 2:4]
+    src.copy_(full[:, 2:4].to(DEV))
+    dx, dy = E.FLOW_DIVISORS if divide else ((w - 1) / 2.0, (h - 1) / 2.0)
+
+    def launch(out):
+        if divide:
+            lib.call("dc_flow_resize_divide_f32", src.data_ptr(), src.stride(0), out.data_ptr(), n, hh, ww, h, w, dx, dy, _st())
+        else:
+            lib.call("dc_flow_resize_normalize_f32", src.data_ptr(), src.stride(0), out.data_ptr(), n, hh, ww, h, w, _st())
+
+    go = _twice(launch, (n, 2, h, w), F32, [g6], what)
+    pat = E._signed(E.NAN_BITS[F32], F32)
+    assert bool((g6.view[:, [0, 1, 4, 5]].contiguous().view(torch.int32) == pat).all()), f"{what}: a neighbouring plane was written"
+    assert torch.equal(src.cpu(), full[:, 2:4]), f"{what}: the source was written"
+    assert bool(torch.isfinite(go.view).all()), f"{what}: non-finite output (a poisoned plane was read)"
+    r, s = L.flow_resize_ref(src, h, w, dx, dy)
+    _note(record, (name,), L.check(go.view, r, s, F32), what)
+    wrapped = ops.flow_resize_divide(src, h, w, dx, dy) if divide else ops.flow_resize_normalize(src, h, w)
+    assert torch.equal(wrapped, go.view), f"{what}: the ops wrapper launches something else"
+
+
+@pytest.mark.parametrize("occ", [True, False], ids=["holes", "noholes"])
+@pytest.mark.parametrize("i", range(len(E.FUSE_CASES)), ids=["x".join(map(str, c)) for c in E.FUSE_CASES])
+def test_fuse_warped_edge(ops, record, i, occ):
+    from diffcodec_amd import lib
+    n, c, h, w = E.FUSE_CASES[i]
+    what = f"fuse_warped {E.FUSE_CASES[i]} occ={int(occ)}"
+    ts = E.fuse_inputs(E.FUSE_CASES[i], i)
+    gs = [_g(tuple(t.shape), F32, t.to(DEV)) for t in ts]
+    p = [g.view.data_ptr() for g in gs]
+
+    def launch(out):
+        lib.call("dc_fuse_warped_f32", p[0], p[1], p[2], p[3], p[4] if occ else 0, p[5] if occ else 0, out.data_ptr(), n, c, h, w, _st())
+
+    go = _twice(launch, (n, c, h, w), F32, gs, what)
+    for g, t in zip(gs, ts):
+        _unchanged(g, t, what)
+    assert bool(torch.isfinite(go.view).all()), what
+    r, s = L.fuse_warped_ref(*(g.view for g in gs[:4]), *((gs[4].view, gs[5].view) if occ else ()))
+    _note(record, ("fuse_warped", "holes" if occ else "noholes"), L.check(go.view, r, s, F32), what)
+    assert torch.equal(ops.fuse_warped(*(g.view for g in gs[:4]), *((gs[4].view, gs[5].view) if occ else ())), go.view)
+
+
+# ------------------------------------------------------------------------------------------ plain elementwise launchers
+@pytest.mark.parametrize("n", E.ELEMENTWISE_CASES["silu_f32"])
+def test_silu_f32_edge(ops, record, n):
+    from diffcodec_amd import lib
+    x = E.elementwise_input(n, n, E.SILU_SPECIALS)
+    gx = _g((n,), F32, x.to(DEV))
+    go = _twice(lambda o: lib.call("dc_silu_f32", gx.view.data_ptr(), o.data_ptr(), n, _st()), (n,), F32, [gx], f"silu_f32 {n}")
+    _unchanged(gx, x, "silu_f32")
+    assert bool(torch.isfinite(go.view).all()), f"silu_f32 {n}: non-finite output"
+    r, s = L.silu_f32_ref(gx.view)
+    _note(record, ("silu_f32",), L.check(go.view, r, s, F32), f"silu_f32 {n}")
+    assert torch.equal(ops.silu_f32(gx.view), go.view)
+
+
+@pytest.mark.parametrize("n", E.ELEMENTWISE_CASES["add_f32"])
+def test_add_f32_edge(ops, record, n):
+    from diffcodec_amd import lib
+    a, b = E.elementwise_input(n, 1), E.elementwise_input(n, 2)
+    ga, gb = _g((n,), F32, a.to(DEV)), _g((n,), F32, b.to(DEV))
+    go = _twice(lambda o: lib.call("dc_add_f32", ga.view.data_ptr(), gb.view.data_ptr(), o.data_ptr(), n, _st()), (n,), F32, [ga, gb],
+                f"add_f32 {n}")
+    r, s = L.add_f32_ref(ga.view, gb.view)
+    _note(record, ("add_f32",), L.check(go.view, r, s, F32), f"add_f32 {n}")
+    assert torch.equal(go.view, ga.view + gb.view)                      # one IEEE sum
+    assert torch.equal(ops.add_f32(ga.view, gb.view), go.view)
+
+
+@pytest.mark.parametrize("n,terms", E.ELEMENTWISE_CASES["lincomb"])
+def test_lincomb_edge(ops, record, n, terms):
+    from diffcodec_amd import lib
+    ts = [E.elementwise_input(n, 10 + j) for j in range(terms)]
+    gs = [_g((n,), F32, t.to(DEV)) for t in ts]
+    p = [g.view.data_ptr() for g in gs] + [0] * (4 - terms)
+    cf = list(E.LINCOMB_COEFS[:terms]) + [0.0] * (4 - terms)
+    go = _twice(lambda o: lib.call("dc_lincomb4_f32", *p, *cf, o.data_ptr(), n, _st()), (n,), F32, gs, f"lincomb {n}x{terms}")
+    r, s = L.lincomb_ref([(cf[j], gs[j].view) for j in range(terms)])
+    _note(record, ("lincomb", terms), L.check(go.view, r, s, F32), f"lincomb {n}x{terms}")
+    assert torch.equal(ops.lincomb([(cf[j], gs[j].view) for j in range(terms)]), go.view)
+
+
+@pytest.mark.parametrize("n", E.ELEMENTWISE_CASES["f32_to_bf16"])
+def test_f32_to_bf16_edge(ops, record, n):
+    from diffcodec_amd import lib
+    x = E.elementwise_input(n, 3, (1.00390625, 1.01171875, -1.00390625, 3.0e38, 1e-30, -0.0))     # ties to even, both ways; near overflow
+    gx = _g((n,), F32, x.to(DEV))
+    go = _twice(lambda o: lib.call("dc_f32_to_bf16", gx.view.data_ptr(), o.data_ptr(), n, _st()), (n,), BF, [gx], f"f32_to_bf16 {n}")
+    assert _same_bits(go.view, gx.view.to(BF)), f"f32_to_bf16 {n}: not one round-to-nearest-even"
+    r, s = L.f32_to_bf16_ref(gx.view[:, None], torch.arange(n))
+    _note(record, ("f32_to_bf16",), L.check(go.view[:, None], r, s, BF), f"f32_to_bf16 {n}")
+
+
+@pytest.mark.parametrize("n", E.ELEMENTWISE_CASES["add_bf16"])
+def test_add_bf16_edge(ops, record, n):
+    from diffcodec_amd import lib
+    a, b = E.elementwise_input(n, 4).to(BF), E.elementwise_input(n, 5).to(BF)
+    ga, gb = _g((n,), BF, a.to(DEV)), _g((n,), BF, b.to(DEV))
+    go = _twice(lambda o: lib.call("dc_add_bf16", ga.view.data_ptr(), gb.view.data_ptr(), o.data_ptr(), n, _st()), (n,), BF, [ga, gb],
+                f"add_bf16 {n}")
+    assert _same_bits(go.view, (ga.view.float() + gb.view.float()).to(BF)), f"add_bf16 {n}: not the fp32 sum rounded once"
+    r, s = L.add_ref(ga.view.reshape(-1, 8), gb.view.reshape(-1, 8), torch.arange(n // 8))
+    _note(record, ("add_bf16",), L.check(go.view.reshape(-1, 8), r, s, BF), f"add_bf16 {n}")
+
+
+@pytest.mark.parametrize("name", ["nchw_f32_to_nhwc_bf16", "nhwc_bf16_to_nchw_f32", "nhwc_f32_to_nchw_f32"])
+@pytest.mark.parametrize("shape", E.ELEMENTWISE_CASES["nchw_f32_to_nhwc_bf16"], ids=lambda s: "x".join(map(str, s)))
+def test_layout_conversion_edge(ops, record, name, shape):
+    """nchw_f32_to_nhwc_bf16 / nhwc_bf16_to_nchw_f32 / nhwc_f32_to_nchw_f32: exact (a permutation, at most one rounding to bf16)"""
+    from diffcodec_amd import lib
+    assert shape in E.ELEMENTWISE_CASES[name]
+    n, c, h, w = shape
+    x = torch.randn(n, c, h, w, generator=torch.Generator().manual_seed(17000 + c))
+    if name == "nchw_f32_to_nhwc_bf16":
+        gx, oshape, odt = _g(shape, F32, x.to(DEV)), (n, h, w, c), BF
+        want = L.nchw_f32_to_nhwc_bf16_ref(gx.view)
+    else:
+        idt = BF if name == "nhwc_bf16_to_nchw_f32" else F32
+        gx, oshape, odt = _g((n, h, w, c), idt, x.permute(0, 2, 3, 1).to(DEV)), shape, F32
+        want = L.nhwc_to_nchw_f32_ref(gx.view)
+    args = lambda o: (gx.view.data_ptr(), o.data_ptr(), n, c, h, w, _st())
+    launch = {"nchw_f32_to_nhwc_bf16": lambda o: lib.call("dc_nchw_f32_to_nhwc_bf16", *args(o)),
+              "nhwc_bf16_to_nchw_f32": lambda o: lib.call("dc_nhwc_bf16_to_nchw_f32", *args(o)),
+              "nhwc_f32_to_nchw_f32": lambda o: lib.call("dc_nhwc_f32_to_nchw_f32", *args(o))}[name]
+    go = _twice(launch, oshape, odt, [gx], f"{name} {shape}")
+    assert _same_bits(go.view, want.contiguous()), f"{name} {shape}: not the exact permutation"
+    assert _same_bits(getattr(ops, name)(gx.view), go.view)
+    record(f"edge[{name}]", "exact")
+
+
+@pytest.mark.parametrize("shape", E.ELEMENTWISE_CASES["transpose_bf16"], ids=lambda s: "x".join(map(str, s)))
+def test_transpose_bf16_edge(ops, record, shape):
+    from diffcodec_amd import lib
+    b, r, c = shape
+    x = torch.randn(b, r, c, generator=torch.Generator().manual_seed(18000 + r))
+    gx = _g(shape, BF, x.to(DEV))
+    go = _twice(lambda o: lib.call("dc_transpose_bf16", gx.view.data_ptr(), o.data_ptr(), b, r, c, _st()), (b, c, r), BF, [gx],
+                f"transpose_bf16 {shape}")
+    assert _same_bits(go.view, gx.view.transpose(1, 2).contiguous()), f"transpose_bf16 {shape}"
+    record("edge[transpose_bf16]", "exact")
+
+
+@pytest.mark.parametrize("shape", E.ELEMENTWISE_CASES["freeu_lowfreq"], ids=lambda s: "x".join(map(str, s)))
+def test_freeu_lowfreq_edge(ops, record, shape):
+    from diffcodec_amd import lib
+    n, h, w, c = shape
+    x = torch.randn(shape, generator=torch.Generator().manual_seed(19000 + w)) + 0.4
+    gx = _g(shape, BF, x.to(DEV))
+    go = _twice(lambda o: lib.call("dc_freeu_lowfreq_nhwc_bf16", gx.view.data_ptr(), o.data_ptr(), n, h, w, c, 0.2, _st()), shape, BF, [gx],
+                f"freeu_lowfreq {shape}")
+    rows = torch.arange(n * h * w)
+    r, s = L.freeu_lowfreq_ref(gx.view, 0.2, rows)
+    _note(record, ("freeu_lowfreq",), L.check(go.view.reshape(-1, c), r, s, BF), f"freeu_lowfreq {shape}")
+
+
+@pytest.mark.parametrize("shape", E.ELEMENTWISE_CASES["freeu_backbone"], ids=lambda s: "x".join(map(str, s)))
+def test_freeu_backbone_edge(ops, record, shape):
+    from diffcodec_amd import lib
+    n, px, c = shape
+    x = torch.randn(shape, generator=torch.Generator().manual_seed(20000 + c))
+    gx = _g(shape, BF, x.to(DEV))
+    go = _twice(lambda o: lib.call("dc_freeu_backbone_nhwc_bf16", gx.view.data_ptr(), o.data_ptr(), n * px, c, 1.4, _st()), shape, BF, [gx],
+                f"freeu_backbone {shape}")
+    r, s = L.freeu_backbone_ref(gx.view, 1.4, torch.arange(n * px))
+    _note(record, ("freeu_backbone",), L.check(go.view.reshape(-1, c), r, s, BF), f"freeu_backbone {shape}")
+    assert _same_bits(go.view[..., c // 2:], gx.view[..., c // 2:]), "freeu_backbone: the second half of the channels moved"
+
+
+@pytest.mark.parametrize("n,dim,step", E.ELEMENTWISE_CASES["timestep_embedding"])
+def test_timestep_embedding_edge(ops, record, n, dim, step):
+    """a device step index into a four-entry timestep table"""
+    from diffcodec_amd import lib
+    gt = _g((4,), F32, torch.tensor(E.TIMESTEP_TABLE).to(DEV))
+    st = torch.tensor([-1, step, -1], dtype=torch.int32, device=DEV)
+    go = _twice(lambda o: lib.call("dc_timestep_embedding_f32", gt.view.data_ptr(), st[1:2].data_ptr(), o.data_ptr(), n, dim, _st()),
+                (n, dim), F32, [gt], f"timestep_embedding {n}x{dim}")
+    assert st.tolist() == [-1, step, -1]
+    r, s = L.timestep_embedding_ref(E.TIMESTEP_TABLE[step], n, dim)
+    _note(record, ("timestep_embedding",), L.check(go.view, r.to(DEV), s.to(DEV), F32), f"timestep_embedding {n}x{dim} step {step}")
+
+
+@pytest.mark.parametrize("b,t,c,vocab", E.ELEMENTWISE_CASES["embed_tokens"])
+def test_embed_tokens_edge(ops, record, b, t, c, vocab):
+    """ids in range only (0 and vocab - 1 among them): the fp32 sum of two bf16 rows, rounded once"""
+    from diffcodec_amd import lib
+    gen = torch.Generator().manual_seed(21000 + c)
+    ids = torch.randint(0, vocab, (b, t), generator=gen)
+    ids[0, 0], ids[-1, -1] = 0, vocab - 1
+    assert int(ids.min()) == 0 and int(ids.max()) == vocab - 1
+    gtok, gpos = _g((vocab, c), BF, torch.randn(vocab, c, generator=gen).to(DEV)), _g((t, c), BF, torch.randn(t, c, generator=gen).to(DEV))
+    ids_d = ids.to(DEV)
+    go = _twice(lambda o: lib.call("dc_embed_tokens_bf16", ids_d.data_ptr(), gtok.view.data_ptr(), gpos.view.data_ptr(), o.data_ptr(), b, t,
+                                   c, vocab, _st()), (b, t, c), BF, [gtok, gpos], f"embed_tokens {(b, t, c, vocab)}")
+    assert torch.equal(ids_d.cpu(), ids)
+    assert _same_bits(go.view, L.embed_tokens_ref(ids_d, gtok.view, gpos.view)), "embed_tokens: not the fp32 sum rounded once"
+    assert _same_bits(ops.embed_tokens(ids_d, gtok.view, gpos.view), go.view)
+    record("edge[embed_tokens]", "exact")
+
+
+@pytest.mark.parametrize("n,c,h,w,xs,f32,u8", E.ELEMENTWISE_CASES["postprocess_image"])
+def test_postprocess_image_edge(ops, record, n, c, h, w, xs, f32, u8):
+    """dc_postprocess_image on a contiguous input and on a pixel-stride-4 view whose fourth channel holds the NaN pattern; fp32 only,
+    uint8 only and both.  The guarded fp32 output of the launch itself is held to the fp64 reference.  The uint8 image must be
+    round-half-even(255 o32) exactly, o32 being the guarded fp32 output of the same launch — or, in the uint8-only case, which writes
+    no fp32 output, that of a separate fp32 launch on the same input (`own32`; where both exist they must agree bit for bit)."""
+    from diffcodec_amd import lib
+    what = f"postprocess_image xs={xs} f32={int(f32)} u8={int(u8)}"
+    x = E.postprocess_input(n, c, h, w, xs)
+    gx = E.Guarded((n, h, w, xs), F32, DEV)
+    xv = gx.view[..., :c]
+    xv.copy_(x[..., :c].to(DEV))
+    own32, _ = ops.postprocess_image(xv, want_u8=False)
+    runs = []
+    for rep in range(2):
+        g32 = _g((n, c, h, w), F32) if f32 else None
+        g8 = _g((n, h, w, c), torch.uint8) if u8 else None
+        lib.call("dc_postprocess_image", xv.data_ptr(), g32.view.data_ptr() if f32 else 0, g8.view.data_ptr() if u8 else 0, n, c, h, w, xs, _st())
+        torch.cuda.synchronize()
+        runs.append((g32, g8))
+    gx.assert_intact(f"{what} x")
+    assert torch.equal(xv.cpu(), x[..., :c]), f"{what}: the input was written"
+    if xs > c:
+        assert bool((gx.view[..., c:].contiguous().view(torch.int32) == E._signed(E.NAN_BITS[F32], F32)).all())
+    r, s = L.postprocess_image_ref(xv)
+    for g32, g8 in runs:
+        if g32 is not None:
+            g32.assert_intact(f"{what} o32")
+            assert g32.unwritten() == 0 and _same_bits(g32.view, runs[0][0].view) and _same_bits(g32.view, own32)
+        o32 = own32 if g32 is None else g32.view
+        if g8 is not None:
+            g8.assert_intact(f"{what} o8")
+            assert torch.equal(g8.view, torch.round(o32 * 255.0).to(torch.uint8).permute(0, 2, 3, 1)), f"{what}: uint8 image"
+    o32 = runs[0][0].view if f32 else own32
+    _note(record, ("postprocess_image",), L.check(o32, r, s, F32), what)
+    assert float(o32.min()) == 0.0 and float(o32.max()) == 1.0

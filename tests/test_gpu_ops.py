@@ -54,6 +54,8 @@ def test_splat_soft_matches_oracle(ops):
         ref = S.softsplat(x, flow, m, "soft") * (1 - mask)
         out = ops.splat_soft(x.to(DEV), flow.to(DEV), m.to(DEV), mask.to(DEV)).cpu()
         close(out, ref, rtol=1e-4, atol=1e-5)      # fp32; same summation order, device expf vs libm expf
+        v = L.check(out.to(DEV), *L.splat_soft_ref(x.to(DEV), flow.to(DEV), m.to(DEV), mask.to(DEV))[:2], torch.float32)
+        assert v["ok"], v                          # ... and the derived fp32 bound against the fp64 reference
         assert torch.equal(out, ops.splat_soft(x.to(DEV), flow.to(DEV), m.to(DEV), mask.to(DEV)).cpu())   # run-to-run bit-identical
         ref_sum = S.splat_sum(x, flow)
         # 'sum' mode has no transcendental: the gather adds every target's sources in ascending raster order with un-contracted
@@ -78,7 +80,10 @@ def test_splat_pathological_flows(ops):
         out = ops.splat_sum(x.to(DEV), flow.to(DEV)).cpu()
         assert torch.equal(out, S.splat_sum(x, flow))
         m = torch.randn(n, 1, h, w, generator=g)
-        close(ops.splat_soft(x.to(DEV), flow.to(DEV), m.to(DEV)).cpu(), S.softsplat(x, flow, m, "soft"), rtol=1e-4, atol=1e-5)
+        soft = ops.splat_soft(x.to(DEV), flow.to(DEV), m.to(DEV))
+        close(soft.cpu(), S.softsplat(x, flow, m, "soft"), rtol=1e-4, atol=1e-5)
+        v = L.check(soft, *L.splat_soft_ref(x.to(DEV), flow.to(DEV), m.to(DEV))[:2], torch.float32)
+        assert v["ok"], v
 
 
 def test_splat_fully_collapsed_flow_is_bounded(ops):
@@ -120,6 +125,8 @@ def test_occlusion_mask_and_flow_resize(ops):
     out = ops.occlusion_mask(fa.to(DEV), fb.to(DEV)).cpu()
     # threshold compare: allow disagreement only where the norm is within 1e-4 of 0.3
     assert (out != ref).float().mean().item() < 2e-3
+    v = L.check_occlusion_mask(out, L.occlusion_mask_ref(fa, fb))      # no disagreement outside the fp64 reference's own band
+    assert v["ok"] and v["band"] <= 0.005, v
     assert 0.05 < ref.mean() < 0.95
 
 

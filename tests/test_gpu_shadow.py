@@ -70,6 +70,10 @@ def test_every_launch_of_a_decode_matches_fp64(sd15, record, frames):
     assert out.shape == (frames, 3, 512, 512) and torch.isfinite(out).all()
     routes = {k[0] for k in sh.stats}
     assert {"gemm_dma", "conv3x3_tile", "igemm", "attention", "group_norm_ab", "conv3x3_nchw_f32"} <= routes, routes
+    # the control stage and the loop's entry / exit: flows and reference frames -> control pyramid, latents -> model input, image out
+    assert {"splat_soft", "occlusion_mask", "flow_resize_normalize", "fuse_warped", "nchw_f32_to_nhwc_bf16", "latents_to_model_input",
+            "postprocess_image"} <= routes, routes
+    assert sh.band and all(share <= 0.005 for _, share in sh.band.values()), sh.band
     if frames in (16, 44):                              # model batches 32 and 88: the production 1x1 kernels, coverage pinned
         assert {"gemm_rowpanel", "gemm_wide", "gemm_p8"} <= routes, routes
         seen = sorted(list(k) for k in sh.routes() if len(k) == 3)
@@ -132,7 +136,7 @@ def test_config4_dual_controlnet(record):
     sh, img = _shadowed(record, "c4_dual_u2", lambda: pipe(output_type="pt", **call).images)
     sh.raise_on_failure()
     assert img.shape == (2, 3, 512, 512) and torch.isfinite(img).all()
-    assert "conv3x3_nchw_f32" in {k[0] for k in sh.stats}
+    assert {"conv3x3_nchw_f32", "flow_resize_divide", "add_f32", "splat_soft", "occlusion_mask", "fuse_warped"} <= {k[0] for k in sh.stats}
 
 
 def test_shadow_does_not_change_results(sd15):

@@ -432,3 +432,252 @@ def test_latents_to_model_input_ref_passes_fp32_and_rejects_faults(mul, rep):
     assert not L.check(trunc.permute(0, 2, 3, 1).repeat(rep, 1, 1, 1), r, s, BF)["ok"]
     if mul != 1.0:
         assert not L.check(lat.to(BF).permute(0, 2, 3, 1).repeat(rep, 1, 1, 1), r, s, BF)["ok"]
+
+
+# ------------------------------------------------------------------------------------------ control stage and plain elementwise launches
+# For every table case of tests/edge_cases.py (all but the one beyond a single grid), on the case's own inputs: the project's fp32 CPU
+# restatement (the C oracle, oracle/control_ref.py, plain torch fp32) passes the check the GPU edge test applies, and a seeded fault
+# fails it wherever it moves the result by more than FAULT_MATERIAL — and it does so on the cases the table holds for it.
+import edge_cases as E                                                # noqa: E402
+from oracle import control_ref as CR                                  # noqa: E402
+from oracle import splat as OS                                        # noqa: E402
+
+F32, F64 = torch.float32, torch.float64
+FAULT_MATERIAL = 1e-3
+SPLAT_SMALL = [c for c in E.SPLAT_CASES if c != E.SPLAT_LARGE]
+SPLAT_FAULTS = ("drop_nw", "drop_ne", "drop_sw", "drop_se", "swap_ne_sw", "drop_border", "nonfinite_zero", "no_mask", "no_eps", "pitch_h")
+
+
+def _splat_variant(x, flow, metric, mask, fault=None):
+    """fp64 'soft' splat with one seeded fault: drop_* one of the four corner lists dropped; swap_ne_sw the NE and SW weights
+    exchanged; drop_border sources whose north-west cell has row or column -1 dropped; nonfinite_zero a non-finite flow treated as
+    zero flow; no_mask; no_eps; pitch_h the gather reading cell (qy + 1) (H + 1) + qx + 1 of bins laid out with pitch W + 1."""
+    n, c, h, w = x.shape
+    gy, gx = torch.meshgrid(torch.arange(h, dtype=F32), torch.arange(w, dtype=F32), indexing="ij")
+    fx, fy = gx[None] + flow[:, 0], gy[None] + flow[:, 1]
+    fin = torch.isfinite(fx) & torch.isfinite(fy)
+    if fault == "nonfinite_zero":
+        fx, fy, fin = torch.where(fin, fx, gx[None].expand_as(fx)), torch.where(fin, fy, gy[None].expand_as(fy)), torch.ones_like(fin)
+    fx, fy = torch.where(fin, fx, torch.zeros_like(fx)).to(F64), torch.where(fin, fy, torch.zeros_like(fy)).to(F64)
+    x0, y0 = torch.floor(fx), torch.floor(fy)
+    inside = fin & (x0 >= -1) & (x0 < w) & (y0 >= -1) & (y0 < h)            # the sources the bins hold
+    if fault == "drop_border":
+        inside = inside & (x0 >= 0) & (y0 >= 0)
+    e = torch.exp(metric.to(F64))
+    planes = torch.cat([x.to(F64) * e, e], 1).reshape(n, c + 1, h * w)
+    out = torch.zeros(n, c + 1, h * w, dtype=F64)
+    wgt = {(0, 0): (x0 + 1 - fx) * (y0 + 1 - fy), (1, 0): (fx - x0) * (y0 + 1 - fy), (0, 1): (x0 + 1 - fx) * (fy - y0),
+           (1, 1): (fx - x0) * (fy - y0)}
+    if fault == "swap_ne_sw":
+        wgt[(1, 0)], wgt[(0, 1)] = wgt[(0, 1)], wgt[(1, 0)]
+    names = {(0, 0): "drop_nw", (1, 0): "drop_ne", (0, 1): "drop_sw", (1, 1): "drop_se"}
+    for (dx, dy), wk in wgt.items():
+        if fault == names[(dx, dy)]:
+            continue
+        if fault == "pitch_h":
+            cell = (y0 + 1) * (w + 1) + x0 + 1                                  # where the bins hold the source
+            targets = []
+            for ty in range(h):                                                # the targets whose (wrong) list index names that cell
+                tx = cell - (ty - dy + 1) * (h + 1) - 1 + dx
+                targets.append((tx, torch.full_like(tx, ty)))
+        else:
+            targets = [(x0 + dx, y0 + dy)]
+        for tx, ty in targets:
+            ok = inside & (tx >= 0) & (tx < w) & (ty >= 0) & (ty < h)
+            idx = torch.where(ok, ty * w + tx, torch.zeros_like(tx)).long().reshape(n, 1, h * w)
+            out.scatter_add_(2, idx.expand(n, c + 1, h * w), planes * torch.where(ok, wk, torch.zeros_like(wk)).reshape(n, 1, h * w))
+    out = out.reshape(n, c + 1, h, w)
+    r = out[:, :c] / (out[:, c:] + (0.0 if fault == "no_eps" else L.EPS_SPLAT))
+    return r if (mask is None or fault == "no_mask") else r * (1 - mask.to(F64))
+
+
+def _hold_fault(name, bad, r, s, label):
+    """a fault that moves the result materially must fail the check; -> whether it was material here"""
+    bad = torch.nan_to_num(bad, nan=1e30, posinf=1e30, neginf=-1e30)
+    if float((bad - r).abs().max()) <= FAULT_MATERIAL:
+        return False
+    assert not L.check(bad, r, s, F32)["ok"], (label, name)
+    return True
+
+
+def _splat_fault_hits(i):
+    """the seeded faults that are material on small splat case i (each one held to the check on the way)"""
+    case = SPLAT_SMALL[i]
+    x, flow, metric, mask = E.splat_inputs(case, E.splat_seed(i))
+    r, s, _ = L.splat_soft_ref(x, flow, metric, mask)
+    return [f for f in SPLAT_FAULTS if not (f == "pitch_h" and case[2] == case[3])
+            and _hold_fault(f, _splat_variant(x, flow, metric, mask, f), r, s, E.splat_label(case))]
+
+
+@pytest.fixture(scope="module")
+def splat_fault_hits():
+    """{fault: [case]} over every small splat case, computed here so that the table-level test stands on its own"""
+    hits = {f: [] for f in SPLAT_FAULTS}
+    for i, case in enumerate(SPLAT_SMALL):
+        for f in _splat_fault_hits(i):
+            hits[f].append(case)
+    return hits
+
+
+@pytest.mark.parametrize("i", range(len(SPLAT_SMALL)), ids=[E.splat_label(c) for c in SPLAT_SMALL])
+def test_splat_bound_passes_the_c_oracle_and_rejects_faults(i):
+    case = SPLAT_SMALL[i]
+    x, flow, metric, mask = E.splat_inputs(case, E.splat_seed(i))
+    label = E.splat_label(case)
+    for mk in (mask, None):
+        r, s, k = L.splat_soft_ref(x, flow, metric, mk)
+        assert torch.isfinite(r).all() and torch.isfinite(s).all()
+        assert torch.allclose(r, _splat_variant(x, flow, metric, mk), rtol=1e-12, atol=1e-300), label     # the two fp64 forms agree
+        y = OS.softsplat(x, flow, metric, "soft")
+        y = y if mk is None else y * (1 - mk)
+        v = L.check(y, r, s, F32)
+        assert v["ok"] and v["ratio"] <= 0.5, (label, v)                      # issue: the C oracle stays at err/tol <= 0.14
+    _splat_fault_hits(i)                                                      # every material fault fails the check on this case
+    rs, ss, _ = L.splat_sum_ref(x, flow)
+    assert L.check(OS.splat_sum(x, flow), rs, ss, F32)["ok"], label
+    if case[4] == "collapse":
+        assert int(k.max()) == case[2] * case[3]                              # every source of the image reaches one target
+
+
+def test_splat_faults_are_exposed_by_the_table(splat_fault_hits):
+    """every seeded fault is material — and therefore rejected — on the flow families that are in the table for it, and on an odd batch"""
+    fam = lambda f: {c[4] for c in splat_fault_hits[f]}
+    for f in ("drop_nw", "drop_ne", "drop_sw", "drop_se"):
+        assert {"smooth", "collapse", "nonfinite"} <= fam(f), (f, fam(f))
+    assert "border" in fam("drop_nw") and "away" in fam("drop_nw")         # weights exactly 1 on the north-west corner
+    assert {"smooth", "collapse"} <= fam("swap_ne_sw")
+    assert {"smooth", "nonfinite"} <= fam("drop_border")                  # (exact border landings give those corners weight 0)
+    assert fam("nonfinite_zero") == {"nonfinite"}
+    assert fam("no_mask") == set(E.FLOW_FAMILIES)
+    assert any(c[5] == "wide" for c in splat_fault_hits["no_eps"])        # (an empty target also exposes it: 0 / 0)
+    assert {c[:4] for c in splat_fault_hits["pitch_h"]} >= {(2, 5, 24, 40), (3, 7, 7, 9)}      # the non-square maps
+    for f in SPLAT_FAULTS:
+        assert any(c[0] == 3 for c in splat_fault_hits[f]), f                # an odd batch
+
+
+OCCLUSION_FAULTS = ("drop_nw", "drop_ne", "drop_sw", "drop_se", "drop_border", "swap_ne_sw")
+
+
+@pytest.mark.parametrize("case", E.OCCLUSION_CASES, ids=[f"{c[0]}x{c[1]}x{c[2]}" for c in E.OCCLUSION_CASES])
+def test_occlusion_band_is_narrow_and_the_check_is_sharp(case):
+    fa, fb = E.occlusion_inputs(case)
+    ref = L.occlusion_mask_ref(fa, fb)
+    assert float(ref["delta"].max()) <= 5e-5                                   # the margin stays four orders below the threshold
+    v = L.check_occlusion_mask(CR.compute_mask(fa, fb), ref)
+    pixels = case[0] * case[1] * case[2]
+    assert v["ok"] and v["flips"] == 0, v                                      # the fp32 restatement disagrees nowhere outside the band
+    assert v["band"] <= 0.005 and (pixels >= 200 or v["band"] == 0.0), v
+    assert 0.05 <= v["ones"] <= 0.95, v
+    # faults: every one of them flips a pixel outside the band on every shape of the table, and must then fail the check
+    ones = torch.ones_like(fb[:, :1])
+    band = (ref["norm"] - L.OCC_THRESHOLD).abs() <= ref["delta"]
+    exposed = set()
+    for f in OCCLUSION_FAULTS:
+        d = fb.to(F64) + _splat_variant(fa, fb, ones, None, f)
+        bad = (torch.sqrt((d * d).sum(1, keepdim=True)) > L.OCC_THRESHOLD).to(F32)
+        if bool(((bad.to(F64) != ref["mask"]) & ~band).any()):
+            assert not L.check_occlusion_mask(bad, ref)["ok"], f
+            exposed.add(f)
+    assert exposed == set(OCCLUSION_FAULTS), (case, sorted(exposed))
+    soft = ref["mask"].to(F32) * 0.999
+    assert not L.check_occlusion_mask(soft, ref)["ok"] and L.check_occlusion_mask(soft, ref)["not_binary"] > 0
+
+
+def _flow_cases():
+    return [(c, False) for c in E.FLOW_RESIZE_CASES] + [(c, True) for c in E.FLOW_RESIZE_CASES + E.FLOW_RESIZE_DIVIDE_ONLY]
+
+
+@pytest.mark.parametrize("case,divide", _flow_cases(), ids=[("divide-" if d else "normalize-") + "x".join(map(str, c)) for c, d in _flow_cases()])
+def test_flow_resize_bound_passes_torch_and_rejects_faults(case, divide):
+    n, hh, ww, h, w = case
+    src = E.flow_resize_input(case, 0)[:, 2:4]
+    dx, dy = E.FLOW_DIVISORS if divide else ((w - 1) / 2.0, (h - 1) / 2.0)
+    r, s = L.flow_resize_ref(src, h, w, dx, dy)
+    t = F.interpolate(src, size=(h, w), mode="bilinear", align_corners=False)
+    if not divide:
+        assert torch.equal(torch.stack([t[:, 0] / dx, t[:, 1] / dy], 1), CR.resize_and_normalize_flow(src, h, w))
+    y = torch.stack([t[:, 0] / dx, t[:, 1] / dy], 1)
+    assert torch.allclose(r, torch.stack([F.interpolate(src.double(), size=(h, w), mode="bilinear", align_corners=False)[:, 0] / dx,
+                                          F.interpolate(src.double(), size=(h, w), mode="bilinear", align_corners=False)[:, 1] / dy], 1),
+                          rtol=1e-12, atol=1e-14)
+    v = L.check(y, r, s, F32)
+    assert v["ok"], (case, v)
+    label = "x".join(map(str, case))
+    if dx != dy:
+        assert _hold_fault("divisors_swapped", torch.stack([t[:, 0] / dy, t[:, 1] / dx], 1).double(), r, s, label)
+    ta = F.interpolate(src.double(), size=(h, w), mode="bilinear", align_corners=True)
+    if (hh, ww) != (1, 1):
+        assert _hold_fault("align_corners", torch.stack([ta[:, 0] / dx, ta[:, 1] / dy], 1), r, s, label)
+    if hh != ww:                                                              # the source read with the other pitch
+        tw = F.interpolate(src.double().reshape(n, 2, ww, hh), size=(h, w), mode="bilinear", align_corners=False)
+        assert _hold_fault("pitch_h", torch.stack([tw[:, 0] / dx, tw[:, 1] / dy], 1), r, s, label) or h * w == 1
+
+
+@pytest.mark.parametrize("occ", [True, False], ids=["holes", "noholes"])
+@pytest.mark.parametrize("i", range(len(E.FUSE_CASES)))
+def test_fuse_bound_passes_torch_and_rejects_faults(i, occ):
+    wf, wl, cf, cb, of, ob = E.fuse_inputs(E.FUSE_CASES[i], i)
+    assert bool(((cf <= 0) & (cb <= 0)).any())
+    assert cf.numel() == 1 or (float(cb.max()) == 1e4 and bool(((cf < 0) & (cb > 0)).any()))
+    assert {float(v) for v in (of + ob).unique()} <= {0.0, 1.0, 2.0} and float((of + ob).max()) == 2.0
+    r, s = L.fuse_warped_ref(wf, wl, cf, cb, of if occ else None, ob if occ else None)
+
+    def restated(clamp=True, thr=1.5):                                        # extractors.py:297-310 as oracle/control_ref.py writes it
+        conf = torch.cat([cf, cb], 1)
+        conf = torch.clamp(conf, min=0) if clamp else conf
+        wn = conf / (conf.sum(1, keepdim=True) + 1e-6)
+        fused = wn[:, :1] * wf + wn[:, 1:] * wl
+        return torch.where(((of + ob) > thr).expand_as(fused), 0.5 * (wf + wl), fused) if occ else fused
+
+    v = L.check(restated(), r, s, F32)
+    assert v["ok"], v
+    label = f"fuse{i}"
+    assert _hold_fault("no_clamp", restated(clamp=False).double(), r, s, label) or (occ and of.numel() == 1)   # one pixel: a hole
+    if occ and of.numel() > 1:
+        assert _hold_fault("holes_at_0.5", restated(thr=0.5).double(), r, s, label)
+
+
+def test_elementwise_bounds_pass_torch_fp32():
+    """silu / add / lincomb / postprocess: torch's fp32 evaluation passes, a result one part in 2^18 off fails; silu stays finite at
+    its special inputs"""
+    for n in E.ELEMENTWISE_CASES["silu_f32"][:3]:
+        x = E.elementwise_input(n, n, E.SILU_SPECIALS)
+        r, s = L.silu_f32_ref(x)
+        y = F.silu(x)
+        assert torch.isfinite(r).all() and torch.isfinite(y).all()
+        assert L.check(y, r, s, F32)["ok"]
+        assert L.check(torch.zeros_like(y).where(x < -88, y), r, s, F32)["ok"]       # a flushed reciprocal passes
+        assert not L.check(y * (1 + 2.0 ** -18), r, s, F32)["ok"] or n == 1 and float(y.abs().max()) == 0
+        assert not L.check(x * torch.sigmoid(1.001 * x), r, s, F32)["ok"] or n == 1
+    for n in E.ELEMENTWISE_CASES["add_f32"][:3]:
+        a, b = E.elementwise_input(n, 1), E.elementwise_input(n, 2)
+        r, s = L.add_f32_ref(a, b)
+        assert L.check(a + b, r, s, F32)["ok"] and not L.check(a + b * (1 + 2.0 ** -16), r, s, F32)["ok"]
+    for n, t in E.ELEMENTWISE_CASES["lincomb"]:
+        if n > 257:
+            continue
+        terms = [(E.LINCOMB_COEFS[j], E.elementwise_input(n, 10 + j)) for j in range(t)]
+        r, s = L.lincomb_ref(terms)
+        y = sum(torch.tensor(c, dtype=F32) * v for c, v in terms)
+        assert L.check(y, r, s, F32)["ok"]
+        bad = y - terms[-1][1] * torch.tensor(terms[-1][0], dtype=F32) * 2.0 ** -16     # the last coefficient slightly off
+        assert not L.check(bad, r, s, F32)["ok"]
+    n, c, h, w = 2, 3, 5, 7
+    for xs in (3, 4):
+        x = E.postprocess_input(n, c, h, w, xs)[..., :c]
+        r, s = L.postprocess_image_ref(x)
+        y = (x / 2 + 0.5).clamp(0, 1).permute(0, 3, 1, 2)
+        assert L.check(y, r, s, F32)["ok"] and float(r.min()) == 0.0 and float(r.max()) == 1.0
+        assert not L.check((x / 2 + 0.5).permute(0, 3, 1, 2), r, s, F32)["ok"]            # no clamp
+
+
+def test_exact_references_round_once():
+    g = torch.Generator().manual_seed(5)
+    x = torch.randn(2, 3, 4, 5, generator=g)
+    y = L.nchw_f32_to_nhwc_bf16_ref(x)
+    assert y.shape == (2, 4, 5, 3) and torch.equal(y.permute(0, 3, 1, 2), x.to(BF))
+    assert torch.equal(L.nhwc_to_nchw_f32_ref(y), x.to(BF).float())
+    tok, pos = torch.randn(11, 8, generator=g).to(BF), torch.randn(7, 8, generator=g).to(BF)
+    ids = torch.tensor([[0, 10, 3, 3, 9], [10, 0, 1, 2, 5]])
+    e = L.embed_tokens_ref(ids, tok, pos)
+    assert torch.equal(e[1, 0], (tok[10].float() + pos[0].float()).to(BF)) and e.shape == (2, 5, 8)
