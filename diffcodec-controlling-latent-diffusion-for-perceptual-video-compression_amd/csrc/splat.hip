@@ -7,6 +7,7 @@
 // Round 2: a DETERMINISTIC GATHER instead of the reference's float-atomic scatter.  A source pixel p lands at
 // (x + fx, y + fy) and feeds the four pixels around that point; turned around, a target pixel t is fed by the sources whose
 // north-west corner cell floor(x + fx, y + fy) is t, t - (1,0), t - (0,1) or t - (1,1).  So:
+//   0. bin_zero  : the counts start at zero
 //   1. bin_count : cell of every source (or -1: non-finite / no corner inside the map), integer count per cell
 //   2. bin_scan  : exclusive scan of the counts per image (one workgroup per image) -> cell starts
 //   3. bin_fill  : sources written into their cell's segment (arrival order) ...
@@ -61,6 +62,11 @@ __device__ __forceinline__ void landing(const float* __restrict__ flow, long lon
 {
     fx = (float)x + flow[(n * 2 + 0) * hw + p];
     fy = (float)y + flow[(n * 2 + 1) * hw + p];
+}
+
+__global__ __launch_bounds__(256) void bin_zero_kernel(int* __restrict__ counts, long long total)
+{
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) counts[i] = 0;
 }
 
 __global__ __launch_bounds__(256) void bin_count_kernel(const float* __restrict__ flow, int* __restrict__ cell_of, int* __restrict__ counts,
@@ -183,8 +189,10 @@ __device__ __forceinline__ void for_each_source(const float* __restrict__ flow, 
     }
 }
 
-// MODE 0: 'sum' (out = sum in*w) ; 1: 'soft' (out = sum in*e*w / (sum e*w + 1e-7) [* (1 - mask)])
-template <int MODE>
+// MODE 0: 'sum' (out = sum in*w) ; 1: 'soft' (out = sum in*e*w / norm(sum e*w) [* (1 - mask)]) ; 2: 'avg' (sum in*w / norm(sum w)) ;
+// 3: 'linear' (sum in*m*w / norm(sum m*w)).  EPS, the normaliser of softsplat.py:256-266: 0 den + 1e-7 ; 1 den == 0 ? 1 : den ;
+// 2 clip(den, 1e-7) — a NaN denominator stays NaN, as under torch's clip.  <1, 0> is the decode path's instance.
+template <int MODE, int EPS>
 __global__ __launch_bounds__(256) void splat_gather_kernel(const float* __restrict__ in, const float* __restrict__ flow,
                                                            const float* __restrict__ metric, const float* __restrict__ mask,
                                                            const int* __restrict__ starts, const int* __restrict__ sorted2,
@@ -204,13 +212,20 @@ __global__ __launch_bounds__(256) void splat_gather_kernel(const float* __restri
                 const float e = expf(metric[n * hw + sp]);                        // softsplat.py:246-247
                 num += rounded(rounded(src[sp] * e) * w);
                 den += rounded(e * w);
+            } else if (MODE == 3) {
+                const float m = metric[n * hw + sp];                              // softsplat.py:243-244
+                num += rounded(rounded(src[sp] * m) * w);
+                den += rounded(m * w);
             } else {
                 num += rounded(src[sp] * w);
+                if (MODE == 2) den += w;                                          // the ones channel of softsplat.py:240-241: 1 * w
             }
         });
         float v = num;
-        if (MODE == 1) {
-            v = num / (den + 0.0000001f);                                         // softsplat.py:256-257,270
+        if (MODE != 0) {
+            if (EPS == 0) v = num / (den + 0.0000001f);                           // softsplat.py:256-260,270
+            else if (EPS == 1) v = num / (den == 0.0f ? 1.0f : den);              // softsplat.py:262-263
+            else v = num / (den < 0.0000001f ? 0.0000001f : den);                 // softsplat.py:265-266
             if (mask) v = v * (1.0f - mask[n * hw + p]);                          // control_utils.py:69-70
         }
         out[i] = v;
@@ -246,8 +261,9 @@ inline int grid_for(long long total) { return (int)min((long long)8192, (total +
 int build_bins(const float* flow, const BinWs& b, int N, int H, int W, hipStream_t st)
 {
     const long long hw = (long long)H * W, cp = bin_cells(H, W) + 1;
-    if (hipMemsetAsync(b.counts, 0, (size_t)(N * cp) * 4, st) != hipSuccess) return DC_ERR_LAUNCH;
     const int g = grid_for((long long)N * hw);
+    // zeroed by a kernel, not a memset: every step is then a kernel node when the launch is captured into a graph
+    hipLaunchKernelGGL(bin_zero_kernel, dim3(grid_for(N * cp)), dim3(256), 0, st, b.counts, N * cp);
     hipLaunchKernelGGL(bin_count_kernel, dim3(g), dim3(256), 0, st, flow, b.cell, b.counts, N, H, W);
     hipLaunchKernelGGL(bin_scan_kernel, dim3(N), dim3(256), 0, st, b.counts, b.starts, cp);
     hipLaunchKernelGGL(bin_fill_kernel, dim3(g), dim3(256), 0, st, b.cell, b.counts, b.starts, b.sorted, N, hw, cp);
@@ -312,7 +328,7 @@ extern "C" int dc_splat_sum_f32(const float* in, const float* flow, float* out, 
     hipStream_t st = (hipStream_t)stream;
     const BinWs b = bin_carve(ws, N, H, W);
     if (int rc = build_bins(flow, b, N, H, W, st)) return rc;
-    hipLaunchKernelGGL(splat_gather_kernel<0>, dim3(grid_for((long long)N * C * H * W)), dim3(256), 0, st, in, flow,
+    hipLaunchKernelGGL((splat_gather_kernel<0, 0>), dim3(grid_for((long long)N * C * H * W)), dim3(256), 0, st, in, flow,
                        (const float*)nullptr, (const float*)nullptr, b.starts, b.sorted2, out, N, C, H, W);
     return dc_launch_status();
 }
@@ -324,8 +340,34 @@ extern "C" int dc_splat_soft_f32(const float* in, const float* flow, const float
     hipStream_t st = (hipStream_t)stream;
     const BinWs b = bin_carve(ws, N, H, W);
     if (int rc = build_bins(flow, b, N, H, W, st)) return rc;
-    hipLaunchKernelGGL(splat_gather_kernel<1>, dim3(grid_for((long long)N * C * H * W)), dim3(256), 0, st, in, flow, metric, mask,
+    hipLaunchKernelGGL((splat_gather_kernel<1, 0>), dim3(grid_for((long long)N * C * H * W)), dim3(256), 0, st, in, flow, metric, mask,
                        b.starts, b.sorted2, out, N, C, H, W);
+    return dc_launch_status();
+}
+
+// launch table of the normalised modes: [mode: avg, linear, soft][eps: add, zero, clip]
+template <int MODE, int EPS>
+static void launch_norm(const float* in, const float* flow, const float* metric, const float* mask, const BinWs& b, float* out, int N, int C,
+                 int H, int W, hipStream_t st)
+{
+    hipLaunchKernelGGL((splat_gather_kernel<MODE, EPS>), dim3(grid_for((long long)N * C * H * W)), dim3(256), 0, st, in, flow, metric,
+                       mask, b.starts, b.sorted2, out, N, C, H, W);
+}
+
+extern "C" int dc_splat_norm_f32(const float* in, const float* flow, const float* metric, const float* mask, float* out, void* ws,
+                                 int N, int C, int H, int W, int mode, int eps, void* stream)
+{
+    if (!in || !flow || !out || !ws || N <= 0 || C <= 0 || H <= 0 || W <= 0) return DC_ERR_INVALID;
+    if (mode < DC_SPLAT_AVG || mode > DC_SPLAT_SOFT || eps < DC_SPLAT_ADDEPS || eps > DC_SPLAT_CLIPEPS) return DC_ERR_INVALID;
+    if ((mode == DC_SPLAT_AVG) != (metric == nullptr)) return DC_ERR_INVALID;
+    using Fn = void (*)(const float*, const float*, const float*, const float*, const BinWs&, float*, int, int, int, int, hipStream_t);
+    static const Fn table[3][3] = {{launch_norm<2, 0>, launch_norm<2, 1>, launch_norm<2, 2>},
+                                   {launch_norm<3, 0>, launch_norm<3, 1>, launch_norm<3, 2>},
+                                   {launch_norm<1, 0>, launch_norm<1, 1>, launch_norm<1, 2>}};
+    hipStream_t st = (hipStream_t)stream;
+    const BinWs b = bin_carve(ws, N, H, W);
+    if (int rc = build_bins(flow, b, N, H, W, st)) return rc;
+    table[mode][eps](in, flow, metric, mask, b, out, N, C, H, W, st);
     return dc_launch_status();
 }
 

@@ -31,6 +31,9 @@ SIGNATURES = {
     "dc_splat_soft_f32": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
     "dc_splat_sum_f32": [vp, vp, vp, vp, i32, i32, i32, i32, vp],
     "dc_splat_ws_bytes": [i32, i32, i32],
+    "dc_splat_norm_f32": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
+    "dc_splat_ingrad_f32": [vp, vp, vp, i32, i32, i32, i32, vp],
+    "dc_splat_flowgrad_f32": [vp, vp, vp, vp, i32, i32, i32, i32, vp],
     "dc_occlusion_mask_f32": [vp, vp, vp, vp, i32, i32, i32, vp],
     "dc_flow_resize_normalize_f32": [vp, i64, vp, i32, i32, i32, i32, i32, vp],
     "dc_flow_resize_divide_f32": [vp, i64, vp, i32, i32, i32, i32, i32, f32, f32, vp],

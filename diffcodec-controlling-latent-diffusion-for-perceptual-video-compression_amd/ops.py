@@ -686,6 +686,60 @@ def splat_sum(x, flow):
     return out
 
 
+SPLAT_MODES = {"avg": 0, "linear": 1, "soft": 2}              # DC_SPLAT_AVG / LINEAR / SOFT
+SPLAT_EPS = {"addeps": 0, "zeroeps": 1, "clipeps": 2}         # DC_SPLAT_ADDEPS / ZEROEPS / CLIPEPS
+
+
+def splat_norm(x, flow, metric, mode, eps="addeps", mask=None):
+    """The normalised modes of the wrapper, fused (softsplat.py:240-270): mode 'avg' (metric None) | 'linear' | 'soft',
+    eps 'addeps' | 'zeroeps' | 'clipeps'.  No gradient."""
+    _chk(x, F32, "in")
+    _chk(flow, F32, "flow")
+    n, c, h, w = x.shape
+    assert flow.shape == (n, 2, h, w)
+    if (mode == "avg") != (metric is None):
+        raise ValueError(f"splat_norm: mode {mode!r} {'takes no' if mode == 'avg' else 'needs a'} metric")
+    if metric is not None:
+        _chk(metric, F32, "metric")
+        assert metric.shape == (n, 1, h, w)
+    if mask is not None:
+        _chk(mask, F32, "mask")
+        assert mask.shape == (n, 1, h, w)
+    out = torch.empty_like(x)
+    ws = _splat_ws(n, h, w, x.device)
+    lib.call("dc_splat_norm_f32", x.data_ptr(), flow.data_ptr(), _ptr(metric), _ptr(mask), out.data_ptr(), ws.data_ptr(), n, c, h, w,
+             SPLAT_MODES[mode], SPLAT_EPS[eps], _stream(),
+             meta=_meta(f"splat kernels (softsplat '{mode}-{eps}')", f"N={n} C={c} {h}x{w}", 10.0 * n * (c + 1) * h * w,
+                        4.0 * n * h * w * (4 * c + c + 12)))
+    return out
+
+
+def splat_ingrad(flow, outgrad):
+    """d loss / d in of the 'sum' splat (softsplat_ingrad, softsplat.py:368-435): every element written, 0 for non-finite sources."""
+    _chk(flow, F32, "flow")
+    _chk(outgrad, F32, "outgrad")
+    n, c, h, w = outgrad.shape
+    assert flow.shape == (n, 2, h, w)
+    ingrad = torch.empty_like(outgrad)
+    # algorithmic traffic: outgrad read once (the four corner reads of neighbouring sources share lines), ingrad written once, flow
+    # once per element from cache: counted once
+    lib.call("dc_splat_ingrad_f32", flow.data_ptr(), outgrad.data_ptr(), ingrad.data_ptr(), n, c, h, w, _stream(),
+             meta=_meta("splat_ingrad_kernel", f"N={n} C={c} {h}x{w}", 12.0 * n * c * h * w, 4.0 * n * h * w * (2 * c + 2)))
+    return ingrad
+
+
+def splat_flowgrad(x, flow, outgrad):
+    """d loss / d flow of the 'sum' splat (softsplat_flowgrad, softsplat.py:439-524) -> [N, 2, H, W]; deterministic."""
+    for t, nm in ((x, "in"), (flow, "flow"), (outgrad, "outgrad")):
+        _chk(t, F32, nm)
+    n, c, h, w = x.shape
+    assert flow.shape == (n, 2, h, w) and outgrad.shape == x.shape
+    flowgrad = torch.empty_like(flow)
+    lib.call("dc_splat_flowgrad_f32", x.data_ptr(), flow.data_ptr(), outgrad.data_ptr(), flowgrad.data_ptr(), n, c, h, w, _stream(),
+             meta=_meta("splat_flowgrad_kernel", f"N={n} C={c} {h}x{w}", 20.0 * n * c * h * w, 4.0 * n * h * w * (2 * c + 4)))
+    return flowgrad
+
+
 def occlusion_mask(flow_a, flow_b):
     _chk(flow_a, F32, "flow_a")
     _chk(flow_b, F32, "flow_b")

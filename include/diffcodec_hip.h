@@ -36,6 +36,38 @@ int dc_splat_soft_f32(const float* in, const float* flow, const float* metric, c
                       float* out, void* ws, int N, int C, int H, int W, void* stream);
 /* 'sum' mode: out = splat(in, flow) (softsplat.py:235,251); bit-exact with the sequential restatement oracle/splat_oracle.c. */
 int dc_splat_sum_f32(const float* in, const float* flow, float* out, void* ws, int N, int C, int H, int W, void* stream);
+/* The normalised modes of the wrapper, fused (no-grad forward) — controlnet/softsplat.py:240-247 (the cat[...] that is never
+ * materialised here), :251 (the splat) and :253-270 (the normaliser):
+ *   mode DC_SPLAT_AVG    'avg'     out = sum in*w           / norm(sum w)            metric must be NULL
+ *        DC_SPLAT_LINEAR 'linear'  out = sum (in*metric)*w  / norm(sum metric*w)
+ *        DC_SPLAT_SOFT   'soft'    out = sum (in*exp(m))*w  / norm(sum exp(m)*w)
+ *   eps  DC_SPLAT_ADDEPS  norm(d) = d + 1e-7 (:256-260)   DC_SPLAT_ZEROEPS  d == 0 ? 1 : d (:262-263)
+ *        DC_SPLAT_CLIPEPS clip(d, 1e-7, None) (:265-266; a NaN d stays NaN, as under torch's clip)
+ * Same gather, same ascending source order and individually rounded products / sums as dc_splat_sum_f32: 'avg' and 'linear' are
+ * bit for bit splat_sum(cat[...]) followed by the fp32 normaliser; (DC_SPLAT_SOFT, DC_SPLAT_ADDEPS) is dc_splat_soft_f32's
+ * instance.  mask [N,1,H,W] or NULL as in dc_splat_soft_f32; ws: dc_splat_ws_bytes(N, H, W) bytes. */
+#define DC_SPLAT_AVG 0
+#define DC_SPLAT_LINEAR 1
+#define DC_SPLAT_SOFT 2
+#define DC_SPLAT_ADDEPS 0
+#define DC_SPLAT_ZEROEPS 1
+#define DC_SPLAT_CLIPEPS 2
+int dc_splat_norm_f32(const float* in, const float* flow, const float* metric, const float* mask, float* out, void* ws,
+                      int N, int C, int H, int W, int mode, int eps, void* stream);
+/* Replaces cuda_launch(cuda_kernel('softsplat_ingrad', ...)) — controlnet/softsplat.py:368-435 (arithmetic :376-423):
+ * ingrad[n,c,y,x] = sum over the in-bounds corners (NW, NE, SW, SE) of outgrad[n,c,corner] * w_corner, every product and sum
+ * rounded on its own.  Every element is written: a source whose landing point is not finite gets 0 (the reference starts from
+ * a zeroed tensor), so `ingrad` may be uninitialised memory.  flow [N,2,H,W]; outgrad, ingrad [N,C,H,W].  No scratch. */
+int dc_splat_ingrad_f32(const float* flow, const float* outgrad, float* ingrad, int N, int C, int H, int W, void* stream);
+/* Replaces cuda_launch(cuda_kernel('softsplat_flowgrad', ...)) — controlnet/softsplat.py:439-524 (arithmetic :447-511):
+ * flowgrad[n,k,y,x] = sum over channels and in-bounds corners of (outgrad[n,c,corner] * in[n,c,y,x]) * dw_k,corner with the dw of
+ * :477-489; both components in one pass over the channels (the reference runs one thread per component).  The channel sum of a
+ * source is split over S lanes of a workgroup (S a function of C and H*W only), each lane summing its channels c = s, s + S, ...
+ * in ascending order, and the S partial sums are added in ascending s: a fixed order, no float atomics, bit-identical from
+ * launch to launch and independent of N.  Non-finite landing points get 0 in both components; every element is written.
+ * in, outgrad [N,C,H,W]; flow, flowgrad [N,2,H,W].  No scratch. */
+int dc_splat_flowgrad_f32(const float* in, const float* flow, const float* outgrad, float* flowgrad, int N, int C, int H, int W,
+                          void* stream);
 /* compute_mask(a, b) — controlnet/control_utils.py:11-17: occ = (|| b + softsplat(a, b, ones, 'soft') ||_2 > 0.3).
  * ws: dc_splat_ws_bytes(N, H, W) bytes. */
 int dc_occlusion_mask_f32(const float* flow_a, const float* flow_b, float* mask_out, void* ws,
