@@ -194,7 +194,9 @@ struct ssim_final {
     int mode;                                // 0 = MS-SSIM, 1 = SSIM, 2 = SSIM with relu (nonnegative_ssim)
 };
 
-// out[nc] = per-(n, c) value, out[NC + n] = mean over c, out[NC + N] = mean over (n, c).  One workgroup.
+// out[nc] = per-(n, c) value, out[NC + n] = mean over c, out[NC + N] = mean over (n, c).  One workgroup.  relu is written
+// v < 0 ? 0 : v, as torch.relu behaves: a NaN mean (a NaN pixel) stays NaN (fmax would turn it into 0) and reaches every mean
+// it belongs to.
 __global__ __launch_bounds__(256) void ssim_finalize_kernel(const double2* __restrict__ means, int N, int C, ssim_final f,
                                                             double* __restrict__ out)
 {
@@ -205,12 +207,12 @@ __global__ __launch_bounds__(256) void ssim_finalize_kernel(const double2* __res
             v = 1.0;
             for (int s = 0; s < f.levels; ++s) {
                 const double2 m = means[(long long)s * NC + nc];
-                const double base = fmax(s < f.levels - 1 ? m.y : m.x, 0.0);      // relu(cs) below the last scale, relu(ssim) at it
-                v *= pow(base, (double)f.w[s]);
+                const double b = s < f.levels - 1 ? m.y : m.x;                      // relu(cs) below the last scale, relu(ssim) at it
+                v *= pow(b < 0.0 ? 0.0 : b, (double)f.w[s]);
             }
         } else {
             v = means[nc].x;
-            if (f.mode == 2) v = fmax(v, 0.0);
+            if (f.mode == 2) v = v < 0.0 ? 0.0 : v;
         }
         out[nc] = v;
     }
@@ -419,7 +421,7 @@ extern "C" int dc_ssim(const void* x, const void* y, int x_u8, const long long* 
                     stream);
 }
 
-extern "C" long long dc_psnr_ws_bytes(int N) { return N > 0 ? (long long)N * MT_PSNR_BLOCKS * 8 : -1; }
+extern "C" long long dc_psnr_ws_bytes(int N) { return N > 0 && N <= 65535 ? (long long)N * MT_PSNR_BLOCKS * 8 : -1; }
 
 extern "C" int dc_psnr(const void* x, const void* y, int x_u8, const long long* strides, int N, int C, int H, int W,
                        double data_range, void* ws, double* out, void* stream)

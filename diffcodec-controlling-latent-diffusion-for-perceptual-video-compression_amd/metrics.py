@@ -12,6 +12,9 @@ data_range=1.0)`, `10*log10(1/mse)`) and test_utils.py:23-55 (`psnr`, `ms_ssim(.
     MS-SSIM  relu(cs) at every scale but the last, relu(ssim) at the last; between scales avg_pool2d(2, padding=(H%2, W%2))
              with count_include_pad; the value is prod_s v_s^w_s per (n, c); size_average=True -> mean over (n, c),
              otherwise the mean over c ([N])
+    NaN      relu is v < 0 ? 0 : v, as torch.relu: a NaN pixel of a float operand makes the value of its (image, channel) plane NaN,
+             and with it the mean of that image and the overall mean, in ms_ssim and in ssim (nonnegative_ssim or not); the other
+             images are unaffected
 
 Parity with the library itself is unpinned (pytorch_msssim is not a dependency); tests/metrics_ref.py restates the rules above in
 fp64 and the device results are checked against that.  Deliberate differences from the library:

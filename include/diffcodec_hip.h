@@ -339,7 +339,9 @@ int dc_blend_tiles_ramp_u8(const float* tiles_nchw, const int* coords_dev, int T
  * bitwise reproducible, no float atomics.  win: host array of win_size (odd, <= 15) taps; weights: host array of `levels`
  * (<= 8) exponents.  ws: scratch of dc_ssim_ws_bytes(...) bytes (any contents).  out (device, fp64) [N*C + N + 1]: the value per
  * (n, c), its mean over c per n, the mean over (n, c).  Every scale must keep H, W >= win_size; dc_ssim_ws_bytes returns -1
- * for a shape / window / level count the kernels do not take. */
+ * for a shape / window / level count the kernels do not take (N * C <= 65535), and the launch then returns -1 and writes nothing.
+ * NaN rule: relu is v < 0 ? 0 : v (torch.relu), in dc_ms_ssim and in dc_ssim with nonnegative = 1: a NaN pixel of a float operand
+ * makes the value of its (n, c) plane, the mean of its sample and the overall mean NaN; other planes and samples are unaffected. */
 long long dc_ssim_ws_bytes(int N, int C, int H, int W, int win_size, int levels);
 int dc_ms_ssim(const void* x, const void* y, int x_u8, const long long* strides, int N, int C, int H, int W, const float* win,
                int win_size, const float* weights, int levels, float K1, float K2, float data_range, void* ws, double* out,
@@ -349,7 +351,7 @@ int dc_ssim(const void* x, const void* y, int x_u8, const long long* strides, in
             int win_size, float K1, float K2, float data_range, int nonnegative, void* ws, double* out, void* stream);
 /* PSNR per image: out (device, fp64) [N] = 10 log10(L^2 / mse) over the C*H*W elements of each image, +inf when mse = 0.  The
  * squared differences are summed exactly in 64-bit integers for uint8, in fp64 in a fixed order for fp32.
- * ws: dc_psnr_ws_bytes(N) bytes. */
+ * ws: dc_psnr_ws_bytes(N) bytes; 1 <= N <= 65535, otherwise dc_psnr_ws_bytes and the launch return -1. */
 long long dc_psnr_ws_bytes(int N);
 int dc_psnr(const void* x, const void* y, int x_u8, const long long* strides, int N, int C, int H, int W, double data_range,
             void* ws, double* out, void* stream);

@@ -703,6 +703,61 @@ def flow_resize_ref(flow2, h, w, div_x, div_y):
     return r, _f32_chain(12, a / div.abs())
 
 
+def flow_hw2_resize_scale_ref(src_hw2, th, tw):
+    """dc_flow_hw2_resize_scale_f32: F.interpolate(bilinear, align_corners=True) of a [H, W, 2] flow (the .flo payload layout) to
+    [2, th, tw], component 0 multiplied by tw / W and component 1 by th / H -> (r, S).
+    The source index follows the kernel and ATen in fp32: scale = (H - 1) / (th - 1) (0 when th = 1) and f = scale * o, each rounded
+    to fp32; i0 = floor(f), the weight l = f - i0 is then exact.  The multipliers are the fp32 values of tw / W and th / H.  Values in
+    fp64.  The value path has 12 roundings (1 - l twice, four products and two sums inside, two products and a sum outside, the
+    multiply) of running values below A = |mul| sum |weight tap|."""
+    hh, ww, _ = src_hw2.shape
+    dev = src_hw2.device
+    s = src_hw2.to(F64)
+
+    def axis(size_in, size_out):
+        scale = np.float32(size_in - 1) / np.float32(size_out - 1) if size_out > 1 else np.float32(0)
+        f = (scale * np.arange(size_out, dtype=np.float32)).astype(np.float32)
+        i0 = np.minimum(f.astype(np.int64), size_in - 1)
+        i1 = np.minimum(i0 + 1, size_in - 1)
+        lam = (f - i0.astype(np.float32)).astype(np.float64)
+        return torch.from_numpy(i0).to(dev), torch.from_numpy(i1).to(dev), torch.from_numpy(lam).to(dev)
+
+    y0, y1, ly = axis(hh, th)
+    x0, x1, lx = axis(ww, tw)
+    ly, lx = ly[:, None, None], lx[None, :, None]
+    hy, hx = 1 - ly, 1 - lx
+    s00, s01, s10, s11 = s[y0][:, x0], s[y0][:, x1], s[y1][:, x0], s[y1][:, x1]                 # [th, tw, 2]
+    mul = torch.tensor([float(np.float32(tw / ww)), float(np.float32(th / hh))], dtype=F64, device=dev)
+    r = (hy * (hx * s00 + lx * s01) + ly * (hx * s10 + lx * s11)) * mul
+    a = (hy * (hx * s00.abs() + lx * s01.abs()) + ly * (hx * s10.abs() + lx * s11.abs())) * mul.abs()
+    return r.permute(2, 0, 1).contiguous(), _f32_chain(12, a.permute(2, 0, 1).contiguous())
+
+
+def blend_tiles_ramp_ref(tiles, coords, h, w, feather, scale):
+    """dc_blend_tiles_ramp_u8 before its rounding: the weighted mean of the tiles covering each pixel, clipped to [0, 255], in fp64
+    -> [h, w, C].  Weight of a tile at a pixel = ramp_y ramp_x, ramp[i] = 0.5 - 0.5 cos(pi (i + 0.5) / feather) over the `feather`
+    pixels next to a tile edge that lies inside the frame, 1 elsewhere (the policy of tiling.merge_ramp, restated independently:
+    tiles [T, C, th, tw], coords (y1, y2, x1, x2))."""
+    t = tiles.detach().cpu().to(F64) * float(np.float32(scale))
+    c = t.shape[1]
+    acc, wsum = torch.zeros(c, h, w, dtype=F64), torch.zeros(h, w, dtype=F64)
+    ramp = torch.tensor([0.5 - 0.5 * math.cos(math.pi * (i + 0.5) / feather) for i in range(feather)], dtype=F64)
+
+    def axis(n, lo_inner, hi_inner):
+        v = torch.ones(n, dtype=F64)
+        if feather and lo_inner:
+            v[:feather] = ramp
+        if feather and hi_inner:
+            v[n - feather:] = ramp.flip(0)
+        return v
+
+    for k, (y1, y2, x1, x2) in enumerate(coords):
+        m = axis(y2 - y1, y1 > 0, y2 < h)[:, None] * axis(x2 - x1, x1 > 0, x2 < w)[None, :]
+        acc[:, y1:y2, x1:x2] += t[k] * m
+        wsum[y1:y2, x1:x2] += m
+    return (acc / wsum).clamp(0.0, 255.0).permute(1, 2, 0).contiguous()
+
+
 def fuse_warped_ref(wf, wl, cf, cb, of=None, ob=None):
     """dc_fuse_warped_f32 (extractors.py:297-310): a = max(cf, 0), b = max(cb, 0), fused = a / (a + b + 1e-6) wf + b / (a + b + 1e-6) wl,
     and 0.5 (wf + wl) where of + ob > 1.5 -> (r, S) [N, C, H, W].  Seven roundings (two sums in the denominator, two divides, two

@@ -6,12 +6,15 @@ Plain module (imported by tests/test_edge_coverage.py on the CPU and tests/test_
   pitched view) hold a NaN with a distinctive payload.  An output view is pre-filled with the same pattern, so an element the
   kernel never writes stays non-finite (L.check treats it as infinitely wrong); `bad()` lists every guard element that no longer
   holds the pattern, compared as integers.  A uint8 buffer holds the byte 0xA5 instead: a legitimate output value, so `unwritten()`
-  means nothing for it and such an output is compared in full.
+  means nothing for it and such an output is compared in full.  float64 (the metric outputs) holds a NaN compared as int64.
 * `conv_key` / `attention_key`: the kernel instance a launch runs, from the dispatcher's own queries (dc_conv_route and
   dc_conv_instance, dc_attention_route).
 * `f32_conv_key`: the same for the fp32 extractor conv (dc_conv3x3_f32_route).
 * `SPLAT_CASES`, `OCCLUSION_CASES`, `FLOW_RESIZE_CASES`, `FUSE_CASES`, `ELEMENTWISE_CASES`: the control stage (splat, occlusion
   mask, flow resize, fusion) and the plain elementwise launchers, with the generators of their inputs.
+* `SSIM_CASES`, `MS_SSIM_CASES`, `PSNR_CASES`, `METRIC_REFUSALS`: dc_ssim / dc_ms_ssim / dc_psnr at the window instances, tile,
+  wave and loop edges of csrc/metrics.hip, over operand forms (two stride sets) and value families, with `metric_inputs` /
+  `metric_operand`; `FDN_CASES`, `FLOW_HW2_CASES`, `PACK_CASES`, `BLEND_CASES`: the input-side and blend launchers.
 * `CONV_CASES`, `ATTN_CASES`, `NORM_CASES`, `F32_CONV_CASES`: the tables.  Every conv / attention case declares the instance it
   targets; tests/test_edge_coverage.py proves that every instance the dispatcher can reach has a case and that every case routes
   where it says."""
@@ -21,8 +24,9 @@ from dataclasses import dataclass
 import torch
 
 GUARD = 256                                   # guard elements on each side of a view
-NAN_BITS = {torch.bfloat16: 0x7FA5, torch.float32: 0x7FA5A5A5, torch.uint8: 0xA5}    # uint8 has no NaN: the byte 0xA5 stands in
-_INT = {torch.bfloat16: torch.int16, torch.float32: torch.int32, torch.uint8: torch.uint8}
+NAN_BITS = {torch.bfloat16: 0x7FA5, torch.float32: 0x7FA5A5A5, torch.uint8: 0xA5,    # uint8 has no NaN: the byte 0xA5 stands in
+            torch.float64: 0x7FFA5A5AA5A5A5A5}
+_INT = {torch.bfloat16: torch.int16, torch.float32: torch.int32, torch.uint8: torch.uint8, torch.float64: torch.int64}
 
 
 # ------------------------------------------------------------------------------------------ guarded buffers
@@ -78,7 +82,7 @@ class Guarded:
 def _signed(bits, dtype):
     if dtype == torch.uint8:
         return bits
-    w = 16 if dtype == torch.bfloat16 else 32
+    w = {torch.bfloat16: 16, torch.float32: 32, torch.float64: 64}[dtype]
     return bits - (1 << w) if bits >= 1 << (w - 1) else bits
 
 
@@ -882,3 +886,274 @@ def postprocess_input(n, c, h, w, xs):
     for off, v in ((0, -1.0), (1, 1.0), (2, -1.5), (3, 2.0), (4, -1.0000001), (5, 0.99999994)):
         flat[off::17] = v
     return x
+
+
+# ------------------------------------------------------------------------------------------ frame quality metrics
+# operand form -> (element type, storage of X, storage of Y).  nhwc / nchw: contiguous; pitched: NHWC rows of W C + 13 elements,
+# the gap holding the guard pattern (a window cropped from a wider frame).  `mixed` gives X and Y different stride sets.
+METRIC_FORMS = {"u8_nhwc": ("u8", "nhwc", "nhwc"), "u8_nchw": ("u8", "nchw", "nchw"), "f32_nchw": ("f32", "nchw", "nchw"),
+                "f32_view": ("f32", "nhwc", "nhwc"), "pitched": ("u8", "pitched", "pitched"), "mixed": ("f32", "nhwc", "nchw")}
+METRIC_FAMILIES_ALL = ("noisy", "identical", "constant", "anti", "extremes", "nan")
+K_DEFAULT, K_WIDE = (0.01, 0.03), (0.02, 0.05)
+PITCH_GAP = 13
+MS_WEIGHTS = {1: (1.0,), 2: (0.4, 0.6), 3: (0.2, 0.3, 0.5), 5: (0.0448, 0.2856, 0.3001, 0.2363, 0.1333),
+              8: (0.05, 0.1, 0.15, 0.2, 0.2, 0.15, 0.1, 0.05)}
+
+
+@dataclass(frozen=True)
+class MetricCase:
+    """One dc_ssim (levels = 0), dc_ms_ssim (levels >= 1, weights MS_WEIGHTS[levels]) or dc_psnr (ws = 0) launch."""
+    n: int
+    c: int
+    h: int
+    w: int
+    ws: int = 11
+    form: str = "u8_nhwc"
+    family: str = "noisy"
+    L: float = 255.0
+    K: tuple = K_DEFAULT
+    levels: int = 0
+    nonneg: bool = False
+    note: str = ""
+
+    @property
+    def dtype(self):
+        return METRIC_FORMS[self.form][0]
+
+    @property
+    def weights(self):
+        return MS_WEIGHTS[self.levels] if self.levels else None
+
+    @property
+    def exact(self):
+        """the value every output element must equal bit for bit, or None"""
+        if self.family == "identical":
+            return 1.0
+        if self.family == "anti" and (self.levels or self.nonneg):
+            return 0.0
+        return None
+
+    def label(self):
+        f = [f"ws{self.ws}"] * bool(self.ws) + [f"lv{self.levels}"] * bool(self.levels) + [self.form, self.family, f"L{self.L:g}"]
+        f += ["Kwide"] * (self.K != K_DEFAULT) + ["nonneg"] * self.nonneg
+        return f"{self.n}x{self.c}x{self.h}x{self.w}-" + "-".join(f)
+
+
+def ssim_instance(c):
+    return ("ssim", c.ws, c.dtype)
+
+
+def _ssim_cases():
+    forms_u8, forms_f32 = ("u8_nhwc", "u8_nchw", "pitched"), ("f32_nchw", "f32_view", "mixed")
+    out = []
+    for i, ws in enumerate((1, 3, 5, 7, 9, 11, 13, 15)):
+        for j, forms in enumerate((forms_u8, forms_f32)):
+            L = 255.0 if (j == 0 or i % 2) else 1.0
+            k = K_WIDE if (i + j) % 2 else K_DEFAULT
+            # one output pixel; the seam shape: 2 x 2 tiles, the last tile 1 column by 1 row
+            out.append(MetricCase(2, 1, ws, ws, ws, forms[i % 3], "noisy", L, k, nonneg=bool(i % 2), note="one output pixel"))
+            out.append(MetricCase(3, 2, 32 + ws, 64 + ws, ws, forms[(i + 1) % 3], "noisy", L, k, note="seam: Ho 33, Wo 65"))
+    out += [
+        MetricCase(1, 2, 42, 74, 11, "u8_nhwc", note="Ho 32, Wo 64: exactly one tile"),
+        MetricCase(1, 2, 42, 74, 11, "mixed", L=1.0, K=K_WIDE, note="Ho 32, Wo 64, two stride sets"),
+        MetricCase(1, 1, 18, 30, 11, "f32_nchw", L=1.0, note="Ho 8: exactly one wave's rows"),
+        MetricCase(2, 1, 19, 75, 11, "pitched", note="Ho 9, Wo 65"),
+        MetricCase(1, 1, 1, 16385, 1, "f32_nchw", note="257 tiles: the reduce kernel's second trip"),
+        MetricCase(1, 1, 1, 16385, 1, "u8_nchw", family="identical", note="257 tiles, exact"),
+        MetricCase(257, 1, 3, 3, 3, "u8_nhwc", note="N = 257: the finalize kernel's second trip"),
+        MetricCase(257, 1, 3, 3, 3, "f32_view", L=1.0, nonneg=True, note="N = 257"),
+        MetricCase(2, 4, 13, 20, 11, "u8_nhwc", note="C = 4"),
+        MetricCase(2, 4, 13, 20, 11, "mixed", note="C = 4, two stride sets"),
+    ]
+    # value families at a shape with a partial tile in each direction, nonnegative on and off
+    for fam in ("identical", "constant", "anti", "extremes", "nan"):
+        for nonneg in (False, True):
+            forms = ("f32_view", "mixed") if fam == "nan" else ("u8_nhwc", "f32_nchw")
+            L = 1.0 if (nonneg and fam != "nan") else 255.0
+            out.append(MetricCase(2, 3, 21, 70, 7, forms[int(nonneg)], fam, L, K_WIDE if nonneg else K_DEFAULT, nonneg=nonneg))
+    out += [MetricCase(2, 1, 5, 5, 5, "mixed", "nan", 1.0, note="one output pixel, NaN"),
+            MetricCase(2, 2, 5, 5, 5, "u8_nchw", "anti", nonneg=True, note="one output pixel, anti")]
+    return out
+
+
+def _ms_ssim_cases():
+    out = [
+        MetricCase(3, 2, 33, 35, 3, "u8_nhwc", levels=5, note="33 -> 17 -> 9 -> 5 -> 3, 35 -> 18 -> 9 -> 5 -> 3"),
+        MetricCase(3, 2, 33, 35, 3, "f32_view", L=1.0, K=K_WIDE, levels=5),
+        MetricCase(3, 2, 33, 35, 3, "mixed", "nan", levels=5),
+        MetricCase(3, 2, 33, 35, 3, "f32_nchw", "anti", 1.0, levels=5),
+        MetricCase(3, 2, 33, 35, 3, "u8_nchw", "identical", levels=5),
+        MetricCase(3, 2, 33, 35, 3, "pitched", "constant", levels=5),
+        MetricCase(3, 2, 33, 35, 3, "u8_nhwc", "extremes", levels=5),
+        MetricCase(1, 1, 225, 227, 15, "u8_nchw", levels=5, note="every scale ends at the 15-tap window"),
+        MetricCase(2, 3, 161, 161, 11, "mixed", levels=5, note="the smallest default-window frame"),
+        MetricCase(1, 3, 1, 1, 1, "f32_nchw", L=1.0, levels=8, note="eight levels of one pixel"),
+        MetricCase(2, 1, 129, 2, 1, "u8_nhwc", levels=8, note="eight levels: 129 -> 65 -> 33 -> 17 -> 9 -> 5 -> 3 -> 2"),
+        MetricCase(1, 3, 47, 90, 7, "f32_view", levels=1, note="one level through dc_ms_ssim"),
+        MetricCase(1, 1, 45, 77, 5, "pitched", levels=3, note="three weights"),
+    ]
+    for h, w in ((23, 24), (24, 23), (23, 23), (24, 24)):            # the first pool of each element type meets every padding parity
+        out.append(MetricCase(2, 2, h, w, 5, "u8_nhwc", levels=2))
+        out.append(MetricCase(2, 2, h, w, 5, "mixed", L=1.0, K=K_WIDE, levels=2))
+    return out
+
+
+def _psnr_cases():
+    shapes = [(3, 1, 1, 1), (3, 3, 21, 255), (3, 1, 64, 256), (3, 5, 13, 257), (3, 3, 43, 513), (3, 1, 63, 1), (3, 1, 129, 255)]
+    forms = list(METRIC_FORMS)
+    out = [MetricCase(*s, 0, forms[i % 6], "noisy", 255.0 if METRIC_FORMS[forms[i % 6]][0] == "u8" or i % 2 else 1.0) for i, s in enumerate(shapes)]
+    out += [MetricCase(3, 3, 43, 257, 0, f, "noisy") for f in forms]           # every form at C H = 129, W = 257
+    out += [MetricCase(3, 3, 43, 513, 0, "u8_nhwc", "extremes", note="every |d| = 255"),
+            MetricCase(3, 1, 65, 257, 0, "u8_nchw", "onepixel", note="one pixel differs by 1"),
+            MetricCase(3, 1, 65, 257, 0, "f32_view", "onepixel", 1.0),
+            MetricCase(3, 1, 65, 257, 0, "pitched", "identical"),
+            MetricCase(3, 2, 32, 256, 0, "mixed", "identical", 1.0)]
+    return out
+
+
+SSIM_CASES, MS_SSIM_CASES, PSNR_CASES = _ssim_cases(), _ms_ssim_cases(), _psnr_cases()
+
+
+def metric_window(ws, sigma=1.5):
+    """the fp32 taps a launch is given (diffcodec_amd.metrics.gaussian_window, rounded to fp32)"""
+    c = torch.arange(ws, dtype=torch.float64) - ws // 2
+    g = torch.exp(-(c ** 2) / (2.0 * sigma * sigma))
+    return (g / g.sum()).float()
+
+
+def nan_position(c):
+    """(n, channel, y, x) of the NaN pixel of the `nan` family: the last channel of sample min(1, N - 1)"""
+    return (min(1, c.n - 1), c.c - 1, c.h // 2, c.w // 2)
+
+
+def metric_inputs(c, seed):
+    """logical NCHW (X, Y) of a case on the CPU, uint8 or fp32 in [0, L]:
+      noisy      a smooth field (a sinusoid of random phase per plane plus texture) and a noisy copy;
+      identical  Y = X;                      constant  two different constants (0.3 L, 0.6 L);
+      anti       Y = L - X (cs < 0);         extremes  0 against L;
+      nan        noisy with one NaN pixel in X (nan_position; float forms only);
+      onepixel   Y = X but for one element per sample, off by 1 (uint8) or L / 255 (PSNR only)."""
+    gen = torch.Generator().manual_seed(17000 + seed)
+    shape = (c.n, c.c, c.h, c.w)
+    gy, gx = torch.arange(c.h, dtype=torch.float32)[:, None], torch.arange(c.w, dtype=torch.float32)[None, :]
+    x = 0.5 + 0.3 * torch.sin(0.37 * gx + 0.23 * gy + 6.28 * torch.rand(c.n, c.c, 1, 1, generator=gen))
+    x = (x + 0.08 * torch.randn(shape, generator=gen)).clamp(0, 1)
+    y = (x + 0.05 * torch.randn(shape, generator=gen)).clamp(0, 1)
+    if c.family == "constant":
+        x, y = torch.full(shape, 0.3), torch.full(shape, 0.6)
+    elif c.family == "extremes":
+        x, y = torch.zeros(shape), torch.ones(shape)
+    u8 = c.dtype == "u8"
+    x, y = ((t * 255.0).round().to(torch.uint8) if u8 else (t * c.L).float() for t in (x, y))
+    if c.family in ("identical", "onepixel"):
+        y = x.clone()
+    if c.family == "onepixel":
+        for n in range(c.n):
+            v = y[n, c.c - 1, c.h - 1, c.w - 1 - n]
+            y[n, c.c - 1, c.h - 1, c.w - 1 - n] = (v + 1 if v < 255 else v - 1) if u8 else v + (c.L / 255 if v < c.L / 2 else -c.L / 255)
+    if c.family == "anti":
+        y = 255 - x if u8 else (c.L - x).float()
+    if c.family == "nan":
+        assert not u8 and c.n >= 2
+        x[nan_position(c)] = math.nan
+    return x, y
+
+
+def metric_operand(t, layout, device):
+    """a logical NCHW tensor stored as `layout` in a Guarded buffer -> (Guarded, element strides (n, c, h, w)); the operand's
+    address is the view's data_ptr()"""
+    n, c, h, w = t.shape
+    if layout == "nchw":
+        g, strides = Guarded((n, c, h, w), t.dtype, device), (c * h * w, h * w, w, 1)
+        g.fill(t)
+    elif layout == "nhwc":
+        g, strides = Guarded((n, h, w, c), t.dtype, device), (h * w * c, 1, w * c, c)
+        g.fill(t.permute(0, 2, 3, 1))
+    else:
+        assert layout == "pitched", layout
+        pitch = w * c + PITCH_GAP
+        g, strides = Guarded((n, h, w * c), t.dtype, device, pitch=pitch), (h * pitch, 1, pitch, c)
+        g.fill(t.permute(0, 2, 3, 1).reshape(n, h, w * c))
+    return g, strides
+
+
+def metric_read(g, shape, strides):
+    """the logical NCHW tensor a kernel reads from a metric_operand through `strides`"""
+    return torch.as_strided(g.base, shape, strides, g.guard)
+
+
+# (label, (N, C, H, W, win_size, levels)): dc_ssim_ws_bytes and the launch return -1 and the launch writes nothing
+METRIC_REFUSALS = [("even window", (1, 1, 32, 32, 10, 1)), ("window 17", (1, 1, 32, 32, 17, 1)), ("levels 0", (1, 1, 32, 32, 3, 0)),
+                   ("levels 9", (1, 1, 1024, 1024, 1, 9)), ("a scale below the window", (1, 1, 20, 20, 11, 2)),
+                   ("N C = 65536", (65536, 1, 3, 3, 3, 1)), ("N C = 65536 by channels", (256, 256, 3, 3, 3, 1))]
+
+
+# ------------------------------------------------------------------------------------------ FDN modulate, input side, tile blend
+FDN_VEC_CAP = 4096 * 256                      # 8-channel vectors one trip of fdn_modulate_kernel covers
+FDN_CASES = [(3, 2, 63, 64), (1, 1, 1, 8), (4, 4, 16, 320), (3, 1, 7, 1288), (3, 2, 4096, 704)]      # (N, Bp, HW, C)
+FLOW_HW2_CASES = [(270, 480, 64, 64), (1, 7, 5, 9), (7, 1, 9, 5), (5, 3, 1, 1), (64, 96, 33, 1), (9, 9, 9, 9), (3, 5, 97, 131)]   # (H, W, th, tw)
+PACK_CASES = [(1, 1), (37, 53), (1450, 1450)]                                                        # 1450^2 = 2,102,500 > GRID_ELEMS
+
+
+def fdn_inputs(case, seed):
+    """fp32 (x [N, HW, C], ab [N, C, 2], gamma, beta [Bp, HW, C]) on the CPU"""
+    n, bp, hw, c = case
+    gen = torch.Generator().manual_seed(18000 + seed)
+    x = 2 * torch.randn(n, hw, c, generator=gen) + 0.5
+    ab = torch.stack([1 + 0.3 * torch.randn(n, c, generator=gen), 0.5 * torch.randn(n, c, generator=gen)], -1)
+    return x, ab, 0.5 * torch.randn(bp, hw, c, generator=gen), 0.5 * torch.randn(bp, hw, c, generator=gen)
+
+
+def flow_hw2_input(case, seed):
+    """fp32 [H, W, 2] (the .flo payload layout)"""
+    return 6 * torch.randn(case[0], case[1], 2, generator=torch.Generator().manual_seed(19000 + seed)) + 0.5
+
+
+def pack_inputs(case):
+    """two uint8 [H, W, 3] images that together hold every byte value (each does, from 86 pixels up)"""
+    h, w = case
+    i = torch.arange(h * w * 3)
+    a = ((i * 7 + 3) % 256).to(torch.uint8).reshape(h, w, 3)
+    b = (255 - (i * 11) % 256).to(torch.uint8).reshape(h, w, 3)
+    return a, b
+
+
+@dataclass(frozen=True)
+class BlendCase:
+    """One dc_blend_tiles_ramp_u8 launch: tiles [T, C, th, tw] on the windows `coords` (y1, y2, x1, x2) of an H x W frame."""
+    name: str
+    c: int
+    h: int
+    w: int
+    th: int
+    tw: int
+    feather: int
+    coords: tuple
+    scale: float = 255.0
+    values: str = "unit"           # unit: [0, 1];  ties: k + 0.5 (scale 1);  clip: [-0.3, 1.3]
+
+
+def _grid_coords(h, w, th, tw, ys, xs):
+    return tuple((y, y + th, x, x + tw) for y in ys for x in xs)
+
+
+BLEND_CASES = [
+    BlendCase("single-window", 3, 20, 28, 20, 28, 4, ((0, 20, 0, 28),)),
+    BlendCase("c1-abutting-feather0", 1, 16, 24, 8, 12, 0, _grid_coords(16, 24, 8, 12, (0, 8), (0, 12))),
+    BlendCase("c2-feather-half-tile", 2, 12, 20, 8, 8, 4, _grid_coords(12, 20, 8, 8, (0, 4), (0, 4, 8, 12))),
+    BlendCase("c4-3x3-nonsquare", 4, 40, 57, 20, 27, 5, _grid_coords(40, 57, 20, 27, (0, 10, 20), (0, 15, 30))),
+    BlendCase("c3-ties", 3, 24, 24, 16, 16, 0, _grid_coords(24, 24, 16, 16, (0, 8), (0, 8)), 1.0, "ties"),
+    BlendCase("c3-clip", 3, 40, 57, 20, 27, 5, _grid_coords(40, 57, 20, 27, (0, 10, 20), (0, 15, 30)), 255.0, "clip"),
+]
+
+
+def blend_inputs(case, seed):
+    """fp32 tiles [T, C, th, tw] on the CPU.  ties: every tile of a window position holds the same k + 0.5 (k cycling 0 .. 254 by
+    pixel of the frame), so that with feather = 0 every weighted mean is exactly k + 0.5 and rint must round to even."""
+    t = len(case.coords)
+    gen = torch.Generator().manual_seed(20000 + seed)
+    if case.values == "ties":
+        frame = ((torch.arange(case.h * case.w * case.c) * 3) % 255).float().reshape(case.c, case.h, case.w) + 0.5
+        return torch.stack([frame[:, y1:y2, x1:x2] for (y1, y2, x1, x2) in case.coords]).contiguous()
+    x = torch.rand(t, case.c, case.th, case.tw, generator=gen)
+    return x * 1.6 - 0.3 if case.values == "clip" else x

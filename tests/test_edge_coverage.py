@@ -1,6 +1,7 @@
 """CPU: the edge-case tables of tests/edge_cases.py cover every kernel instance the dispatchers can reach, every case routes to the
 instance it declares, and the checks the GPU edge tests rely on (guarded buffers, the flat and peaked attention input families held
 to oracle/launch_ref.py) reject the faults they are there to catch."""
+import functools
 import json
 import math
 import os
@@ -487,3 +488,250 @@ def test_uint8_guard_flags_writes_outside_the_view():
     assert g.bad() and g.bad()[0][0] == "after"
     with pytest.raises(AssertionError):
         g.assert_intact("u8")
+
+
+# ------------------------------------------------------------------------------------------ metric tables
+def metric_instances():
+    """the instances the metric tables must reach: ssim_scale_kernel<T, WS> per window and element type, every level count of the
+    MS-SSIM table's weights, both PSNR element types"""
+    return ([("ssim", ws, t) for ws in range(1, 16, 2) for t in ("u8", "f32")] + [("ms_ssim", lv) for lv in sorted(E.MS_WEIGHTS)]
+            + [("psnr", t) for t in ("u8", "f32")])
+
+
+def metric_uncovered(ssim, ms, psnr):
+    have = {E.ssim_instance(c) for c in ssim} | {("ms_ssim", c.levels) for c in ms} | {("psnr", c.dtype) for c in psnr}
+    return [str(k) for k in metric_instances() if k not in have]
+
+
+def test_every_metric_instance_has_a_case_and_removing_it_names_the_instance():
+    assert metric_uncovered(E.SSIM_CASES, E.MS_SSIM_CASES, E.PSNR_CASES) == []
+    assert sorted(E.MS_WEIGHTS) == [1, 2, 3, 5, 8] and all(len(w) == k for k, w in E.MS_WEIGHTS.items())
+    tables = dict(ssim=E.SSIM_CASES, ms=E.MS_SSIM_CASES, psnr=E.PSNR_CASES)
+    key = dict(ssim=E.ssim_instance, ms=lambda c: ("ms_ssim", c.levels), psnr=lambda c: ("psnr", c.dtype))
+    soles = 0
+    for name, cases in tables.items():
+        for k in {key[name](c) for c in cases}:                      # without the cases of an instance, exactly that one is named
+            rest = dict(tables, **{name: [c for c in cases if key[name](c) != k]})
+            assert metric_uncovered(**rest) == [str(k)]
+        count = {}
+        for c in cases:
+            count[key[name](c)] = count.get(key[name](c), 0) + 1
+        for i, c in enumerate(cases):
+            if count[key[name](c)] == 1:
+                soles += 1
+                assert metric_uncovered(**dict(tables, **{name: cases[:i] + cases[i + 1:]})) == [str(key[name](c))]
+    assert soles >= 2                                                 # the level counts 1 and 3 have one case each
+
+
+def test_metric_tables_span_the_tile_loop_stride_and_value_edges():
+    """the tables still hold what they were built for (the shapes are the smallest at which each mechanism of csrc/metrics.hip can
+    go wrong: 64 x 32 output tiles, 8 rows per wave, 256-wide loops over partials and over N, PSNR rows striding by 64 and columns
+    by 256)"""
+    ss, ms, ps = E.SSIM_CASES, E.MS_SSIM_CASES, E.PSNR_CASES
+    out = lambda c: (c.h - c.ws + 1, c.w - c.ws + 1)
+    for ws in range(1, 16, 2):
+        for t in ("u8", "f32"):
+            mine = [c for c in ss if E.ssim_instance(c) == ("ssim", ws, t)]
+            assert any(out(c) == (1, 1) for c in mine), (ws, t)                                   # one output pixel
+            assert any(out(c) == (33, 65) and (c.n, c.c) == (3, 2) for c in mine), (ws, t)        # 2 x 2 tiles, the last 1 x 1
+    eleven = [c for c in ss if c.ws == 11]
+    assert {(32, 64), (8, 20), (9, 65)} <= {out(c) for c in eleven} and any(c.c == 4 for c in eleven)
+    assert any((out(c)[1] + 63) // 64 > 256 for c in ss)                                           # the reduce kernel's second trip
+    assert any(c.n * c.c > 256 and c.n > 256 for c in ss)                                          # the finalize kernel's second trip
+    assert {c.nonneg for c in ss} == {False, True}
+    for table in (ss, ms):
+        assert {c.form for c in table} == set(E.METRIC_FORMS)
+        assert {c.family for c in table} == set(E.METRIC_FAMILIES_ALL)
+        assert {c.L for c in table} == {255.0, 1.0} and {c.K for c in table} == {E.K_DEFAULT, E.K_WIDE}
+        assert all(c.dtype == "f32" and c.n >= 2 for c in table if c.family == "nan")
+        assert all(c.L == 255.0 for c in table if c.dtype == "u8")
+        assert all(c.ws >= 3 for c in table if c.family == "anti")                                # ws = 1 has cs = 1 identically
+    assert max(c.n * c.c * c.h * c.w for c in ss + ms) == 2 * 3 * 161 * 161                        # nothing above the smallest default-window frame
+    shapes = {(c.n, c.c, c.h, c.w, c.ws, c.levels, c.form) for c in ms}
+    assert {(3, 2, 33, 35, 3, 5, "u8_nhwc"), (1, 1, 225, 227, 15, 5, "u8_nchw"), (2, 3, 161, 161, 11, 5, "mixed"), (1, 3, 1, 1, 1, 8, "f32_nchw"),
+            (2, 1, 129, 2, 1, 8, "u8_nhwc"), (1, 3, 47, 90, 7, 1, "f32_view"), (1, 1, 45, 77, 5, 3, "pitched")} <= shapes
+    for hw in ((23, 24), (24, 23), (23, 23), (24, 24)):                                            # every padding parity of the first pool
+        assert {c.dtype for c in ms if (c.h, c.w) == hw and c.levels == 2} == {"u8", "f32"}
+    from diffcodec_amd import lib as l
+    for c in ss + ms:                                                                              # the launcher takes every case
+        assert l.load().dc_ssim_ws_bytes(c.n, c.c, c.h, c.w, c.ws, c.levels or 1) > 0, c.label()
+    assert {c.c * c.h for c in ps} >= {1, 63, 64, 65, 129} and {c.w for c in ps} >= {1, 255, 256, 257, 513}
+    assert all(c.n == 3 for c in ps) and {c.form for c in ps} == set(E.METRIC_FORMS)
+    assert {"extremes", "onepixel", "identical"} <= {c.family for c in ps}
+    assert any(c.family == "extremes" and c.dtype == "u8" for c in ps)
+    labels = [c.label() for c in ss + ms + ps]
+    assert len(set(labels)) == len(labels)
+
+
+def test_metric_refusals_are_refused_by_the_size_query(lib):
+    for label, args in E.METRIC_REFUSALS:
+        assert lib.load().dc_ssim_ws_bytes(*args) == -1, label
+    assert {a[4] for _, a in E.METRIC_REFUSALS} >= {10, 17} and {a[5] for _, a in E.METRIC_REFUSALS} >= {0, 9}
+    assert any(a[0] * a[1] == 65536 for _, a in E.METRIC_REFUSALS)
+    assert lib.load().dc_psnr_ws_bytes(0) == -1 and lib.load().dc_psnr_ws_bytes(65536) == -1 and lib.load().dc_psnr_ws_bytes(3) == 3 * 512
+
+
+def test_float64_guard_flags_writes_outside_the_view_and_unwritten_elements():
+    g = E.Guarded((7,), torch.float64, "cpu")
+    assert g.bad() == [] and g.unwritten() == 7 and bool(torch.isnan(g.base).all())
+    g.view[:6] = torch.arange(6, dtype=F64)
+    g.view[2] = math.nan                                   # a NaN result is not the pattern
+    assert g.unwritten() == 1 and g.bad() == []
+    g.view[6] = math.inf
+    assert g.unwritten() == 0
+    for where, idx in (("before", g.guard - 1), ("after", g.guard + 7)):
+        h = E.Guarded((7,), torch.float64, "cpu")
+        h.base[idx] = 0.0
+        assert h.bad() and h.bad()[0][0] == where
+        with pytest.raises(AssertionError):
+            h.assert_intact("out")
+    h = E.Guarded((7,), torch.float64, "cpu")
+    h.base[3] = math.nan                                   # another NaN in a guard element is a write
+    assert h.bad() == [("before", 3 - h.guard)]
+
+
+def test_new_launcher_tables_span_their_edges():
+    """FDN modulate: one vector, C off a multiple of 64, Bp in {1, N, a divisor}, exactly one case past the 4096 x 256 cap; the
+    .flo resize: H = 1, W = 1, a 1 x 1 and a one-column target, identity, up and down; the pack: one pixel and one case past a
+    grid; the blend: every C, a single window, feather 0 and 2 feather = tile, th != tw with four-fold corners, ties and clipping"""
+    vec = [n * hw * (c // 8) for n, _, hw, c in E.FDN_CASES]
+    assert sum(v > E.FDN_VEC_CAP for v in vec) == 1 and min(vec) == 1 and all(c % 8 == 0 for *_, c in E.FDN_CASES)
+    assert any(c % 64 for *_, c in E.FDN_CASES) and any(bp == 1 < n for n, bp, _, _ in E.FDN_CASES)
+    assert any(bp == n > 1 for n, bp, _, _ in E.FDN_CASES) and any(n % bp for n, bp, _, _ in E.FDN_CASES)
+    fl = E.FLOW_HW2_CASES
+    assert any(h == 1 for h, *_ in fl) and any(w == 1 for _, w, _, _ in fl) and (5, 3, 1, 1) in fl and any(tw == 1 < th for _, _, th, tw in fl)
+    assert any((h, w) == (th, tw) for h, w, th, tw in fl) and any(th > h and tw > w for h, w, th, tw in fl) and any(th < h for h, w, th, tw in fl)
+    assert (1, 1) in E.PACK_CASES and sum(h * w > E.GRID_ELEMS for h, w in E.PACK_CASES) == 1
+    bl = E.BLEND_CASES
+    assert {c.c for c in bl} == {1, 2, 3, 4} and any(len(c.coords) == 1 and (c.th, c.tw) == (c.h, c.w) for c in bl)
+    assert any(c.feather == 0 and len(c.coords) > 1 for c in bl) and any(2 * c.feather == c.th for c in bl)
+    assert any(c.th != c.tw and c.h != c.w and len(c.coords) == 9 for c in bl)
+    assert any(c.values == "ties" and c.scale == 1.0 and c.feather == 0 for c in bl) and any(c.values == "clip" for c in bl)
+    for c in bl:
+        cover = torch.zeros(c.h, c.w)
+        for (y1, y2, x1, x2) in c.coords:
+            assert (y2 - y1, x2 - x1) == (c.th, c.tw) and 0 <= y1 and y2 <= c.h and 0 <= x1 and x2 <= c.w
+            cover[y1:y2, x1:x2] += 1
+        assert cover.min() >= 1 and (len(c.coords) != 9 or cover.max() == 4), c.name
+    t = E.blend_inputs(next(c for c in bl if c.values == "clip"), 0)
+    assert bool((t < 0).any()) and bool((t > 1).any())
+
+
+# ------------------------------------------------------------------------------------------ the census of launchers
+_EDGES, _METRICS = "test_gpu_edges", "test_gpu_metrics"
+# C name -> (test module, token[, holder]).  token = the C name: the module holds a literal lib.call of it.  Otherwise token = the
+# name under which the module reaches a package wrapper, and holder = the package function ("f" or "Class.f") that must hold the
+# literal lib.call of the C name.
+LAUNCHER_TESTS = {n: (_EDGES, n) for n in (
+    "dc_splat_soft_f32", "dc_splat_sum_f32", "dc_occlusion_mask_f32", "dc_flow_resize_normalize_f32", "dc_flow_resize_divide_f32",
+    "dc_fuse_warped_f32", "dc_conv3x3_nchw_f32", "dc_nchw_f32_to_nhwc_bf16", "dc_nhwc_bf16_to_nchw_f32", "dc_nhwc_f32_to_nchw_f32",
+    "dc_f32_to_bf16", "dc_row_stats_bf16", "dc_ln_finalize", "dc_conv_small_cin_bf16", "dc_conv_small_cout_bf16", "dc_gn_stats_nhwc_bf16",
+    "dc_gn_finalize", "dc_gn_direct_nhwc_bf16", "dc_gn_apply_nhwc_bf16", "dc_fdn_modulate_nhwc_bf16", "dc_layernorm_bf16",
+    "dc_attention_bf16", "dc_attention_causal_small_bf16", "dc_embed_tokens_bf16", "dc_softmax_rows_f32_to_bf16",
+    "dc_timestep_embedding_f32", "dc_freeu_lowfreq_nhwc_bf16", "dc_freeu_backbone_nhwc_bf16", "dc_lincomb4_f32", "dc_transpose_bf16",
+    "dc_vae_sample_latents", "dc_silu_f32", "dc_add_bf16", "dc_add_f32", "dc_postprocess_image", "dc_flow_hw2_resize_scale_f32",
+    "dc_pack_sixch_u8_f32", "dc_blend_tiles_ramp_u8")}
+LAUNCHER_TESTS.update({
+    "dc_conv_igemm_bf16": (_EDGES, "conv", "conv"),                       # the descriptor is built by ops.conv
+    "dc_cfg_ddim_step": (_EDGES, "cfg_ddim_step", "cfg_ddim_step"),
+    "dc_cfg_unipc_step": (_EDGES, "cfg_unipc_step", "cfg_unipc_step"),
+    "dc_latents_to_model_input": (_EDGES, "latents_to_model_input", "latents_to_model_input"),
+    "dc_ssim": (_METRICS, "dc_ssim"), "dc_ms_ssim": (_METRICS, "dc_ms_ssim"), "dc_psnr": (_METRICS, "dc_psnr"),
+    "dc_splat_norm_f32": ("test_gpu_softsplat", "dc_splat_norm_f32"),
+    "dc_splat_ingrad_f32": ("test_gpu_softsplat", "dc_splat_ingrad_f32"),
+    "dc_splat_flowgrad_f32": ("test_gpu_softsplat", "dc_splat_flowgrad_f32"),
+    "dc_resample_u8": ("test_gpu_resample", "dc_resample_u8"),
+    "dc_lpips_alex": ("test_gpu_lpips", "LPIPS", "LPIPS.__call__"),
+    "dc_lpips_alex_features": ("test_gpu_lpips", "features", "LPIPS.features"),
+    "dc_lpips_conv": ("test_gpu_lpips", "dc_lpips_conv"),
+    "dc_fid_features": ("test_gpu_fid", "features", "FrechetInceptionDistance.features"),
+    "dc_fid_maps": ("test_gpu_fid", "maps", "FrechetInceptionDistance.maps"),
+    "dc_fid_conv": ("test_gpu_fid", "dc_fid_conv"),
+    "dc_fid_accumulate": ("test_gpu_fid", "update_features", "FrechetInceptionDistance.update_features"),
+    "dc_fvd_features": ("test_gpu_fvd", "features", "FrechetVideoDistance.features"),
+    "dc_fvd_endpoints": ("test_gpu_fvd", "endpoints", "FrechetVideoDistance.endpoints"),
+    "dc_fvd_preprocess": ("test_gpu_fvd", "preprocess", "FrechetVideoDistance.preprocess"),
+    "dc_fvd_conv": ("test_gpu_fvd", "dc_fvd_conv"), "dc_fvd_maxpool": ("test_gpu_fvd", "dc_fvd_maxpool"),
+})
+NOT_LAUNCHERS = ("dc_conv_instance", "dc_gn_stats_chunks", "dc_gemm_row_stats_parts", "dc_conv_gn_part_chunks")
+
+
+def is_launcher(name):
+    return not (name.endswith(("_ws_bytes", "_route", "_weight_floats")) or name in NOT_LAUNCHERS)
+
+
+@functools.lru_cache(maxsize=None)
+def _names_used(path):
+    """identifiers and attribute names of a module's syntax tree (a name in a comment or a string does not count)"""
+    import ast
+    tree = ast.parse(open(path).read())
+    return {n.attr for n in ast.walk(tree) if isinstance(n, ast.Attribute)} | {n.id for n in ast.walk(tree) if isinstance(n, ast.Name)}
+
+
+@functools.lru_cache(maxsize=None)
+def _package_holders(cname):
+    """the package functions ("f", "Class.f") whose body holds a literal lib.call of `cname`"""
+    import ast
+    import glob
+    from diffcodec_amd import lib as l
+    found = set()
+
+    def calls(fn):
+        return any(isinstance(n, ast.Call) and isinstance(n.func, ast.Attribute) and n.func.attr == "call" and n.args and
+                   isinstance(n.args[0], ast.Constant) and n.args[0].value == cname for n in ast.walk(fn))
+
+    for path in glob.glob(os.path.join(os.path.dirname(l.__file__), "*.py")):
+        tree = ast.parse(open(path).read())
+        for node in tree.body:
+            if isinstance(node, ast.FunctionDef) and calls(node):
+                found.add(node.name)
+            if isinstance(node, ast.ClassDef):
+                found |= {f"{node.name}.{f.name}" for f in node.body if isinstance(f, ast.FunctionDef) and calls(f)}
+    return found
+
+
+@functools.lru_cache(maxsize=None)
+def _lib_calls_cached(path):
+    return frozenset(_lib_calls(path))
+
+
+def launcher_census(table):
+    """-> the complaints, one per launcher of lib.SIGNATURES whose entry is missing or does not hold"""
+    from diffcodec_amd import lib as l
+    out = []
+    for name in l.SIGNATURES:
+        if not is_launcher(name):
+            continue
+        if name not in table:
+            out.append(f"{name}: no entry in LAUNCHER_TESTS")
+            continue
+        module, token, *holder = table[name]
+        path = os.path.join(ROOT, "tests", module + ".py")
+        if not os.path.exists(path):
+            out.append(f"{name}: tests/{module}.py does not exist")
+        elif token == name:
+            if name not in _lib_calls_cached(path):
+                out.append(f"{name}: no literal lib.call in tests/{module}.py")
+        elif not holder or holder[0] not in _package_holders(name):
+            out.append(f"{name}: the package function {holder[0] if holder else '?'} holds no literal lib.call of it")
+        elif token not in _names_used(path):
+            out.append(f"{name}: tests/{module}.py never names the wrapper {token}")
+    out += [f"{name}: an entry for something that is not a launcher of lib.SIGNATURES" for name in table
+            if name not in l.SIGNATURES or not is_launcher(name)]
+    return out
+
+
+def test_every_launcher_of_the_abi_has_a_gpu_test():
+    assert launcher_census(LAUNCHER_TESTS) == []
+
+
+def test_removing_a_census_entry_names_the_launcher():
+    from diffcodec_amd import lib as l
+    assert sum(is_launcher(n) for n in l.SIGNATURES) == len(LAUNCHER_TESTS)
+    for name in LAUNCHER_TESTS:
+        rest = {k: v for k, v in LAUNCHER_TESTS.items() if k != name}
+        got = launcher_census(rest)
+        assert len(got) == 1 and got[0].startswith(name + ":"), (name, got)
+    broken = dict(LAUNCHER_TESTS, dc_psnr=("test_gpu_ops", "dc_psnr"), dc_fid_maps=("test_gpu_fid", "maps", "FrechetInceptionDistance.features"),
+                  dc_fvd_features=("test_gpu_lpips", "endpoints", "FrechetVideoDistance.features"))
+    assert [g.split(":")[0] for g in launcher_census(broken)] == ["dc_psnr", "dc_fid_maps", "dc_fvd_features"]

@@ -1,6 +1,7 @@
 """GPU: every case of tests/edge_cases.py — each conv / linear, fp32 extractor conv and attention kernel instance the dispatchers can
 reach, the normalisation kernels at their template and chunking edges, the fused loop's state kernels, the control stage (splat,
-occlusion mask, flow resize, fusion) and the plain elementwise launchers — launched on guarded operands and outputs, its route asserted first,
+occlusion mask, flow resize, fusion), the plain elementwise launchers, FDN modulate, the input-side launchers (flow resize from the
+.flo layout, the six-channel pack) and the tile blend — launched on guarded operands and outputs, its route asserted first,
 its output held to the fp64 reference of oracle/launch_ref.py with L.check, its guards checked bit for bit, and a second launch
 into a second guarded output required to be bitwise equal.  Worst err/tol per instance goes to `record`."""
 import math
@@ -935,3 +936,108 @@ def test_postprocess_image_edge(ops, record, n, c, h, w, xs, f32, u8):
     o32 = runs[0][0].view if f32 else own32
     _note(record, ("postprocess_image",), L.check(o32, r, s, F32), what)
     assert float(o32.min()) == 0.0 and float(o32.max()) == 1.0
+
+
+# ------------------------------------------------------------------------------------------ FDN modulate, input side, tile blend
+@pytest.mark.parametrize("i", range(len(E.FDN_CASES)), ids=["x".join(map(str, c)) for c in E.FDN_CASES])
+def test_fdn_modulate_edge(ops, record, i):
+    """dc_fdn_modulate_nhwc_bf16: one vector, C off 64, Bp = N, Bp = 1, and 1,081,344 vectors (past the 4096 x 256 grid cap: sampled
+    rows, whose last block lies in the second trip)"""
+    from diffcodec_amd import lib
+    case = E.FDN_CASES[i]
+    n, bp, hw, c = case
+    what = f"fdn_modulate {case}"
+    x, ab, gam, bet = E.fdn_inputs(case, i)
+    gx, gg, gb = (_g(tuple(t.shape), BF, t.to(DEV)) for t in (x, gam, bet))
+    gab = _g((n, c, 2), F32, ab.to(DEV))
+
+    def launch(out):
+        lib.call("dc_fdn_modulate_nhwc_bf16", gx.view.data_ptr(), gab.view.data_ptr(), gg.view.data_ptr(), gb.view.data_ptr(),
+                 out.data_ptr(), n, bp, hw, c, _st())
+
+    go = _twice(launch, (n, hw, c), BF, [gx, gab, gg, gb], what)
+    large = n * hw * (c // 8) > E.FDN_VEC_CAP
+    rows = L.sample_rows(n * hw) if large else torch.arange(n * hw)
+    if large:
+        assert int(rows.max()) * (c // 8) >= E.FDN_VEC_CAP                   # rows of the second trip are sampled
+    r, s = L.fdn_modulate_ref(gx.view, gab.view, gg.view, gb.view, rows)
+    _note(record, ("fdn_modulate",), L.check(go.view.reshape(n * hw, c)[rows.to(DEV)], r, s, BF), what)
+    assert torch.equal(ops.fdn_modulate(gx.view, gab.view, gg.view, gb.view), go.view), f"{what}: the ops wrapper launches something else"
+
+
+@pytest.mark.parametrize("case", E.FLOW_HW2_CASES, ids=lambda c: "x".join(map(str, c)))
+def test_flow_hw2_resize_scale_edge(ops, record, case):
+    """dc_flow_hw2_resize_scale_f32 on a guarded [H, W, 2] source: a float2 read one pair past the end gives a non-finite output"""
+    from diffcodec_amd import lib
+    hh, ww, th, tw = case
+    what = f"flow_hw2_resize_scale {case}"
+    flow = E.flow_hw2_input(case, 0)
+    gs = _g((hh, ww, 2), F32, flow.to(DEV))
+    go = _twice(lambda o: lib.call("dc_flow_hw2_resize_scale_f32", gs.view.data_ptr(), hh, ww, o.data_ptr(), th, tw, _st()),
+                (2, th, tw), F32, [gs], what)
+    _unchanged(gs, flow, what)
+    assert bool(torch.isfinite(go.view).all()), f"{what}: non-finite output (a guard element was read)"
+    r, s = L.flow_hw2_resize_scale_ref(gs.view, th, tw)
+    _note(record, ("flow_hw2_resize_scale",), L.check(go.view, r, s, F32), what)
+    assert torch.equal(ops.flow_hw2_resize_scale(gs.view, th, tw), go.view), f"{what}: the ops wrapper launches something else"
+
+
+@pytest.mark.parametrize("case", E.PACK_CASES, ids=lambda c: "x".join(map(str, c)))
+def test_pack_sixch_edge(ops, record, case):
+    """dc_pack_sixch_u8_f32: bit for bit fp32 x / 255 of every byte value; 1450 x 1450 takes the loop's second trip"""
+    from diffcodec_amd import lib
+    h, w = case
+    what = f"pack_sixch {case}"
+    a, b = E.pack_inputs(case)
+    if h * w * 3 >= 256:
+        assert len(torch.unique(a)) == 256 and len(torch.unique(b)) == 256
+    ga, gb = _g((h, w, 3), torch.uint8, a.to(DEV)), _g((h, w, 3), torch.uint8, b.to(DEV))
+    go = _twice(lambda o: lib.call("dc_pack_sixch_u8_f32", ga.view.data_ptr(), gb.view.data_ptr(), o.data_ptr(), h, w, _st()),
+                (1, 6, h, w), F32, [ga, gb], what)
+    _unchanged(ga, a, what)
+    _unchanged(gb, b, what)
+    ref = torch.cat([a.permute(2, 0, 1).float().div(255.0), b.permute(2, 0, 1).float().div(255.0)], 0).unsqueeze(0)
+    wrong = int((go.view.cpu().view(torch.int32) != ref.view(torch.int32)).sum())
+    record("edge[pack_sixch]", f"{what} elements_off={wrong}")
+    assert wrong == 0, f"{what}: {wrong} elements differ from fp32 x / 255"
+    assert torch.equal(ops.pack_sixch(ga.view, gb.view), go.view)
+
+
+@pytest.mark.parametrize("i", range(len(E.BLEND_CASES)), ids=[c.name for c in E.BLEND_CASES])
+def test_blend_tiles_ramp_edge(ops, record, i):
+    """dc_blend_tiles_ramp_u8 on guarded tiles and a guarded ramp of exactly `feather` taps: bit for bit tiling.merge_ramp, and within
+    0.5 + 1e-3 of the fp64 weighted mean (L.blend_tiles_ramp_ref), so that the host merge is not the only witness"""
+    import numpy as np
+    from diffcodec_amd import lib, tiling
+    c = E.BLEND_CASES[i]
+    what = f"blend_tiles_ramp {c.name}"
+    tiles = E.blend_inputs(c, i)
+    t = len(c.coords)
+    assert tuple(tiles.shape) == (t, c.c, c.th, c.tw) and 2 * c.feather <= min(c.th, c.tw)
+    gt = _g(tuple(tiles.shape), F32, tiles.to(DEV))
+    f = c.feather
+    ramp = (0.5 - 0.5 * np.cos(np.pi * (np.arange(f, dtype=np.float32) + 0.5) / f)).astype(np.float32) if f else None
+    gr = _g((f,), F32, torch.from_numpy(ramp).to(DEV)) if f else None
+    coords = torch.tensor(c.coords, dtype=torch.int32).reshape(-1, 4).to(DEV)
+
+    def launch(out):
+        lib.call("dc_blend_tiles_ramp_u8", gt.view.data_ptr(), coords.data_ptr(), t, c.c, c.th, c.tw, gr.view.data_ptr() if f else 0, f,
+                 out.data_ptr(), c.h, c.w, float(c.scale), _st())
+
+    go = _twice(launch, (c.h, c.w, c.c), torch.uint8, [gt] + ([gr] if f else []), what)
+    _unchanged(gt, tiles, what)
+    assert torch.equal(coords.cpu(), torch.tensor(c.coords, dtype=torch.int32).reshape(-1, 4))
+    dev = go.view.cpu()
+    host = tiling.merge_ramp([np.asarray(x.permute(1, 2, 0).numpy() * np.float32(c.scale), np.float32) for x in tiles], list(c.coords),
+                             (c.h, c.w), order="hwc", feather=f)
+    off = int((dev != torch.from_numpy(host)).sum())
+    mean = L.blend_tiles_ramp_ref(tiles, c.coords, c.h, c.w, f, c.scale)
+    dist = float((dev.double() - mean).abs().max())
+    record("edge[blend_tiles_ramp]", f"{what} elements_off_host_merge={off} max_distance_from_fp64_mean={dist:.6f}")
+    assert off == 0, f"{what}: {off} elements differ from tiling.merge_ramp"
+    assert dist <= 0.5 + 1e-3, f"{what}: {dist} from the fp64 weighted mean"
+    if c.values == "ties":
+        assert bool((dev % 2 == 0).all()) and bool(((mean - mean.floor()) == 0.5).all()), f"{what}: ties must round to even"
+    if c.values == "clip":
+        assert bool((dev == 0).any()) and bool((dev == 255).any())
+    assert torch.equal(ops.blend_tiles_ramp(gt.view, list(c.coords), (c.h, c.w), f, c.scale), go.view)

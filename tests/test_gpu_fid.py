@@ -122,6 +122,35 @@ def test_maps_match_fp64_restatement(models, sd, record, name):
         assert torch.equal(model.features(c["x"].to(DEV)), models["u8"].features(c["xu"].to(DEV)))
 
 
+def test_single_block_entry_on_guarded_maps(models, sd, record):
+    """dc_fid_conv (the one-block entry point) on guarded operands and outputs: each block from the device's own input map, twice;
+    each output within BAR_M of the fp64 restatement's map"""
+    import edge_cases as E
+    from diffcodec_amd import lib
+    c = _case("n2_5x7_u8", sd)
+    model = models["u8"]
+    maps = model.maps(c["x"].to(DEV))
+    wts = model._weights(torch.device(DEV, torch.cuda.current_device()))
+    st = torch.cuda.current_stream().cuda_stream
+    n = maps[0].shape[0]
+    for layer in range(3):
+        gin = E.Guarded(tuple(maps[layer].shape), torch.float32, DEV)
+        gin.fill(maps[layer])
+        outs = []
+        for rep in range(2):
+            go = E.Guarded(tuple(maps[layer + 1].shape), torch.float32, DEV)
+            lib.call("dc_fid_conv", layer, gin.view.data_ptr(), n, wts.data_ptr(), go.view.data_ptr(), st)
+            torch.cuda.synchronize()
+            gin.assert_intact(f"fid_conv layer {layer} input")
+            go.assert_intact(f"fid_conv layer {layer} output")
+            assert go.unwritten() == 0
+            outs.append(go.view)
+        assert torch.equal(outs[0], outs[1])
+        e = _err(outs[0], c["mx"][layer + 1])
+        record(f"fid_conv_layer{layer}_rel_err", e)
+        assert e <= BAR_M, (layer, e)
+
+
 @pytest.mark.parametrize("name", list(CASES))
 def test_features_match_fp64_restatement(models, sd, record, name):
     c = _case(name, sd)

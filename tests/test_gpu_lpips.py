@@ -129,6 +129,45 @@ def test_value_matches_fp64_restatement(model, sd, record, name):
     assert torch.equal(model(c["x"].to(DEV), c["y"].to(DEV), normalize=c["normalize"]), val)
 
 
+def test_single_layer_entry_on_guarded_maps(model, sd, record):
+    """dc_lpips_conv (the one-stage entry point) on guarded operands and outputs: layer 0 from the uint8 frames, layers 1..4 from the
+    device's own maps (max-pooled where AlexNet pools), twice; each output within BAR_F of the fp64 restatement's map"""
+    import ctypes
+    import edge_cases as E
+    from diffcodec_amd import lib
+    name = "n3_67x95_u8"
+    c = _case(name, sd)
+    n, h, w = CASES[name][:3]
+    wts = model._weights(torch.device(DEV, torch.cuda.current_device()))
+    st = torch.cuda.current_stream().cuda_stream
+    feats = model.features(c["x"].to(DEV))
+    gx = E.Guarded(tuple(c["x"].shape), torch.uint8, DEV)
+    gx.fill(c["x"].to(DEV))
+    strides = (ctypes.c_longlong * 4)(h * w * 3, 1, w * 3, 3)
+    for layer in range(5):
+        if layer == 0:
+            gin, args = gx, (gx.view.data_ptr(), 1, strides, n, h, w)
+        else:
+            src = F.max_pool2d(feats[layer - 1], 3, 2) if layer <= 2 else feats[layer - 1]
+            gin = E.Guarded(tuple(src.shape), torch.float32, DEV)
+            gin.fill(src)
+            args = (gin.view.data_ptr(), 0, None, n, src.shape[2], src.shape[3])
+        outs = []
+        for rep in range(2):
+            go = E.Guarded(tuple(feats[layer].shape), torch.float32, DEV)
+            lib.call("dc_lpips_conv", layer, *args, 0, wts.data_ptr(), go.view.data_ptr(), st)
+            torch.cuda.synchronize()
+            gin.assert_intact(f"lpips_conv layer {layer} input")
+            go.assert_intact(f"lpips_conv layer {layer} output")
+            assert go.unwritten() == 0
+            outs.append(go.view)
+        assert torch.equal(outs[0], outs[1])
+        ref = c["fx"][layer]
+        err = (outs[0].double().cpu() - ref).abs().max().item() / ref.abs().max().item()
+        record(f"lpips_conv_layer{layer}_rel_err", err)
+        assert err <= BAR_F, (layer, err)
+
+
 def test_exactness(model, sd, record):
     c = _case("n16_64x64_f1", sd)
     x, y = c["x"].to(DEV), c["y"].to(DEV)

@@ -1,6 +1,12 @@
 """GPU: PSNR / SSIM / MS-SSIM of csrc/metrics.hip (diffcodec_amd.metrics) against the fp64 restatement tests/metrics_ref.py, their
 exactness, layouts and reproducibility, and decode_clip(score=True) — single rank, through the tile blend, and sharded over two
-ranks with the scores (not the pixels) gathered."""
+ranks with the scores (not the pixels) gathered.
+
+The edge tests (tests/edge_cases.py: SSIM_CASES, MS_SSIM_CASES, PSNR_CASES, METRIC_REFUSALS) call dc_ssim / dc_ms_ssim / dc_psnr
+directly on guarded operands, a guarded scratch of exactly dc_*_ws_bytes and a guarded fp64 output, twice (scratch poisoned, then
+zeroed), and hold all three segments of the output to R.expected within R.ssim_bound."""
+import ctypes
+import math
 import os
 import socket
 
@@ -10,6 +16,7 @@ import torch
 import torch.multiprocessing as mp
 import torch.nn.functional as F
 
+import edge_cases as E
 import metrics_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -263,3 +270,164 @@ def test_world2_gloo_scores_gathered_on_rank0(small, tmp_path):
     assert res[0][1] == [1, 3] and res[1][1] == [2]
     assert res[1][2] == {2: ref[2]}                               # rank 1 keeps its own
     assert res[0][2] == ref, (res[0][2], ref)
+
+
+# ------------------------------------------------------------------------------------------- edge tables on guarded buffers
+@pytest.fixture(scope="module")
+def lib():
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    from diffcodec_amd import lib as l
+    return l
+
+
+_WORST = {}
+
+
+def _note(record, key, ratio):
+    k = "/".join(str(v) for v in key)
+    _WORST[k] = max(_WORST.get(k, 0.0), ratio)
+    record(f"edge[{k}]", f"worst_err_over_bound={_WORST[k]:.4f}")
+
+
+def _st():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _bits(t):
+    t = t.contiguous()
+    return t if t.dtype == torch.uint8 else t.view({4: torch.int32, 8: torch.int64}[t.element_size()])
+
+
+def _operands(c, X, Y):
+    _, lx, ly = E.METRIC_FORMS[c.form]
+    gx, sx = E.metric_operand(X, lx, DEV)
+    gy, sy = E.metric_operand(Y, ly, DEV)
+    assert (sx != sy) == (c.form == "mixed")
+    return gx, gy, sx, sy, (ctypes.c_longlong * 8)(*sx, *sy)
+
+
+def _launch_twice(launch, nbytes, nout, operands, what):
+    """two launches into two guarded fp64 outputs, the guarded scratch holding the guard pattern for the first and zeros for the
+    second: every guard intact and every output element written after each, the outputs bitwise equal -> the first output (CPU)"""
+    assert nbytes > 0, f"{what}: dc_*_ws_bytes = {nbytes}"
+    ws = E.Guarded((nbytes,), torch.uint8, DEV)
+    outs = []
+    for rep in range(2):
+        if rep:
+            ws.view.zero_()
+        go = E.Guarded((nout,), torch.float64, DEV)
+        launch(ws.view.data_ptr(), go.view.data_ptr())
+        torch.cuda.synchronize()
+        for k, g in enumerate(list(operands) + [ws, go]):
+            g.assert_intact(f"{what} launch {rep} buffer {k}")
+        assert go.unwritten() == 0, f"{what} launch {rep}: {go.unwritten()} output elements never written"
+        outs.append(go.view)
+    assert torch.equal(_bits(outs[0]), _bits(outs[1])), f"{what}: the output depends on what the scratch held"
+    return outs[0].cpu()
+
+
+def _ssim_edge(lib, record, c, seed, key):
+    X, Y = E.metric_inputs(c, seed)
+    g = E.metric_window(c.ws)
+    exp = R.case_expected(c, X, Y, g)
+    gx, gy, sx, sy, strides = _operands(c, X, Y)
+    u8 = int(c.dtype == "u8")
+    win = (ctypes.c_float * c.ws)(*g.tolist())
+    nbytes = lib.load().dc_ssim_ws_bytes(c.n, c.c, c.h, c.w, c.ws, c.levels or 1)
+    if c.levels:
+        wts = (ctypes.c_float * c.levels)(*c.weights)
+
+        def launch(ws, out):
+            lib.call("dc_ms_ssim", gx.view.data_ptr(), gy.view.data_ptr(), u8, strides, c.n, c.c, c.h, c.w, win, c.ws, wts, c.levels,
+                     c.K[0], c.K[1], c.L, ws, out, _st())
+    else:
+        def launch(ws, out):
+            lib.call("dc_ssim", gx.view.data_ptr(), gy.view.data_ptr(), u8, strides, c.n, c.c, c.h, c.w, win, c.ws, c.K[0], c.K[1],
+                     c.L, int(c.nonneg), ws, out, _st())
+
+    out = _launch_twice(launch, nbytes, c.n * c.c + c.n + 1, [gx, gy], c.label())
+    for gop, t, st in ((gx, X, sx), (gy, Y, sy)):
+        assert torch.equal(_bits(E.metric_read(gop, tuple(t.shape), st).cpu()), _bits(t)), f"{c.label()}: an operand was written"
+    v = R.check_out(out, exp)
+    print(f"{c.label()}: err/bound {v['ratio']:.4g} ({v['what']})")
+    _note(record, key, v["ratio"])
+    assert v["ok"], (c.label(), v, out.tolist()[:12])
+
+
+@pytest.mark.parametrize("i", range(len(E.SSIM_CASES)), ids=[c.label() for c in E.SSIM_CASES])
+def test_ssim_edge(lib, record, i):
+    c = E.SSIM_CASES[i]
+    _ssim_edge(lib, record, c, i, E.ssim_instance(c))
+
+
+@pytest.mark.parametrize("i", range(len(E.MS_SSIM_CASES)), ids=[c.label() for c in E.MS_SSIM_CASES])
+def test_ms_ssim_edge(lib, record, i):
+    c = E.MS_SSIM_CASES[i]
+    _ssim_edge(lib, record, c, i, ("ms_ssim", c.levels))
+
+
+@pytest.mark.parametrize("i", range(len(E.PSNR_CASES)), ids=[c.label() for c in E.PSNR_CASES])
+def test_psnr_edge(lib, record, i):
+    """uint8: within 1e-14 max(|ref|, 1) of the value of the exact integer SSE; fp32 operands: 1e-12 max(|ref|, 1) of the fp64
+    restatement; identical images: +inf"""
+    c = E.PSNR_CASES[i]
+    X, Y = E.metric_inputs(c, i)
+    gx, gy, sx, sy, strides = _operands(c, X, Y)
+    u8 = c.dtype == "u8"
+
+    def launch(ws, out):
+        lib.call("dc_psnr", gx.view.data_ptr(), gy.view.data_ptr(), int(u8), strides, c.n, c.c, c.h, c.w, float(c.L), ws, out, _st())
+
+    out = _launch_twice(launch, lib.load().dc_psnr_ws_bytes(c.n), c.n, [gx, gy], c.label())
+    if u8:
+        d = X.numpy().astype(np.int64) - Y.numpy().astype(np.int64)
+        sse = (d * d).reshape(c.n, -1).sum(1)
+        with np.errstate(divide="ignore"):
+            ref = torch.from_numpy(10 * np.log10(float(c.L) ** 2 / (sse / float(c.c * c.h * c.w))))
+        rel = 1e-14
+    else:
+        ref, rel = R.psnr(X.double(), Y.double(), c.L), 1e-12
+    if c.family == "identical":
+        assert bool((ref == math.inf).all())
+    inf = torch.isinf(ref)
+    assert torch.equal(out[inf], ref[inf]), (c.label(), out)
+    ratio = ((out - ref).abs()[~inf] / (rel * ref.abs().clamp_min(1.0)[~inf]))
+    worst = float(ratio.max()) if ratio.numel() else 0.0
+    print(f"{c.label()}: err/bound {worst:.4g}")
+    _note(record, ("psnr", c.dtype), worst)
+    assert not bool(torch.isnan(out).any()) and worst <= 1.0, (c.label(), out.tolist(), ref.tolist())
+
+
+def test_metric_launches_refuse_what_ws_bytes_refuses(lib):
+    """every METRIC_REFUSALS shape, a null window, null weights in MS mode and PSNR with N = 0 / 65536: dc_*_ws_bytes and the
+    launch return -1 and a guarded output keeps its pattern"""
+    L = lib.load()
+    x, y = (E.Guarded((64,), torch.float32, DEV) for _ in range(2))
+    x.view.fill_(0.5)
+    y.view.fill_(0.25)
+    ws = E.Guarded((1 << 16,), torch.uint8, DEV)
+    out = E.Guarded((16,), torch.float64, DEV)
+    xp, yp, wp, op = x.view.data_ptr(), y.view.data_ptr(), ws.view.data_ptr(), out.view.data_ptr()
+    wts = (ctypes.c_float * 9)(*([0.1] * 9))
+    for label, (n, c, h, w, wsz, lv) in E.METRIC_REFUSALS:
+        strides = (ctypes.c_longlong * 8)(*((c * h * w, h * w, w, 1) * 2))
+        win = (ctypes.c_float * 17)(*([1.0 / max(wsz, 1)] * 17))
+        assert L.dc_ssim_ws_bytes(n, c, h, w, wsz, lv) == -1, label
+        assert L.dc_ms_ssim(xp, yp, 0, strides, n, c, h, w, win, wsz, wts, lv, 0.01, 0.03, 1.0, wp, op, _st()) == -1, label
+        if lv == 1:
+            assert L.dc_ssim(xp, yp, 0, strides, n, c, h, w, win, wsz, 0.01, 0.03, 1.0, 0, wp, op, _st()) == -1, label
+    strides = (ctypes.c_longlong * 8)(*((64, 64, 8, 1) * 2))
+    win = (ctypes.c_float * 3)(0.25, 0.5, 0.25)
+    assert L.dc_ssim_ws_bytes(1, 1, 8, 8, 3, 1) > 0
+    assert L.dc_ssim(xp, yp, 0, strides, 1, 1, 8, 8, None, 3, 0.01, 0.03, 1.0, 0, wp, op, _st()) == -1
+    assert L.dc_ms_ssim(xp, yp, 0, strides, 1, 1, 8, 8, None, 3, wts, 1, 0.01, 0.03, 1.0, wp, op, _st()) == -1
+    assert L.dc_ms_ssim(xp, yp, 0, strides, 1, 1, 8, 8, win, 3, None, 1, 0.01, 0.03, 1.0, wp, op, _st()) == -1
+    for n in (0, 65536):
+        assert L.dc_psnr_ws_bytes(n) == -1, n
+        assert L.dc_psnr(xp, yp, 0, strides, n, 1, 8, 8, 1.0, wp, op, _st()) == -1, n
+    assert L.dc_psnr_ws_bytes(65535) == 65535 * 512
+    torch.cuda.synchronize()
+    for g in (x, y, ws, out):
+        g.assert_intact("refusals")
+    assert out.unwritten() == 16

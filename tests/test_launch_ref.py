@@ -613,6 +613,33 @@ def test_flow_resize_bound_passes_torch_and_rejects_faults(case, divide):
         assert _hold_fault("pitch_h", torch.stack([tw[:, 0] / dx, tw[:, 1] / dy], 1), r, s, label) or h * w == 1
 
 
+@pytest.mark.parametrize("case", E.FLOW_HW2_CASES, ids=lambda c: "x".join(map(str, c)))
+def test_flow_hw2_resize_scale_ref_passes_torch_and_rejects_faults(case):
+    """torch's fp32 F.interpolate(align_corners=True) followed by the multiply passes L.check against L.flow_hw2_resize_scale_ref;
+    the half-pixel (align_corners=False) index rule and swapped u / v multipliers fail (on every case where they change a value:
+    all but the identity resize 9x9 -> 9x9)"""
+    hh, ww, th, tw = case
+    flow = E.flow_hw2_input(case, 0)
+    r, s = L.flow_hw2_resize_scale_ref(flow, th, tw)
+    nchw = flow.permute(2, 0, 1).unsqueeze(0)
+
+    def torch_path(align, mu, mv, dtype=torch.float32):
+        t = F.interpolate(nchw.to(dtype), size=(th, tw), mode="bilinear", align_corners=align)
+        t[:, 0] *= mu
+        t[:, 1] *= mv
+        return t[0]
+
+    v = L.check(torch_path(True, tw / ww, th / hh), r, s, F32)
+    assert v["ok"], (case, v)
+    ref64 = torch_path(True, float(torch.tensor(tw / ww, dtype=F32)), float(torch.tensor(th / hh, dtype=F32)), torch.float64)
+    assert float((r - ref64).abs().max()) <= 1e-4 * float(r.abs().max())     # the fp32 index rule moves a weight by a few ulp of the index
+    label = "x".join(map(str, case))
+    if case != (9, 9, 9, 9):
+        assert _hold_fault("half_pixel", torch_path(False, tw / ww, th / hh).double(), r, s, label), case
+        assert tw / ww != th / hh
+        assert _hold_fault("multipliers_swapped", torch_path(True, th / hh, tw / ww).double(), r, s, label), case
+
+
 @pytest.mark.parametrize("occ", [True, False], ids=["holes", "noholes"])
 @pytest.mark.parametrize("i", range(len(E.FUSE_CASES)))
 def test_fuse_bound_passes_torch_and_rejects_faults(i, occ):
