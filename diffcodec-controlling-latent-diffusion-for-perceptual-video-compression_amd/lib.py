@@ -110,6 +110,22 @@ SIGNATURES = {
     "dc_resample_u8": [vp, POINTER(i64), i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp],
 }
 
+# name -> argtypes of include/diffcodec_flow_hip.h (csrc/cmp.hip; tests/test_cmp_abi.py cross-checks that header)
+FLOW_SIGNATURES = {
+    "dc_cmp_conv": [vp, i32, POINTER(i64), POINTER(f32), i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, i32, vp, i32, i32, vp],
+    "dc_cmp_maxpool": [vp, i32, i32, i32, i32, i32, i32, vp, vp],
+    "dc_cmp_avgpool": [vp, i32, i32, i32, i32, vp, i32, i32, vp],
+    "dc_cmp_upsample": [vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, vp],
+    "dc_cmp_convert_flow": [vp, i32, i32, i32, i32, f32, vp, vp],
+    "dc_cmp_sparse_grid": [vp, i32, i32, i32, i32, vp, vp],
+    "dc_cmp_head": [vp, i32, i32, i32, i32, vp, i32, f32, vp, vp, vp],
+    "dc_cmp_weight_floats": [i32, i32],
+    "dc_cmp_ws_bytes": [i32, i32, i32, i32],
+    "dc_cmp_forward": [i32, vp, i32, POINTER(i64), vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp],
+    "dc_cmp_flow": [i32, vp, i32, POINTER(i64), vp, i32, i32, i32, i32, f32, vp, vp, vp, vp],
+    "dc_cmp_endpoints": [i32, vp, i32, POINTER(i64), vp, i32, i32, i32, i32, f32, vp, vp, POINTER(vp), vp, vp, vp, vp],
+}
+
 _lib = None
 
 
@@ -132,6 +148,10 @@ def load():
         fn.argtypes = args
         fn.restype = c_longlong if name.endswith("_ws_bytes") else c_int
     lib.dc_gn_stats_chunks.restype = c_int
+    for name, args in FLOW_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.argtypes = args
+        fn.restype = c_longlong if name.endswith("_ws_bytes") else c_int
     _lib = lib
     return lib
 
