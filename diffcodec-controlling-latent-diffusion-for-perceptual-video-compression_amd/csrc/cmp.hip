@@ -24,7 +24,7 @@
 //   upsample  bilinear, align_corners = True, into a channel slice; source positions in fp64, the blend in fp32.
 //   convert   two nbins-bin softmaxes (x bins, then y bins) and the expectation over the bin centres, max-subtracted.
 //   grid      dense flow -> [flow at the grid points, 0 elsewhere | mask], gather form.
-#include "dc_common.h"
+#include "dc_f32_mfma.h"
 #include "../../include/diffcodec_flow_hip.h"
 #include <vector>
 
@@ -119,12 +119,7 @@ __global__ __launch_bounds__(256) void cmp_conv_kernel(cm_conv a)
         __syncthreads();
         if (c + 1 < nchunk) fetch(c + 1);
 #pragma unroll
-        for (int kp = 0; kp < CM_KC / 2; ++kp) {                         // lane half h takes k = 2 kp + h
-            const float bv = Pl[(2 * kp + h) * CM_PIX + pbase];
-#pragma unroll
-            for (int q = 0; q < 2; ++q)
-                if (q < nq) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(Wl[abase + kp * 2 * CM_COB + q * 32], bv, acc[q], 0, 0, 0);
-        }
+        for (int kp = 0; kp < CM_KC / 2; ++kp) dc_f32_kpair(acc, nq, &Wl[abase + kp * 2 * CM_COB], Pl[(2 * kp + h) * CM_PIX + pbase]);
     }
 
     const int p = p0 + pbase;
@@ -136,7 +131,7 @@ __global__ __launch_bounds__(256) void cmp_conv_kernel(cm_conv a)
             if (q < nq) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int ch = cb * CM_COB + q * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    const int ch = dc_f32_channel(r, h, cb * CM_COB + q * 32);
                     if (ch < a.Cout) {
                         float v = __builtin_fmaf(acc[q][r], a.s[ch], a.t[ch]);
                         if (ro) v += ro[(long long)ch * P];
@@ -284,20 +279,13 @@ __global__ __launch_bounds__(256) void cmp_head_kernel(cm_head a)
     const float* __restrict__ xn = a.x + (long long)n * a.Cin * a.P;
 
     f32x16 acc[CM_HT];
-#pragma unroll
-    for (int q = 0; q < CM_HT; ++q)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
+    dc_f32_zero(acc);
 
     const int pbase = wave * 32 + j;
     const int nchunk = (a.Cin + CM_KC - 1) / CM_KC;
     for (int c = 0; c < nchunk; ++c) {
         if (c) __syncthreads();
-        const float* __restrict__ wc = a.wp + (long long)c * CM_KC * a.CoP;
-        for (int p = tid; p < CM_KC * w4; p += 256) {
-            const int row = p / w4, c4 = (p - row * w4) * 4;
-            *(f32x4*)&Wl[row * CM_HC + c4] = *(const f32x4*)&wc[(long long)row * a.CoP + c4];
-        }
+        dc_f32_copy_w<CM_HC>(Wl, a.wp + (long long)c * CM_KC * a.CoP, a.CoP, CM_KC, w4, tid);
 #pragma unroll
         for (int i = 0; i < CM_KC / 2; ++i) {
             const int kr = kr0 + 2 * i, k = c * CM_KC + kr;
@@ -305,15 +293,10 @@ __global__ __launch_bounds__(256) void cmp_head_kernel(cm_head a)
         }
         __syncthreads();
 #pragma unroll
-        for (int kp = 0; kp < CM_KC / 2; ++kp) {
-            const float bv = Pl[(2 * kp + h) * CM_PIX + pbase];
-#pragma unroll
-            for (int q = 0; q < CM_HT; ++q)
-                if (q < nt) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(Wl[(2 * kp + h) * CM_HC + q * 32 + j], bv, acc[q], 0, 0, 0);
-        }
+        for (int kp = 0; kp < CM_KC / 2; ++kp) dc_f32_kpair(acc, nt, &Wl[(2 * kp + h) * CM_HC + j], Pl[(2 * kp + h) * CM_PIX + pbase]);
     }
 
-    // this lane holds, for pixel p, the channels q * 32 + (r & 3) + 8 (r >> 2) + 4 h; lane ^ 32 holds the others
+    // this lane holds, for pixel p, the channels dc_f32_channel(r, h, 32 q); lane ^ 32 holds the others
     const int p = p0 + pbase, C2 = 2 * a.nbins;
     const bool pvalid = p < a.P;
     float mx[2] = {-INFINITY, -INFINITY};
@@ -322,7 +305,7 @@ __global__ __launch_bounds__(256) void cmp_head_kernel(cm_head a)
         if (q < nt) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int ch = q * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int ch = dc_f32_channel(r, h, q * 32);
                 if (ch < C2) {
                     const float v = __builtin_fmaf(acc[q][r], a.s[ch], a.t[ch]);
                     acc[q][r] = v;
@@ -344,7 +327,7 @@ __global__ __launch_bounds__(256) void cmp_head_kernel(cm_head a)
         if (q < nt) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int ch = q * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int ch = dc_f32_channel(r, h, q * 32);
                 if (ch < C2) {
                     const int half = ch >= a.nbins, b = ch - half * a.nbins;
                     const double e = (double)expf(acc[q][r] - mx[half]);
@@ -364,8 +347,9 @@ __global__ __launch_bounds__(256) void cmp_head_kernel(cm_head a)
     if (pvalid) a.flow[((long long)n * 2 + h) * a.P + p] = (float)(h ? tot_m[1] / tot_e[1] : tot_m[0] / tot_e[0]);
 }
 
-inline int cm_blocks(long long total) { return (int)((total + 255) / 256 < 65535 * 16 ? (total + 255) / 256 : 65535 * 16); }
+inline int cm_blocks(long long total) { return dc_f32_blocks(total, 65535 * 16); }
 inline bool cm_dim(long long v) { return v > 0 && v <= (1 << 24); }
+inline long long cm_rows(int K) { return (long long)((K + CM_KC - 1) / CM_KC) * CM_KC; }   // k rows of a packed unit: whole chunks
 
 template <int KS>
 void cm_launch(const cm_conv& a, int u8, dim3 grid, hipStream_t st)
@@ -396,12 +380,9 @@ extern "C" int dc_cmp_conv(const void* x, int x_u8, const long long* xstrides, c
     a.Ho = (H + 2 * a.pad - dilation * (k - 1) - 1) / stride + 1;
     a.Wo = (W + 2 * a.pad - dilation * (k - 1) - 1) / stride + 1;
     a.K = Cin * k * k;
-    a.CoP = (Cout + 31) & ~31;
+    a.CoP = dc_f32_cop(Cout);
     a.Cout = Cout, a.Ctot = Ctot, a.coff = c_off, a.relu = relu;
-    const long long rows = (long long)((a.K + CM_KC - 1) / CM_KC) * CM_KC;
-    a.wp = packed;
-    a.s = packed + rows * a.CoP;
-    a.t = a.s + a.CoP;
+    dc_f32_split(packed, cm_rows(a.K), a.CoP, a.wp, a.s, a.t);
     a.res = residual;
     a.y = y;
     for (int c = 0; c < 3; ++c) {
@@ -479,11 +460,8 @@ extern "C" int dc_cmp_head(const float* x, int N, int Cin, int h, int w, const f
     if (nbins < 1 || 2 * nbins > CM_HC || !(fmax > 0.f) || (long long)h * w > (1ll << 28) || ((uintptr_t)packed & 15) != 0) return DC_ERR_INVALID;
     cm_head a;
     a.x = x, a.Cin = Cin, a.P = h * w, a.nbins = nbins, a.fmax = (double)fmax;
-    a.CoP = (2 * nbins + 31) & ~31;
-    const long long rows = (long long)((Cin + CM_KC - 1) / CM_KC) * CM_KC;
-    a.wp = packed;
-    a.s = packed + rows * a.CoP;
-    a.t = a.s + a.CoP;
+    a.CoP = dc_f32_cop(2 * nbins);
+    dc_f32_split(packed, cm_rows(Cin), a.CoP, a.wp, a.s, a.t);
     a.logits = logits, a.flow = flow;
     hipLaunchKernelGGL(cmp_head_kernel, dim3((a.P + CM_PIX - 1) / CM_PIX, N), dim3(256), 0, (hipStream_t)stream, a);
     return dc_launch_status();
@@ -533,7 +511,7 @@ bool cm_specs(int arch, int nbins, std::vector<cm_spec>& t)
 }
 inline long long cm_packed_floats(const cm_spec& c)
 {
-    return ((long long)((c.cin * c.k * c.k + CM_KC - 1) / CM_KC) * CM_KC + 2) * ((c.cout + 31) & ~31);
+    return (cm_rows(c.cin * c.k * c.k) + 2) * dc_f32_cop(c.cout);
 }
 
 struct cm_plan {
@@ -552,31 +530,26 @@ bool cm_make_plan(int arch, int N, int H, int W, int nbins, cm_plan& p)
     if (p.h8 < pool || p.w8 < pool) return false;                        // a decoder max-pool would be empty
     const long long P2 = (long long)p.h2 * p.w2, P4 = (long long)p.h4 * p.w4, P8 = (long long)p.h8 * p.w8, n = N;
     if (n * 2048 * P8 > (1ll << 34)) return false;
-    long long o = 0;
-    auto take = [&](long long floats) {
-        const long long at = o;
-        o += (floats + 63) & ~63ll;
-        return at;
-    };
-    p.enc = take(n * (CM_ENC + CM_SP) * P8);
-    p.stem = take(n * 64 * P2);
-    p.layer1 = take(n * 256 * P4);
-    p.sp1 = take(n * 16 * P2);
-    p.sp1p = take(n * 16 * p.hs * p.ws);
-    p.sp2 = take(n * CM_SP * p.hs * p.ws);
-    p.cat = take(n * 128 * (arch == 0 ? 4 : 3) * P8);
-    p.pool = take(n * (CM_ENC + CM_SP) * (p.h8 / 2) * (p.w8 / 2));
-    p.bx = take(2 * n * 128 * P8);
-    p.f8 = take(arch == 0 ? n * 256 * P8 : 0);
-    p.cat4 = take(arch == 0 ? n * 384 * P4 : 0);
-    p.f4 = take(arch == 0 ? n * 128 * P4 : 0);
-    p.cat2 = take(arch == 0 ? n * 160 * P2 : 0);
-    p.f2 = take(arch == 0 ? n * 64 * P2 : 0);
-    p.flow = take(n * 2 * (arch == 0 ? P2 : P8));
+    dc_f32_bump<4> ws;
+    p.enc = ws.take(n * (CM_ENC + CM_SP) * P8);
+    p.stem = ws.take(n * 64 * P2);
+    p.layer1 = ws.take(n * 256 * P4);
+    p.sp1 = ws.take(n * 16 * P2);
+    p.sp1p = ws.take(n * 16 * p.hs * p.ws);
+    p.sp2 = ws.take(n * CM_SP * p.hs * p.ws);
+    p.cat = ws.take(n * 128 * (arch == 0 ? 4 : 3) * P8);
+    p.pool = ws.take(n * (CM_ENC + CM_SP) * (p.h8 / 2) * (p.w8 / 2));
+    p.bx = ws.take(2 * n * 128 * P8);
+    p.f8 = ws.take(arch == 0 ? n * 256 * P8 : 0);
+    p.cat4 = ws.take(arch == 0 ? n * 384 * P4 : 0);
+    p.f4 = ws.take(arch == 0 ? n * 128 * P4 : 0);
+    p.cat2 = ws.take(arch == 0 ? n * 160 * P2 : 0);
+    p.f2 = ws.take(arch == 0 ? n * 64 * P2 : 0);
+    p.flow = ws.take(n * 2 * (arch == 0 ? P2 : P8));
     const long long big = n * (256 * P4 > 2048 * P8 ? 256 * P4 : 2048 * P8), small = n * (128 * P4 > 512 * P8 ? 128 * P4 : 512 * P8);
-    for (auto& b : p.big) b = take(big);
-    for (auto& b : p.small) b = take(small);
-    p.total = o;
+    for (auto& b : p.big) b = ws.take(big);
+    for (auto& b : p.small) b = ws.take(small);
+    p.total = ws.off;
     return true;
 }
 

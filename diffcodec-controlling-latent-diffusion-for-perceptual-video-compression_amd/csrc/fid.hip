@@ -20,7 +20,7 @@
 //             channel), per-thread fp64 sums in a fixed order, a fixed butterfly, one fp32 feature.
 //   state     n, sum f [64], sum f f^T [64][64] in fp64: one thread per entry adds the rows image by image in batch order, so
 //             update(a); update(b) leaves the bits of update(cat(a, b)).
-#include "dc_common.h"
+#include "dc_f32_mfma.h"
 #include "../../include/diffcodec_hip.h"
 
 namespace {
@@ -30,10 +30,6 @@ constexpr int FD_COLS = 32, FD_ROWS = 4;    // output pixels per workgroup: FD_R
 constexpr int FD_FEAT = 64;
 constexpr int FD_STATE = 1 + FD_FEAT + FD_FEAT * FD_FEAT;
 constexpr int FD_H1 = 149, FD_H2 = 147, FD_HP = 73;
-
-struct fd_strides {
-    long long n, c, h, w;
-};
 
 // ------------------------------------------------------------------------------------------------ resize + scale
 template <typename T>
@@ -49,7 +45,7 @@ __device__ __forceinline__ float fd_load(const T* __restrict__ p, long long i)
 }
 
 template <typename T>
-__global__ __launch_bounds__(256) void fid_resize_kernel(const T* __restrict__ x, fd_strides s, int H, int W, float* __restrict__ y,
+__global__ __launch_bounds__(256) void fid_resize_kernel(const T* __restrict__ x, dc_strides4 s, int H, int W, float* __restrict__ y,
                                                          long long total)
 {
 #pragma clang fp contract(off)
@@ -79,12 +75,7 @@ struct fd_geom {
     static constexpr int PH = (FD_ROWS - 1) * S + 3, PW = (FD_COLS - 1) * S + 3;
     static constexpr int PE = CK * PH * PW;
     static constexpr int KC = CK * 9, KCP = (KC + 1) & ~1;               // k rows of a chunk, padded to whole pairs
-    // patch offset of chunk-local k = (ci, ky, kx); a padded k (zero weight row) reads the tap before it
-    static __device__ constexpr int off(int k)
-    {
-        const int kk = k < KC ? k : KC - 1;
-        return (kk / 9) * (PH * PW) + ((kk % 9) / 3) * PW + (kk % 3);
-    }
+    static __device__ constexpr int off(int k) { return dc_f32_patch_off<3, PW, PH * PW, KC>(k); }   // k = (ci, ky, kx)
 };
 
 // x [N][CIN][H][W] -> y [N][CO][Ho][Wo], wp [(CIN / CK) * KC (+ pad)][CO] K-major, bn_s / bn_t [CO]
@@ -95,7 +86,6 @@ __global__ __launch_bounds__(256) void fid_conv_kernel(const float* __restrict__
 {
     using G = fd_geom<CK, S>;
     constexpr int NC = CO / 32, NCHUNK = CIN / CK;
-    constexpr int W4 = G::KCP * CO / 4;                                  // float4 pieces of a weight chunk
     static_assert(CIN % CK == 0 && CO % 32 == 0 && (NCHUNK == 1 || G::KC == G::KCP), "chunks must tile K");
     __shared__ __attribute__((aligned(16))) float Wl[G::KCP * CO];
     __shared__ float Pl[G::PE];
@@ -108,17 +98,14 @@ __global__ __launch_bounds__(256) void fid_conv_kernel(const float* __restrict__
     const int iy0 = ty0 * S - PAD, ix0 = tx0 * S - PAD;
 
     f32x16 acc[NC];
-#pragma unroll
-    for (int q = 0; q < NC; ++q)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
+    dc_f32_zero(acc);
 
     const int pbase = wave * S * G::PW + j * S;
     const int abase = h * CO + j;
     for (int c = 0; c < NCHUNK; ++c) {
         if (c) __syncthreads();                                          // everyone is done reading the previous chunk
         const f32x4* __restrict__ wc = (const f32x4*)(wp + (long long)c * G::KC * CO);
-        for (int p = tid; p < W4; p += 256) ((f32x4*)Wl)[p] = wc[p];
+        for (int p = tid; p < G::KCP * CO / 4; p += 256) ((f32x4*)Wl)[p] = wc[p];
         const float* __restrict__ xc = xn + (long long)c * CK * H * W;
         for (int e = tid; e < G::PE; e += 256) {
             const int ci = e / (G::PH * G::PW), r = e - ci * (G::PH * G::PW);
@@ -130,10 +117,7 @@ __global__ __launch_bounds__(256) void fid_conv_kernel(const float* __restrict__
 #pragma unroll
         for (int kp = 0; kp < G::KCP / 2; ++kp) {                       // lane half h takes k = 2 kp + h
             const int poff = h ? G::off(2 * kp + 1) : G::off(2 * kp);
-            const float b = Pl[pbase + poff];
-#pragma unroll
-            for (int q = 0; q < NC; ++q)
-                acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(Wl[abase + kp * 2 * CO + q * 32], b, acc[q], 0, 0, 0);
+            dc_f32_kpair(acc, NC, &Wl[abase + kp * 2 * CO], Pl[pbase + poff]);
         }
     }
 
@@ -145,7 +129,7 @@ __global__ __launch_bounds__(256) void fid_conv_kernel(const float* __restrict__
         for (int q = 0; q < NC; ++q)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int col = q * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int col = dc_f32_channel(r, h, q * 32);
                 yo[(long long)col * Ho * Wo] = fmaxf(__builtin_fmaf(acc[q][r], bn_s[col], bn_t[col]), 0.f);
             }
     }
@@ -197,8 +181,6 @@ __global__ __launch_bounds__(256) void fid_accumulate_kernel(const float* __rest
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-inline long long fd_align(long long b) { return (b + 255) & ~255ll; }
-
 // packed weights (floats): per block the K-major matrix [K (padded)][Cout], then s [Cout], t [Cout]
 constexpr int FD_K[3] = {28, 288, 288};
 constexpr int FD_CO[3] = {32, 32, 64};
@@ -227,16 +209,12 @@ struct fd_plan {
 bool make_fd_plan(int N, int H, int W, fd_plan& p)
 {
     if (N <= 0 || N > 65535 || H < 1 || W < 1 || H > 16384 || W > 16384) return false;
-    long long off = 0;
-    p.resized = off;
-    off += fd_align((long long)N * 3 * FD_SIZE * FD_SIZE * 4);
-    p.m1 = off;
-    off += fd_align((long long)N * 32 * FD_H1 * FD_H1 * 4);
-    p.m2 = off;
-    off += fd_align((long long)N * 32 * FD_H2 * FD_H2 * 4);
-    p.m3 = off;
-    off += fd_align((long long)N * 64 * FD_H2 * FD_H2 * 4);
-    p.total = off;
+    dc_f32_bump<1> ws;
+    p.resized = ws.take((long long)N * 3 * FD_SIZE * FD_SIZE * 4);
+    p.m1 = ws.take((long long)N * 32 * FD_H1 * FD_H1 * 4);
+    p.m2 = ws.take((long long)N * 32 * FD_H2 * FD_H2 * 4);
+    p.m3 = ws.take((long long)N * 64 * FD_H2 * FD_H2 * 4);
+    p.total = ws.off;
     return true;
 }
 
@@ -249,12 +227,12 @@ void launch_conv(const float* x, const float* w, const float* s, const float* t,
                        Wo, tiles_x);
 }
 
-void run_stem(const void* x, int u8, fd_strides sx, int N, int H, int W, const float* wts, float* resized, float* m1, float* m2,
+void run_stem(const void* x, int u8, dc_strides4 sx, int N, int H, int W, const float* wts, float* resized, float* m1, float* m2,
               float* m3, float* pooled, float* feat, hipStream_t st)
 {
     const fd_weights o = fd_weight_layout();
     const long long total = (long long)N * 3 * FD_SIZE * FD_SIZE;
-    const int grid = (int)min((long long)8192, (total + 255) / 256);
+    const int grid = dc_f32_blocks(total, 8192);
     if (u8)
         hipLaunchKernelGGL(fid_resize_kernel<uint8_t>, dim3(grid), dim3(256), 0, st, (const uint8_t*)x, sx, H, W, resized, total);
     else
@@ -282,8 +260,7 @@ extern "C" int dc_fid_features(const void* x, int x_u8, const long long* strides
     fd_plan p;
     if (!x || !strides || !weights || !ws || !out || !make_fd_plan(N, H, W, p)) return DC_ERR_INVALID;
     char* base = (char*)ws;
-    const fd_strides sx{strides[0], strides[1], strides[2], strides[3]};
-    run_stem(x, x_u8, sx, N, H, W, weights, (float*)(base + p.resized), (float*)(base + p.m1), (float*)(base + p.m2),
+    run_stem(x, x_u8, dc_strides4(strides), N, H, W, weights, (float*)(base + p.resized), (float*)(base + p.m1), (float*)(base + p.m2),
              (float*)(base + p.m3), nullptr, out, (hipStream_t)stream);
     return dc_launch_status();
 }
@@ -293,8 +270,7 @@ extern "C" int dc_fid_maps(const void* x, int x_u8, const long long* strides, in
 {
     fd_plan p;
     if (!x || !strides || !weights || !resized || !m1 || !m2 || !m3 || !pooled || !out || !make_fd_plan(N, H, W, p)) return DC_ERR_INVALID;
-    const fd_strides sx{strides[0], strides[1], strides[2], strides[3]};
-    run_stem(x, x_u8, sx, N, H, W, weights, resized, m1, m2, m3, pooled, out, (hipStream_t)stream);
+    run_stem(x, x_u8, dc_strides4(strides), N, H, W, weights, resized, m1, m2, m3, pooled, out, (hipStream_t)stream);
     return dc_launch_status();
 }
 

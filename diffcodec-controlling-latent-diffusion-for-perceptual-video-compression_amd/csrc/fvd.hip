@@ -22,7 +22,7 @@
 //   max-pool    SAME padding by the same rule; the padded positions are zeros that ENTER the max (F.pad, then pool).
 //   head        mean over [2,7,7] windows (stride 1) of Mixed_5c in fp64 in a fixed order, the 1x1x1 logits conv with bias (the
 //               conv kernel with s = 1, t = bias, no ReLU), the mean over the remaining time positions in fp64.
-#include "dc_common.h"
+#include "dc_f32_mfma.h"
 #include "../../include/diffcodec_hip.h"
 
 namespace {
@@ -92,12 +92,7 @@ struct fv_geom {
     static constexpr int PE = CI * KTC * PS;
     static constexpr int KC = CI * KTC * KS * KS, KCP = (KC + 1) & ~1;   // k rows of a chunk, padded to whole pairs
     static constexpr int NKT = KS / KTC;                                 // chunks along the kernel's time axis
-    // patch offset of chunk-local k = (ci, kt, kh, kw); a padded k (zero weight row) reads the tap before it
-    static __device__ constexpr int off(int k)
-    {
-        const int kk = k < KC ? k : KC - 1;
-        return (kk / (KS * KS)) * PS + ((kk % (KS * KS)) / KS) * PW + (kk % KS);
-    }
+    static __device__ constexpr int off(int k) { return dc_f32_patch_off<KS, PW, PS, KC>(k); }   // k = (ci, kt, kh, kw)
 };
 
 __device__ __forceinline__ void fv_store(const fv_conv& a, const f32x16 (&acc)[2], int nq, int cb, int h, float* __restrict__ yo,
@@ -108,7 +103,7 @@ __device__ __forceinline__ void fv_store(const fv_conv& a, const f32x16 (&acc)[2
         if (q < nq) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int col = cb * FV_COB + q * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int col = dc_f32_channel(r, h, cb * FV_COB + q * 32);
                 if (col < a.Cout) {
                     const float v = __builtin_fmaf(acc[q][r], a.s[col], a.t[col]);
                     yo[(long long)col * cstride] = a.relu ? fmaxf(v, 0.f) : v;
@@ -139,7 +134,7 @@ __global__ __launch_bounds__(256) void fvd_conv_kernel(fv_conv a)
 
     f32x16 acc[2];
 #pragma unroll
-    for (int q = 0; q < 2; ++q)
+    for (int q = 0; q < 2; ++q)                                          // dc_f32_zero moves an s_nop of <3, 1, 4, 3>: the text stays
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
 
@@ -155,11 +150,7 @@ __global__ __launch_bounds__(256) void fvd_conv_kernel(fv_conv a)
         }
         if (staged) __syncthreads();                                     // everyone is done reading the previous chunk
         staged = true;
-        const float* __restrict__ wc = a.wp + (long long)c * G::KCP * a.CoP + cb * FV_COB;
-        for (int p = tid; p < G::KCP * (FV_COB / 4); p += 256) {
-            const int row = p / (FV_COB / 4), c4 = (p % (FV_COB / 4)) * 4;
-            if (c4 < wcols) *(f32x4*)&Wl[row * FV_COB + c4] = *(const f32x4*)&wc[(long long)row * a.CoP + c4];
-        }
+        dc_f32_copy_w<FV_COB>(Wl, a.wp + (long long)c * G::KCP * a.CoP + cb * FV_COB, a.CoP, G::KCP, FV_COB / 4, tid, wcols);
         for (int e = tid; e < G::PE; e += 256) {
             const int sl = e / G::PS, r = e - sl * G::PS;
             const int ci = sl / KTC, kt = sl - ci * KTC;
@@ -172,10 +163,7 @@ __global__ __launch_bounds__(256) void fvd_conv_kernel(fv_conv a)
 #pragma unroll
         for (int kp = 0; kp < G::KCP / 2; ++kp) {                       // lane half h takes k = 2 kp + h
             const int poff = h ? G::off(2 * kp + 1) : G::off(2 * kp);
-            const float bv = Pl[pbase + poff];
-#pragma unroll
-            for (int q = 0; q < 2; ++q)
-                if (q < nq) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(Wl[abase + kp * 2 * FV_COB + q * 32], bv, acc[q], 0, 0, 0);
+            dc_f32_kpair(acc, nq, &Wl[abase + kp * 2 * FV_COB], Pl[pbase + poff]);
         }
     }
 
@@ -202,21 +190,14 @@ __global__ __launch_bounds__(256) void fvd_pointwise_kernel(fv_conv a)
     const float* __restrict__ xn = a.x + (long long)n * a.Cin * P;
 
     f32x16 acc[2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
+    dc_f32_zero(acc);
 
     const int pbase = wave * 32 + j;
     const int abase = h * FV_COB + j;
     const int nchunk = (a.Cin + FV_PCI - 1) / FV_PCI;
     for (int c = 0; c < nchunk; ++c) {
         if (c) __syncthreads();
-        const float* __restrict__ wc = a.wp + (long long)c * FV_PCI * a.CoP + cb * FV_COB;
-        for (int p = tid; p < FV_PCI * (FV_COB / 4); p += 256) {
-            const int row = p / (FV_COB / 4), c4 = (p % (FV_COB / 4)) * 4;
-            if (c4 < wcols) *(f32x4*)&Wl[row * FV_COB + c4] = *(const f32x4*)&wc[(long long)row * a.CoP + c4];
-        }
+        dc_f32_copy_w<FV_COB>(Wl, a.wp + (long long)c * FV_PCI * a.CoP + cb * FV_COB, a.CoP, FV_PCI, FV_COB / 4, tid, wcols);
         for (int e = tid; e < FV_PCI * FV_PPOS; e += 256) {
             const int ci = e / FV_PPOS, pp = e - ci * FV_PPOS;
             const int cin = c * FV_PCI + ci;
@@ -225,12 +206,7 @@ __global__ __launch_bounds__(256) void fvd_pointwise_kernel(fv_conv a)
         }
         __syncthreads();
 #pragma unroll
-        for (int kp = 0; kp < FV_PCI / 2; ++kp) {
-            const float bv = Pl[(2 * kp + h) * FV_PPOS + pbase];
-#pragma unroll
-            for (int q = 0; q < 2; ++q)
-                if (q < nq) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(Wl[abase + kp * 2 * FV_COB + q * 32], bv, acc[q], 0, 0, 0);
-        }
+        for (int kp = 0; kp < FV_PCI / 2; ++kp) dc_f32_kpair(acc, nq, &Wl[abase + kp * 2 * FV_COB], Pl[(2 * kp + h) * FV_PPOS + pbase]);
     }
 
     const long long p = p0 + pbase;
@@ -296,13 +272,11 @@ __global__ __launch_bounds__(256) void fvd_timemean_kernel(const float* __restri
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-inline long long fv_align(long long b) { return (b + 255) & ~255ll; }
-inline int fv_cop(int cout) { return (cout + 31) & ~31; }
 inline int fv_krows(int cin, int k)
 {
     return k == 7 ? cin * 7 * 50 : k == 3 ? ((cin + 3) / 4) * 108 : ((cin + FV_PCI - 1) / FV_PCI) * FV_PCI;
 }
-inline long long fv_unit_floats(int cin, int cout, int k) { return ((long long)fv_krows(cin, k) + 2) * fv_cop(cout); }
+inline long long fv_unit_floats(int cin, int cout, int k) { return ((long long)fv_krows(cin, k) + 2) * dc_f32_cop(cout); }
 // TF "SAME": output size and front padding of one axis
 inline void fv_same(int size, int k, int s, int& out, int& front)
 {
@@ -321,10 +295,8 @@ bool launch_unit(const float* x, int N, int Cin, int T, int H, int W, int k, int
     fv_conv a;
     a.x = x;
     a.y = y;
-    a.CoP = fv_cop(Cout);
-    a.wp = packed;
-    a.s = packed + (long long)fv_krows(Cin, k) * a.CoP;
-    a.t = a.s + a.CoP;
+    a.CoP = dc_f32_cop(Cout);
+    dc_f32_split(packed, fv_krows(Cin, k), a.CoP, a.wp, a.s, a.t);
     a.Cin = Cin, a.T = T, a.H = H, a.W = W, a.Cout = Cout, a.Ctot = Ctot, a.coff = coff, a.relu = relu;
     fv_same(T, k, stride, a.To, a.pt);
     fv_same(H, k, stride, a.Ho, a.ph);
@@ -356,7 +328,7 @@ bool launch_pool(const float* x, int N, int C, int T, int H, int W, int kt, int 
     fv_same(H, kh, s_h, g.Ho, g.ph);
     fv_same(W, kw, s_w, g.Wo, g.pw);
     const long long total = (long long)N * C * g.To * g.Ho * g.Wo;
-    const int grid = (int)min((long long)16384, (total + 255) / 256);
+    const int grid = dc_f32_blocks(total, 16384);
     hipLaunchKernelGGL(fvd_maxpool_kernel, dim3(grid), dim3(256), 0, st, x, y, g, total);
     return true;
 }
@@ -409,12 +381,12 @@ bool make_fv_plan(int N, int T, int H, int W, fv_plan& p)
 {
     if (N <= 0 || N > 65535 || T < 9 || T > 4096 || H < 1 || W < 1 || H > 16384 || W > 16384) return false;
     p.T1 = (T + 1) / 2, p.T4 = (p.T1 + 1) / 2, p.T5 = (p.T4 + 1) / 2;
-    long long off = 0;
-    p.prep = off, off += fv_align((long long)N * 3 * T * FV_SIZE * FV_SIZE * 4);
+    dc_f32_bump<1> ws;
+    p.prep = ws.take((long long)N * 3 * T * FV_SIZE * FV_SIZE * 4);
     for (int e = 0; e < FV_ENDPOINTS; ++e) {
         int C, Te, S;
         fv_endpoint_shape(p, e, C, Te, S);
-        p.ep[e] = off, off += fv_align((long long)N * C * Te * S * S * 4);
+        p.ep[e] = ws.take((long long)N * C * Te * S * S * 4);
     }
     // branch temporaries: the largest 1x1x1 reductions (128 channels at 28 x 28) and the largest pooled module input (256 at 28 x 28)
     long long t12 = 0, t3 = 0;
@@ -425,12 +397,12 @@ bool make_fv_plan(int N, int T, int H, int W, fv_plan& p)
         if (pix * c12 > t12) t12 = pix * c12;
         if (pix * FV_MIXED[m].cin > t3) t3 = pix * FV_MIXED[m].cin;
     }
-    p.tmp1 = off, off += fv_align(t12);
-    p.tmp2 = off, off += fv_align(t12);
-    p.tmp3 = off, off += fv_align(t3);
-    p.pooled = off, off += fv_align((long long)N * 1024 * (p.T5 - 1) * 4);
-    p.logits = off, off += fv_align((long long)N * FV_FEAT * (p.T5 - 1) * 4);
-    p.total = off;
+    p.tmp1 = ws.take(t12);
+    p.tmp2 = ws.take(t12);
+    p.tmp3 = ws.take(t3);
+    p.pooled = ws.take((long long)N * 1024 * (p.T5 - 1) * 4);
+    p.logits = ws.take((long long)N * FV_FEAT * (p.T5 - 1) * 4);
+    p.total = ws.off;
     return true;
 }
 
@@ -439,7 +411,7 @@ bool launch_preprocess(const void* x, int u8, int div255, fv_strides s, int N, i
 {
     if (N <= 0 || T <= 0 || H < 1 || W < 1 || RH < FV_SIZE || RW < FV_SIZE || (RH != FV_SIZE && RW != FV_SIZE)) return false;
     const long long total = (long long)N * 3 * T * FV_SIZE * FV_SIZE;
-    const int grid = (int)min((long long)16384, (total + 255) / 256);
+    const int grid = dc_f32_blocks(total, 16384);
     if (u8)
         hipLaunchKernelGGL(fvd_preprocess_kernel<uint8_t>, dim3(grid), dim3(256), 0, st, (const uint8_t*)x, s, T, H, W, RH, RW, div255, y,
                            total);

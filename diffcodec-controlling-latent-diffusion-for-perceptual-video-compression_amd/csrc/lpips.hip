@@ -12,8 +12,7 @@
 //   workgroup = 4 waves, tile = 64 output channels x (4 rows x 32 columns) of one image; ragged edges are masked in the patch load
 //   (zero padding materialised in LDS) and in the store, so any map size works (from 512^2: 127 / 63 / 31 wide, one column of the
 //   32 idle).  Wave w takes channel half w & 1 and rows 2 (w >> 1), 2 (w >> 1) + 1: two accumulator tiles, one A read per two MFMAs.
-//   MFMA operand layout: A = W[co = lane & 31][k = lane >> 5], B = X[k = lane >> 5][pixel = lane & 31]; C/D: lane & 31 = pixel,
-//   register r = channel (r & 3) + 8 (r >> 2) + 4 (lane >> 5): a store instruction writes 32 consecutive pixels of a channel row.
+//   MFMA operand and C/D layouts: dc_f32_mfma.h.
 //   conv2-5 (5x5 | 3x3, stride 1): K runs over chunks of CK input channels (4 | 8); the chunk's patch and weight slice are staged in
 //     LDS from registers loaded one chunk ahead; one k-step is a PAIR of input channels at one tap.
 //   conv1 (3 -> 64, 11x11, stride 4, pad 2): K = (c, ky, kx) = 363, padded to 364 with a zero weight row; the whole weight matrix
@@ -24,7 +23,7 @@
 //   squares, pass 2 sums w_c (x_c / (|x| + eps) - y_c / (|y| + eps))^2; the normalised maps never exist in memory.  One fp64 partial
 //   per workgroup, then one finalize launch sums each (layer, image) slab in a fixed order into the spatial mean and the five means
 //   into the value.
-#include "dc_common.h"
+#include "dc_f32_mfma.h"
 #include "../../include/diffcodec_hip.h"
 
 namespace {
@@ -38,10 +37,6 @@ constexpr int LP_KS[LP_LAYERS] = {11, 5, 3, 3, 3};
 constexpr int LP_K1 = 364;                 // conv1's K (3 * 11 * 11 = 363) padded to a whole number of pairs
 constexpr int LP_MIN_HW = 31;              // smallest image: the maps are 7 / 3 / 1 / 1 / 1
 constexpr int LP_TAIL_PX = 64;             // pixels per workgroup of the tail: one per lane
-
-struct lp_strides {
-    long long n, c, h, w;
-};
 
 // ------------------------------------------------------------------------------------------------ conv2 .. conv5
 template <int KS, int CK>
@@ -110,10 +105,7 @@ __global__ __launch_bounds__(256, 2) void lpips_conv_kernel(const float* __restr
     const int abase = h * KK * LP_CO + ch * 32 + j;
 
     f32x16 acc[2];
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
+    dc_f32_zero(acc);
 
     const int nchunk = Cin / CK;
     load_chunk(0);
@@ -143,7 +135,7 @@ __global__ __launch_bounds__(256, 2) void lpips_conv_kernel(const float* __restr
             float* __restrict__ yo = y + (((long long)n * Cout + co0 + ch * 32) * H + oy) * W + ox;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int col = (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int col = dc_f32_channel(r, h);
                 yo[(long long)col * H * W] = fmaxf(acc[b][r] + bias[co0 + ch * 32 + col], 0.f);
             }
         }
@@ -156,12 +148,7 @@ constexpr int L1_PH = (LP_ROWS - 1) * L1_S + L1_KS, L1_PW = (LP_COLS - 1) * L1_S
 constexpr int L1_PE = 3 * L1_PH * L1_PW;
 constexpr int L1_LDS_BYTES = (LP_K1 * LP_CO + L1_PE) * 4;
 
-// patch offset of k = (c, ky, kx); the padded k = 363 (zero weight) reads the tap before it
-__device__ constexpr int l1_off(int k)
-{
-    const int kk = k < 363 ? k : 362;
-    return (kk / 121) * (L1_PH * L1_PW) + ((kk % 121) / 11) * L1_PW + (kk % 11);
-}
+__device__ constexpr int l1_off(int k) { return dc_f32_patch_off<L1_KS, L1_PW, L1_PH * L1_PW, 363>(k); }   // k = (c, ky, kx)
 
 template <typename T>
 __device__ __forceinline__ float l1_load(const T* __restrict__ p, long long i)
@@ -172,7 +159,7 @@ __device__ __forceinline__ float l1_load(const T* __restrict__ p, long long i)
 }
 
 template <typename T>
-__global__ __launch_bounds__(256) void lpips_conv1_kernel(const T* __restrict__ x, const T* __restrict__ y, lp_strides sx, lp_strides sy,
+__global__ __launch_bounds__(256) void lpips_conv1_kernel(const T* __restrict__ x, const T* __restrict__ y, dc_strides4 sx, dc_strides4 sy,
                                                           int NX, const float* __restrict__ wp, const float* __restrict__ bias,
                                                           float* __restrict__ out, int H, int W, int Ho, int Wo, int tiles_x,
                                                           int normalize)
@@ -188,9 +175,9 @@ __global__ __launch_bounds__(256) void lpips_conv1_kernel(const T* __restrict__ 
     const int n = blockIdx.z;
     const bool first = n < NX;
     const T* __restrict__ src = first ? x + n * sx.n : y + (n - NX) * sy.n;
-    const lp_strides s = first ? sx : sy;
+    const dc_strides4 s = first ? sx : sy;
 
-    for (int p = tid; p < LP_K1 * LP_CO / 4; p += 256) ((f32x4*)Wl)[p] = ((const f32x4*)wp)[p];
+    dc_f32_copy_w<LP_CO>(Wl, wp, LP_CO, LP_K1, LP_CO / 4, tid);
     const int iy0 = ty0 * L1_S - L1_PAD, ix0 = tx0 * L1_S - L1_PAD;
     for (int e = tid; e < L1_PE; e += 256) {
         const int c = e / (L1_PH * L1_PW), r = e - c * (L1_PH * L1_PW);
@@ -213,10 +200,7 @@ __global__ __launch_bounds__(256) void lpips_conv1_kernel(const T* __restrict__ 
     for (int b = 0; b < 2; ++b) pbase[b] = (ph * 2 + b) * L1_S * L1_PW + j * L1_S;
     const int abase = h * LP_CO + ch * 32 + j;
     f32x16 acc[2];
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
+    dc_f32_zero(acc);
 #pragma unroll
     for (int kp = 0; kp < LP_K1 / 2; ++kp) {               // lane half h takes k = 2 kp + h
         const float a = Wl[abase + kp * 2 * LP_CO];
@@ -233,7 +217,7 @@ __global__ __launch_bounds__(256) void lpips_conv1_kernel(const T* __restrict__ 
             float* __restrict__ yo = out + (((long long)n * LP_CO + ch * 32) * Ho + oy) * Wo + ox;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int col = (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int col = dc_f32_channel(r, h);
                 yo[(long long)col * Ho * Wo] = fmaxf(acc[b][r] + bias[ch * 32 + col], 0.f);
             }
         }
@@ -322,8 +306,6 @@ __global__ __launch_bounds__(64) void lpips_finalize_kernel(const double* __rest
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-inline long long lp_align(long long b) { return (b + 255) & ~255ll; }
-
 // Map sizes and workspace layout for M images (a call on N pairs has M = 2 N): the five post-ReLU maps, the two pooled maps,
 // and (pairs only) the tail partials.
 struct lp_plan {
@@ -348,22 +330,18 @@ bool make_lp_plan(int M, int pairs, int H, int W, lp_plan& p)
         p.h[l] = p.hp[1];
         p.w[l] = p.wp[1];
     }
-    long long off = 0, parts = 0;
+    dc_f32_bump<1> ws;
+    long long parts = 0;
     for (int l = 0; l < LP_LAYERS; ++l) {
-        p.feat_off[l] = off;
-        off += lp_align((long long)M * LP_CH[l] * p.h[l] * p.w[l] * 4);
+        p.feat_off[l] = ws.take((long long)M * LP_CH[l] * p.h[l] * p.w[l] * 4);
         p.seg.off[l] = parts;
         p.seg.count[l] = (p.h[l] * p.w[l] + LP_TAIL_PX - 1) / LP_TAIL_PX;
         p.seg.area[l] = (long long)p.h[l] * p.w[l];
         parts += (long long)pairs * p.seg.count[l];
     }
-    for (int l = 0; l < 2; ++l) {
-        p.pool_off[l] = off;
-        off += lp_align((long long)M * LP_CH[l] * p.hp[l] * p.wp[l] * 4);
-    }
-    p.part_off = off;
-    off += lp_align(parts * 8);
-    p.total = off;
+    for (int l = 0; l < 2; ++l) p.pool_off[l] = ws.take((long long)M * LP_CH[l] * p.hp[l] * p.wp[l] * 4);
+    p.part_off = ws.take(parts * 8);
+    p.total = ws.off;
     return true;
 }
 
@@ -398,7 +376,7 @@ void launch_conv(const float* x, const float* w, const float* b, float* y, int M
 }
 
 template <typename T>
-void launch_conv1(const void* x, const void* y, lp_strides sx, lp_strides sy, int NX, int M, const float* w, const float* b, float* out,
+void launch_conv1(const void* x, const void* y, dc_strides4 sx, dc_strides4 sy, int NX, int M, const float* w, const float* b, float* out,
                   int H, int W, int Ho, int Wo, int normalize, hipStream_t st)
 {
     auto kern = lpips_conv1_kernel<T>;
@@ -412,12 +390,12 @@ void launch_conv1(const void* x, const void* y, lp_strides sx, lp_strides sy, in
 void launch_pool(const float* x, float* y, int planes, int H, int W, int Ho, int Wo, hipStream_t st)
 {
     const long long total = (long long)planes * Ho * Wo;
-    const int grid = (int)min((long long)8192, (total + 255) / 256);
+    const int grid = dc_f32_blocks(total, 8192);
     hipLaunchKernelGGL(lpips_pool_kernel, dim3(grid), dim3(256), 0, st, x, y, H, W, Ho, Wo, total);
 }
 
 // The five post-ReLU maps of M images (the first NX from x, the rest from y) into f[0..4]; pool[0..1] take the pooled maps.
-void run_features(const void* x, const void* y, int u8, lp_strides sx, lp_strides sy, int NX, int M, int H, int W, int normalize,
+void run_features(const void* x, const void* y, int u8, dc_strides4 sx, dc_strides4 sy, int NX, int M, int H, int W, int normalize,
                   const float* wts, const lp_plan& p, float* const f[LP_LAYERS], float* const pool[2], hipStream_t st)
 {
     const lp_weights o = lp_weight_layout();
@@ -459,7 +437,7 @@ extern "C" int dc_lpips_alex(const void* x, const void* y, int x_u8, const long 
     float* f[LP_LAYERS];
     for (int l = 0; l < LP_LAYERS; ++l) f[l] = (float*)(base + p.feat_off[l]);
     float* pool[2] = {(float*)(base + p.pool_off[0]), (float*)(base + p.pool_off[1])};
-    const lp_strides sx{strides[0], strides[1], strides[2], strides[3]}, sy{strides[4], strides[5], strides[6], strides[7]};
+    const dc_strides4 sx(strides), sy(strides + 4);
     run_features(x, y, x_u8, sx, sy, N, 2 * N, H, W, normalize, weights, p, f, pool, st);
     const lp_weights o = lp_weight_layout();
     double* part = (double*)(base + p.part_off);
@@ -477,7 +455,7 @@ extern "C" int dc_lpips_alex_features(const void* x, int x_u8, const long long* 
     if (!x || !strides || !weights || !ws || !f1 || !f2 || !f3 || !f4 || !f5 || !make_lp_plan(N, 0, H, W, p)) return DC_ERR_INVALID;
     float* f[LP_LAYERS] = {f1, f2, f3, f4, f5};
     float* pool[2] = {(float*)ws, (float*)((char*)ws + (p.pool_off[1] - p.pool_off[0]))};   // this entry's scratch: the pooled maps only
-    const lp_strides sx{strides[0], strides[1], strides[2], strides[3]};
+    const dc_strides4 sx(strides);
     run_features(x, x, x_u8, sx, sx, N, N, H, W, normalize, weights, p, f, pool, (hipStream_t)stream);
     return dc_launch_status();
 }
@@ -493,7 +471,7 @@ extern "C" int dc_lpips_conv(int layer, const void* x, int x_u8, const long long
     if (layer == 0) {
         lp_plan p;
         if (!strides || !make_lp_plan(M, 0, H, W, p)) return DC_ERR_INVALID;
-        const lp_strides sx{strides[0], strides[1], strides[2], strides[3]};
+        const dc_strides4 sx(strides);
         if (x_u8)
             launch_conv1<uint8_t>(x, x, sx, sx, M, M, w, b, y, H, W, p.h[0], p.w[0], normalize, st);
         else

@@ -15,6 +15,7 @@ import ctypes
 import torch
 
 from . import lib
+from .metrics import fold_bn
 
 DATA_MEAN = (123.675, 116.28, 103.53)       # data_mean / data_div of every reference config (RGB, 0..255 scale)
 DATA_DIV = (58.395, 57.12, 57.375)
@@ -93,9 +94,8 @@ def fold_and_pack(weight, bias, bn, eps=BN_EPS):
     if bn is None:
         s, t = torch.ones(co, dtype=torch.float64), b
     else:
-        g, beta, mean, var = (x.detach().double().cpu() for x in bn)
-        s = g / torch.sqrt(var + eps)
-        t = beta - mean * s + b * s
+        s, t = fold_bn(*bn, eps)
+        t = t + b * s
     K = ci * k * k
     rows, cop = (K + 31) // 32 * 32, (co + 31) // 32 * 32
     m = torch.zeros(rows + 2, cop, dtype=torch.float64)

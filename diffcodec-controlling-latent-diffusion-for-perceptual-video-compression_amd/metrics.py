@@ -252,6 +252,85 @@ def calculate_metrics_batch(original, pred, lpips=None, fid=None, fvd=None, size
     return out
 
 
+# ------------------------------------------------------------------------------------------------- packed networks
+def _state_tensor(what, sd, key, shape):
+    if key not in sd:
+        raise ValueError(f"{what} state dict: missing key {key!r}")
+    t = sd[key]
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what} state dict: {key!r} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+    return t.detach().to("cpu", torch.float32)
+
+
+def fold_bn(weight, bias, mean, var, eps):
+    """Eval BatchNorm as y = s x + t, formed in fp64: s = weight / sqrt(var + eps), t = bias - mean s."""
+    g, b, m, v = (x.detach().double().cpu() for x in (weight, bias, mean, var))
+    s = g / torch.sqrt(v + eps)
+    return s, b - m * s
+
+
+class _PackedNet:
+    """What LPIPS, FrechetInceptionDistance and FrechetVideoDistance share: the packed fp32 weight vector on the CPU (`packed`), its
+    per-device copies, loading from a state dict, and running a batch in chunks that bound the scratch.  A subclass sets `_WHAT`
+    (the name in its messages), `_FLOATS` (the library's dc_*_weight_floats), `_pack` and `_chunk_bytes`."""
+    _FROM = "from_state_dict"
+
+    def _init_weights(self):
+        self.packed = None              # fp32 CPU vector (the subclass's pack_*_weights)
+        self._on_device = {}
+
+    @classmethod
+    def from_state_dict(cls, state_dict, **kwargs):
+        return cls(**kwargs).load_state_dict(state_dict)
+
+    def load_state_dict(self, state_dict, *more):
+        packed = self._pack(state_dict, *more)
+        want = getattr(lib.load(), self._FLOATS)()
+        if packed.numel() != want:
+            raise RuntimeError(f"packed {self._WHAT} weights hold {packed.numel()} floats, the library expects {want}")
+        self.packed = packed
+        self._on_device = {}
+        return self
+
+    def to(self, device):
+        self._weights(torch.device(device))
+        return self
+
+    @staticmethod
+    def _device(device):
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        return device
+
+    def _weights(self, device):
+        if self.packed is None:
+            raise RuntimeError(f"{type(self).__name__} has no weights: call load_state_dict / {self._FROM} (nothing is downloaded)")
+        device = self._device(device)
+        w = self._on_device.get(device)
+        if w is None:
+            w = self._on_device[device] = self.packed.to(device)
+        return w
+
+    @staticmethod
+    def _stage(x, y=None):
+        """(x, y as uint8 or fp32 on the GPU, whether the caller passed host tensors)"""
+        X, Y, host = _to_device(x, x if y is None else y)
+        if X.dtype != torch.uint8 and X.dtype != torch.float32:
+            X, Y = X.float(), Y.float()
+        return X, Y, host
+
+    def _step(self, n, ws_bytes):
+        """items per launch sequence: as many as keep `ws_bytes(items)` of scratch under the class's chunk bound"""
+        return max(1, min(n, self._chunk_bytes() // max(1, ws_bytes(1))))
+
+    def _slices(self, n, device, ws_bytes):
+        """(slice of the batch, its scratch) chunk by chunk"""
+        step = self._step(n, ws_bytes)
+        for i in range(0, n, step):
+            sl = slice(i, min(i + step, n))
+            yield sl, torch.empty(ws_bytes(sl.stop - sl.start), dtype=torch.uint8, device=device)
+
+
 # ------------------------------------------------------------------------------------------------------------- LPIPS
 LPIPS_CHANNELS = (64, 192, 384, 256, 256)
 LPIPS_CIN = (3, 64, 192, 384, 256)
@@ -271,15 +350,6 @@ def lpips_map_sizes(h, w):
     return [s1, s2, s3, s3, s3]
 
 
-def _lpips_tensor(sd, key, shape):
-    if key not in sd:
-        raise ValueError(f"LPIPS state dict: missing key {key!r}")
-    t = sd[key]
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError(f"LPIPS state dict: {key!r} has shape {tuple(t.shape)}, expected {tuple(shape)}")
-    return t.detach().to("cpu", torch.float32)
-
-
 def pack_lpips_weights(state_dict, lin_state_dict=None):
     """One fp32 CPU vector in the layout dc_lpips_alex reads: per conv the K-major matrix [(ci, ky, kx)][Cout] (conv1 followed by
     one zero row, 363 -> 364) and its bias, then the five lin vectors.  Accepts the two layouts of LPIPS.load_state_dict."""
@@ -290,18 +360,18 @@ def pack_lpips_weights(state_dict, lin_state_dict=None):
     parts = []
     for l, (co, ci, k, pos) in enumerate(zip(LPIPS_CHANNELS, LPIPS_CIN, LPIPS_KERNEL, LPIPS_FEATURE_INDEX)):
         stem = f"net.slice{l + 1}.{pos}" if library else f"features.{pos}"
-        w = _lpips_tensor(sd, stem + ".weight", (co, ci, k, k))
-        b = _lpips_tensor(sd, stem + ".bias", (co,))
+        w = _state_tensor("LPIPS", sd, stem + ".weight", (co, ci, k, k))
+        b = _state_tensor("LPIPS", sd, stem + ".bias", (co,))
         wk = w.reshape(co, ci * k * k).t().contiguous()
         if l == 0:
             wk = torch.cat([wk, torch.zeros(1, co)], 0)
         parts += [wk.reshape(-1), b]
     for l, co in enumerate(LPIPS_CHANNELS):
-        parts.append(_lpips_tensor(sd, f"lin{l}.model.1.weight", (1, co, 1, 1)).reshape(-1))
+        parts.append(_state_tensor("LPIPS", sd, f"lin{l}.model.1.weight", (1, co, 1, 1)).reshape(-1))
     return torch.cat(parts).contiguous()
 
 
-class LPIPS:
+class LPIPS(_PackedNet):
     """`lpips.LPIPS(net='alex')` (version 0.1) on the device in exact fp32 (csrc/lpips.hip): call surface of the library's module,
     `model(in0, in1, retPerLayer=False, normalize=False)` -> fp32 [N,1,1,1] (and the list of five per-layer [N,1,1,1]).
 
@@ -334,37 +404,18 @@ class LPIPS:
         if str(version) != "0.1":
             raise NotImplementedError(f"LPIPS version {version!r}: only '0.1' is implemented")
         self.normfix = bool(normfix)
-        self.packed = None              # fp32 CPU vector (pack_lpips_weights)
-        self._on_device = {}
+        self._init_weights()
+
+    _WHAT, _FLOATS, _FROM = "LPIPS", "dc_lpips_weight_floats", "LPIPS.from_state_dict"
+    _pack = staticmethod(pack_lpips_weights)
+    _chunk_bytes = staticmethod(lambda: LPIPS_CHUNK_BYTES)
 
     @classmethod
     def from_state_dict(cls, state_dict, lin_state_dict=None, **kwargs):
-        m = cls(**kwargs)
-        m.load_state_dict(state_dict, lin_state_dict)
-        return m
+        return cls(**kwargs).load_state_dict(state_dict, lin_state_dict)
 
     def load_state_dict(self, state_dict, lin_state_dict=None):
-        packed = pack_lpips_weights(state_dict, lin_state_dict)
-        want = lib.load().dc_lpips_weight_floats()
-        if packed.numel() != want:
-            raise RuntimeError(f"packed LPIPS weights hold {packed.numel()} floats, the library expects {want}")
-        self.packed = packed
-        self._on_device = {}
-        return self
-
-    def to(self, device):
-        self._weights(torch.device(device))
-        return self
-
-    def _weights(self, device):
-        if self.packed is None:
-            raise RuntimeError("LPIPS has no weights: call load_state_dict / LPIPS.from_state_dict (nothing is downloaded)")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        w = self._on_device.get(device)
-        if w is None:
-            w = self._on_device[device] = self.packed.to(device)
-        return w
+        return super().load_state_dict(state_dict, lin_state_dict)
 
     @staticmethod
     def _check_image(c, h, w):
@@ -377,18 +428,13 @@ class LPIPS:
         X, Y = _check_pair(in0, in1)
         (n, c, h, w), _ = _nchw(X)
         self._check_image(c, h, w)
-        X, Y, host = _to_device(X, Y)
-        if X.dtype != torch.uint8 and X.dtype != torch.float32:
-            X, Y = X.float(), Y.float()
+        X, Y, host = self._stage(X, Y)
         wts = self._weights(X.device)
-        L = lib.load()
-        step = max(1, min(n, LPIPS_CHUNK_BYTES // max(1, L.dc_lpips_ws_bytes(1, h, w))))
         outs = []
         with torch.cuda.device(X.device):
             stream = torch.cuda.current_stream().cuda_stream
-            for i in range(0, n, step):
-                xs, ys, (m, _, _, _), strides, u8 = _prepare(X[i:i + step], Y[i:i + step])
-                scratch = torch.empty(L.dc_lpips_ws_bytes(m, h, w), dtype=torch.uint8, device=X.device)
+            for sl, scratch in self._slices(n, X.device, lambda m: lib.load().dc_lpips_ws_bytes(m, h, w)):
+                xs, ys, (m, _, _, _), strides, u8 = _prepare(X[sl], Y[sl])
                 out = torch.empty(6 * m, dtype=torch.float64, device=X.device)
                 lib.call("dc_lpips_alex", xs.data_ptr(), ys.data_ptr(), u8, strides, m, h, w, int(bool(normalize)), int(self.normfix),
                          wts.data_ptr(), scratch.data_ptr(), out.data_ptr(), stream)
@@ -408,23 +454,17 @@ class LPIPS:
         X, _ = _check_pair(x, x)
         (n, c, h, w), _ = _nchw(X)
         self._check_image(c, h, w)
-        X, _, host = _to_device(X, X)
-        if X.dtype != torch.uint8 and X.dtype != torch.float32:
-            X = X.float()
+        X, _, host = self._stage(X)
         wts = self._weights(X.device)
-        L = lib.load()
         sizes = lpips_map_sizes(h, w)
         feats = [torch.empty((n, co) + s, dtype=torch.float32, device=X.device) for co, s in zip(LPIPS_CHANNELS, sizes)]
-        step = max(1, min(n, LPIPS_CHUNK_BYTES // max(1, L.dc_lpips_features_ws_bytes(1, h, w))))
         with torch.cuda.device(X.device):
             stream = torch.cuda.current_stream().cuda_stream
-            for i in range(0, n, step):
-                xs = X[i:i + step]
-                m = xs.shape[0]
-                _, sx = _nchw(xs)
-                scratch = torch.empty(L.dc_lpips_features_ws_bytes(m, h, w), dtype=torch.uint8, device=X.device)
-                lib.call("dc_lpips_alex_features", xs.data_ptr(), int(xs.dtype == torch.uint8), (ctypes.c_longlong * 4)(*sx), m, h, w,
-                         int(bool(normalize)), wts.data_ptr(), scratch.data_ptr(), *[f[i:i + step].data_ptr() for f in feats], stream)
+            for sl, scratch in self._slices(n, X.device, lambda m: lib.load().dc_lpips_features_ws_bytes(m, h, w)):
+                xs = X[sl]
+                lib.call("dc_lpips_alex_features", xs.data_ptr(), int(xs.dtype == torch.uint8), (ctypes.c_longlong * 4)(*_nchw(xs)[1]),
+                         xs.shape[0], h, w, int(bool(normalize)), wts.data_ptr(), scratch.data_ptr(), *[f[sl].data_ptr() for f in feats],
+                         stream)
         return [f.cpu() for f in feats] if host else feats
 
 
@@ -440,28 +480,19 @@ FID_BN_EPS = 1e-3
 FID_CHUNK_BYTES = 1 << 30                            # scratch bound of one launch sequence (12.2 MB of maps per image)
 
 
-def _fid_tensor(sd, key, shape):
-    if key not in sd:
-        raise ValueError(f"FID state dict: missing key {key!r}")
-    t = sd[key]
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError(f"FID state dict: {key!r} has shape {tuple(t.shape)}, expected {tuple(shape)}")
-    return t.detach().to("cpu", torch.float32)
-
-
 def pack_fid_weights(state_dict):
     """One fp32 CPU vector in the layout dc_fid_features reads: per block the K-major matrix [(ci, ky, kx)][Cout] (block 1 followed
     by one zero row, 27 -> 28), then s = bn.weight / sqrt(running_var + 1e-3) and t = bn.bias - running_mean * s, both formed in
     fp64 and rounded to fp32."""
     parts = []
     for l, (name, ci, co) in enumerate(zip(FID_BLOCKS, FID_CIN, FID_COUT)):
-        w = _fid_tensor(state_dict, f"{name}.conv.weight", (co, ci, 3, 3))
-        g, b, m, v = (_fid_tensor(state_dict, f"{name}.bn.{k}", (co,)).double() for k in ("weight", "bias", "running_mean", "running_var"))
+        w = _state_tensor("FID", state_dict, f"{name}.conv.weight", (co, ci, 3, 3))
+        s, t = fold_bn(*(_state_tensor("FID", state_dict, f"{name}.bn.{k}", (co,)) for k in ("weight", "bias", "running_mean", "running_var")),
+                       FID_BN_EPS)
         wk = w.reshape(co, ci * 9).t().contiguous()
         if l == 0:
             wk = torch.cat([wk, torch.zeros(1, co)], 0)
-        s = g / torch.sqrt(v + FID_BN_EPS)
-        parts += [wk.reshape(-1), s.float(), (b - m * s).float()]
+        parts += [wk.reshape(-1), s.float(), t.float()]
     return torch.cat(parts).contiguous()
 
 
@@ -496,7 +527,7 @@ def frechet_distance(state_real, state_fake):
     return _frechet_value(mu_r, cov_r, mu_f, cov_f)
 
 
-class FrechetInceptionDistance:
+class FrechetInceptionDistance(_PackedNet):
     """`torchmetrics.image.fid.FrechetInceptionDistance(feature=64)` on the device in exact fp32 (csrc/fid.hip): `update(imgs, real)`
     accumulates, `compute()` returns the value as a Python float.
 
@@ -531,45 +562,18 @@ class FrechetInceptionDistance:
         if feature != 64:
             raise NotImplementedError(f"FrechetInceptionDistance feature {feature!r}: only 64 is implemented")
         self.normalize = bool(normalize)
-        self.packed = None
-        self._on_device = {}
+        self._init_weights()
         self._state = {True: torch.zeros(FID_STATE, dtype=torch.float64), False: torch.zeros(FID_STATE, dtype=torch.float64)}
 
-    @classmethod
-    def from_state_dict(cls, state_dict, **kwargs):
-        m = cls(**kwargs)
-        m.load_state_dict(state_dict)
-        return m
-
-    def load_state_dict(self, state_dict):
-        packed = pack_fid_weights(state_dict)
-        want = lib.load().dc_fid_weight_floats()
-        if packed.numel() != want:
-            raise RuntimeError(f"packed FID weights hold {packed.numel()} floats, the library expects {want}")
-        self.packed = packed
-        self._on_device = {}
-        return self
+    _WHAT, _FLOATS = "FID", "dc_fid_weight_floats"
+    _pack = staticmethod(pack_fid_weights)
+    _chunk_bytes = staticmethod(lambda: FID_CHUNK_BYTES)
 
     def to(self, device):
+        super().to(device)
         device = self._device(torch.device(device))
-        self._weights(device)
         self._state = {k: v.to(device) for k, v in self._state.items()}
         return self
-
-    @staticmethod
-    def _device(device):
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        return device
-
-    def _weights(self, device):
-        if self.packed is None:
-            raise RuntimeError("FrechetInceptionDistance has no weights: call load_state_dict / from_state_dict (nothing is downloaded)")
-        device = self._device(device)
-        w = self._on_device.get(device)
-        if w is None:
-            w = self._on_device[device] = self.packed.to(device)
-        return w
 
     def _images(self, imgs):
         """(operand on the GPU, whether the caller passed a host tensor, (n, h, w))"""
@@ -587,29 +591,23 @@ class FrechetInceptionDistance:
             raise ValueError(f"FID takes 3-channel images, got {c} channels")
         if h < 1 or w < 1:
             raise ValueError(f"FID needs H, W >= 1, got {h}x{w}")
-        X, _, host = _to_device(imgs, imgs)
-        if X.dtype != torch.uint8 and X.dtype != torch.float32:
-            X = X.float()
+        X, _, host = self._stage(imgs)
         return X, host, (n, h, w)
 
     def _chunks(self, n, h, w):
-        return max(1, min(n, FID_CHUNK_BYTES // max(1, lib.load().dc_fid_ws_bytes(1, h, w))))
+        return self._step(n, lambda m: lib.load().dc_fid_ws_bytes(m, h, w))
 
     def features(self, imgs):
         """fp32 [N,64]: the pooled features of `imgs` (uint8 NHWC, or float NCHW with normalize=True)."""
         X, host, (n, h, w) = self._images(imgs)
         wts = self._weights(X.device)
-        L = lib.load()
         out = torch.empty((n, FID_FEATURES), dtype=torch.float32, device=X.device)
-        step = self._chunks(n, h, w)
         with torch.cuda.device(X.device):
             stream = torch.cuda.current_stream().cuda_stream
-            for i in range(0, n, step):
-                xs = X[i:i + step]
-                m = xs.shape[0]
-                scratch = torch.empty(L.dc_fid_ws_bytes(m, h, w), dtype=torch.uint8, device=X.device)
-                lib.call("dc_fid_features", xs.data_ptr(), int(xs.dtype == torch.uint8), (ctypes.c_longlong * 4)(*_nchw(xs)[1]), m, h, w,
-                         wts.data_ptr(), scratch.data_ptr(), out[i:i + step].data_ptr(), stream)
+            for sl, scratch in self._slices(n, X.device, lambda m: lib.load().dc_fid_ws_bytes(m, h, w)):
+                xs = X[sl]
+                lib.call("dc_fid_features", xs.data_ptr(), int(xs.dtype == torch.uint8), (ctypes.c_longlong * 4)(*_nchw(xs)[1]), xs.shape[0],
+                         h, w, wts.data_ptr(), scratch.data_ptr(), out[sl].data_ptr(), stream)
         return out.cpu() if host else out
 
     def maps(self, imgs):
@@ -750,15 +748,6 @@ def fvd_resized_size(h, w):
     return (FVD_SIZE, math.ceil(w * scale)) if h < w else (math.ceil(h * scale), FVD_SIZE)
 
 
-def _fvd_tensor(sd, key, shape):
-    if key not in sd:
-        raise ValueError(f"FVD state dict: missing key {key!r}")
-    t = sd[key]
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError(f"FVD state dict: {key!r} has shape {tuple(t.shape)}, expected {tuple(shape)}")
-    return t.detach().to("cpu", torch.float32)
-
-
 def pack_fvd_unit(w, s, t):
     """One Unit3D in the layout dc_fvd_conv reads: the K-major matrix [(ci, kt, kh, kw)][Cout rounded up to 32] with the zero rows
     of its kernel class (7: one after the 49 taps of every (ci, kt); 3: up to a multiple of 4 input channels; 1: up to a multiple of
@@ -787,12 +776,12 @@ def pack_fvd_weights(state_dict, bn_eps=FVD_BN_EPS):
     with s = 1, t = its bias."""
     parts = []
     for name, ci, co, k, _ in fvd_units():
-        w = _fvd_tensor(state_dict, f"{name}.conv3d.weight", (co, ci, k, k, k))
-        g, b, m, v = (_fvd_tensor(state_dict, f"{name}.bn.{q}", (co,)).double() for q in ("weight", "bias", "running_mean", "running_var"))
-        s = g / torch.sqrt(v + bn_eps)
-        parts.append(pack_fvd_unit(w, s, b - m * s))
-    w = _fvd_tensor(state_dict, "logits.conv3d.weight", (FVD_FEATURES, 1024, 1, 1, 1))
-    b = _fvd_tensor(state_dict, "logits.conv3d.bias", (FVD_FEATURES,))
+        w = _state_tensor("FVD", state_dict, f"{name}.conv3d.weight", (co, ci, k, k, k))
+        s, t = fold_bn(*(_state_tensor("FVD", state_dict, f"{name}.bn.{q}", (co,)) for q in ("weight", "bias", "running_mean", "running_var")),
+                       bn_eps)
+        parts.append(pack_fvd_unit(w, s, t))
+    w = _state_tensor("FVD", state_dict, "logits.conv3d.weight", (FVD_FEATURES, 1024, 1, 1, 1))
+    b = _state_tensor("FVD", state_dict, "logits.conv3d.bias", (FVD_FEATURES,))
     parts.append(pack_fvd_unit(w, torch.ones(FVD_FEATURES), b))
     return torch.cat(parts).contiguous()
 
@@ -805,7 +794,7 @@ def _fvd_stats(rows):
     return mu, c.t() @ c / (n - 1)
 
 
-class FrechetVideoDistance:
+class FrechetVideoDistance(_PackedNet):
     """The FVD of the reference's clip scoring (test_utils.py:45-70, fvd_utils/models/fvd) on the device in exact fp32
     (csrc/fvd.hip): the Inception-v1 I3D network of pytorch_i3d.py, 400 logits per video, and the Frechet distance of two sets of
     such rows.
@@ -837,38 +826,14 @@ class FrechetVideoDistance:
     def __init__(self, bn_eps=FVD_BN_EPS, byte_range=False):
         self.bn_eps = float(bn_eps)
         self.byte_range = bool(byte_range)
-        self.packed = None
-        self._on_device = {}
+        self._init_weights()
         self._rows = {True: [], False: []}
 
-    @classmethod
-    def from_state_dict(cls, state_dict, **kwargs):
-        m = cls(**kwargs)
-        m.load_state_dict(state_dict)
-        return m
+    _WHAT, _FLOATS = "FVD", "dc_fvd_weight_floats"
+    _chunk_bytes = staticmethod(lambda: FVD_CHUNK_BYTES)
 
-    def load_state_dict(self, state_dict):
-        packed = pack_fvd_weights(state_dict, self.bn_eps)
-        want = lib.load().dc_fvd_weight_floats()
-        if packed.numel() != want:
-            raise RuntimeError(f"packed FVD weights hold {packed.numel()} floats, the library expects {want}")
-        self.packed = packed
-        self._on_device = {}
-        return self
-
-    def to(self, device):
-        self._weights(torch.device(device))
-        return self
-
-    def _weights(self, device):
-        if self.packed is None:
-            raise RuntimeError("FrechetVideoDistance has no weights: call load_state_dict / from_state_dict (nothing is downloaded)")
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        w = self._on_device.get(device)
-        if w is None:
-            w = self._on_device[device] = self.packed.to(device)
-        return w
+    def _pack(self, state_dict):
+        return pack_fvd_weights(state_dict, self.bn_eps)
 
     @staticmethod
     def _check(videos, min_frames=FVD_MIN_FRAMES):
@@ -893,16 +858,21 @@ class FrechetVideoDistance:
 
     def _operand(self, videos, min_frames=FVD_MIN_FRAMES):
         dims, _ = self._check(videos, min_frames)
-        X, _, host = _to_device(videos, videos)
-        if X.dtype != torch.uint8 and X.dtype != torch.float32:
-            X = X.float()
+        X, _, host = self._stage(videos)
         return X, host, dims
 
+    @staticmethod
+    def _ws_bytes(t, h, w):
+        """m -> dc_fvd_ws_bytes(m, t, h, w); a size the library refuses is a ValueError"""
+        def ws_bytes(m):
+            nbytes = lib.load().dc_fvd_ws_bytes(m, t, h, w)
+            if nbytes < 0:
+                raise ValueError(f"FVD takes videos of at most {FVD_MAX_FRAMES} frames of at most {FVD_MAX_SIDE} x {FVD_MAX_SIDE}, got {t} x {h} x {w}")
+            return nbytes
+        return ws_bytes
+
     def _chunks(self, n, t, h, w):
-        one = lib.load().dc_fvd_ws_bytes(1, t, h, w)
-        if one < 0:
-            raise ValueError(f"FVD takes videos of at most {FVD_MAX_FRAMES} frames of at most {FVD_MAX_SIDE} x {FVD_MAX_SIDE}, got {t} x {h} x {w}")
-        return max(1, min(n, FVD_CHUNK_BYTES // max(1, one)))
+        return self._step(n, self._ws_bytes(t, h, w))
 
     def _call_args(self, xs, t, h, w):
         (m, _, _, _), strides = self._check(xs, 1)
@@ -914,34 +884,25 @@ class FrechetVideoDistance:
         """fp32 [N,400]: the logits of `videos` (uint8 [N,T,H,W,3] or floating [N,T,3,H,W])."""
         X, host, (n, t, h, w) = self._operand(videos)
         wts = self._weights(X.device)
-        L = lib.load()
         out = torch.empty((n, FVD_FEATURES), dtype=torch.float32, device=X.device)
-        step = self._chunks(n, t, h, w)
         with torch.cuda.device(X.device):
             stream = torch.cuda.current_stream().cuda_stream
-            for i in range(0, n, step):
-                xs = X[i:i + step]
-                scratch = torch.empty(L.dc_fvd_ws_bytes(xs.shape[0], t, h, w), dtype=torch.uint8, device=X.device)
-                lib.call("dc_fvd_features", *self._call_args(xs, t, h, w), wts.data_ptr(), scratch.data_ptr(), out[i:i + step].data_ptr(),
-                         stream)
+            for sl, scratch in self._slices(n, X.device, self._ws_bytes(t, h, w)):
+                lib.call("dc_fvd_features", *self._call_args(X[sl], t, h, w), wts.data_ptr(), scratch.data_ptr(), out[sl].data_ptr(), stream)
         return out.cpu() if host else out
 
     def endpoints(self, videos):
         """The 16 endpoint maps (FVD_ENDPOINTS order), contiguous fp32 [N,C,T',S,S] (the test seam; `features` keeps them in scratch)."""
         X, host, (n, t, h, w) = self._operand(videos)
         wts = self._weights(X.device)
-        L = lib.load()
         outs = [torch.empty((n,) + s, dtype=torch.float32, device=X.device) for s in fvd_endpoint_shapes(t)]
         feat = torch.empty((n, FVD_FEATURES), dtype=torch.float32, device=X.device)
-        step = self._chunks(n, t, h, w)
         with torch.cuda.device(X.device):
             stream = torch.cuda.current_stream().cuda_stream
-            for i in range(0, n, step):
-                xs = X[i:i + step]
-                scratch = torch.empty(L.dc_fvd_ws_bytes(xs.shape[0], t, h, w), dtype=torch.uint8, device=X.device)
-                maps = (ctypes.c_void_p * len(outs))(*[o[i:i + step].data_ptr() for o in outs])
-                lib.call("dc_fvd_endpoints", *self._call_args(xs, t, h, w), wts.data_ptr(), scratch.data_ptr(), maps,
-                         feat[i:i + step].data_ptr(), stream)
+            for sl, scratch in self._slices(n, X.device, self._ws_bytes(t, h, w)):
+                maps = (ctypes.c_void_p * len(outs))(*[o[sl].data_ptr() for o in outs])
+                lib.call("dc_fvd_endpoints", *self._call_args(X[sl], t, h, w), wts.data_ptr(), scratch.data_ptr(), maps,
+                         feat[sl].data_ptr(), stream)
         return [o.cpu() for o in outs] if host else outs
 
     def preprocess(self, videos):

@@ -2,7 +2,7 @@
 N = 2 (the two directions of one frame) and N = 16, and report each convolution family's share and TFLOP/s against the
 157.3 TFLOP/s fp32 matrix peak of the MI355X.
 
-    python tools/bench_cmp.py [--out profiles/cmp_bench.txt]
+    python tools/bench_cmp.py [--out profiles/cmp_bench.txt] [--lib PATH]      (--lib: another build of the same ABI)
 
 Whole-call times are the median of `--iters` eager calls and of as many replays of a captured graph, after warm-up; family times
 come from a separate pass over HipCMP.staged_endpoints (the same launches, driven one by one) with lib.LaunchTimer (two events
@@ -42,7 +42,10 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--size", type=int, default=512)
+    ap.add_argument("--lib", default=None, help="another build of libdiffcodec_hip.so (same ABI)")
     args = ap.parse_args()
+    if args.lib:
+        lib.LIB_PATH = os.path.abspath(args.lib)
     model = HipCMP.from_state_dict(R.synth_weights("skip"), R.CONFIGS["skip"], "cuda")
     lines = [f"HipCMP.flow, MotionDecoderSkipLayer, {args.size} x {args.size}, fp32 on v_mfma_f32_32x32x2_f32 "
              f"({torch.cuda.get_device_name(0)}); peak {PEAK} TFLOP/s"]

@@ -13,7 +13,9 @@ call and per image), `features` alone, the accumulate launch alone and, per conv
 FVD leg (csrc/fvd.hip, seeded random weights): `features` of one 16 x 512 x 512 uint8 video and of a batch of 8, one JSON line each
 with the milliseconds per call and per video and the TFLOP/s over the convolutions' 27.8 G multiply-adds per 16-frame video.
 
-    python tools/bench_metrics.py [--batch 16] [--iters 20] [--no-lpips] [--no-fid] [--no-fvd] [--only-fvd]"""
+    python tools/bench_metrics.py [--batch 16] [--iters 20] [--no-lpips] [--no-fid] [--no-fvd] [--only-fvd] [--no-ssim] [--lib PATH]
+
+`--lib` times another build of the same ABI (one process per library); `--no-ssim` skips the PSNR / MS-SSIM leg."""
 import argparse
 import json
 import os
@@ -167,13 +169,17 @@ def main():
     ap.add_argument("--no-fid", action="store_true")
     ap.add_argument("--no-fvd", action="store_true")
     ap.add_argument("--only-fvd", action="store_true")
+    ap.add_argument("--no-ssim", action="store_true")
+    ap.add_argument("--lib", default=None, help="another build of libdiffcodec_hip.so (same ABI)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_metrics needs the GPU"
-    from diffcodec_amd import metrics as M
+    from diffcodec_amd import lib, metrics as M
+    if a.lib:
+        lib.LIB_PATH = os.path.abspath(a.lib)
     if a.only_fvd:
         return fvd_leg(a.iters)
     g = torch.Generator(device="cuda").manual_seed(0)
-    for h, w in ((512, 512), (1080, 1920)):
+    for h, w in () if a.no_ssim else ((512, 512), (1080, 1920)):
         x = torch.randint(0, 256, (a.batch, h, w, 3), dtype=torch.uint8, device="cuda", generator=g)
         noise = torch.randint(-8, 9, (a.batch, h, w, 3), device="cuda", generator=g)
         y = (x.int() + noise).clamp(0, 255).to(torch.uint8)
