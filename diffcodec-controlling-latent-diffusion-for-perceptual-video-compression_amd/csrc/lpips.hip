@@ -24,6 +24,7 @@
 //   per workgroup, then one finalize launch sums each (layer, image) slab in a fixed order into the spatial mean and the five means
 //   into the value.
 #include "dc_f32_mfma.h"
+#include "dc_lpips_geom.h"
 #include "../../include/diffcodec_hip.h"
 
 namespace {
@@ -412,6 +413,15 @@ void run_features(const void* x, const void* y, int u8, dc_strides4 sx, dc_strid
 }
 
 }  // namespace
+
+bool dc_lpips_geometry(int M, int pairs, int H, int W, dc_lpips_geom* g)
+{
+    lp_plan p;
+    if (!make_lp_plan(M, pairs, H, W, p)) return false;
+    for (int l = 0; l < LP_LAYERS; ++l) g->h[l] = p.h[l], g->w[l] = p.w[l], g->feat_off[l] = p.feat_off[l];
+    g->total = p.total;
+    return true;
+}
 
 extern "C" int dc_lpips_weight_floats(void) { return (int)lp_weight_layout().total; }
 

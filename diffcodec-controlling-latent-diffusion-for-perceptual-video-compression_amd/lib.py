@@ -126,6 +126,23 @@ FLOW_SIGNATURES = {
     "dc_cmp_endpoints": [i32, vp, i32, POINTER(i64), vp, i32, i32, i32, i32, f32, vp, vp, POINTER(vp), vp, vp, vp, vp],
 }
 
+# name -> argtypes of include/diffcodec_loss_hip.h (csrc/lpips_grad.hip, csrc/edge_loss.hip; tests/test_loss_abi.py cross-checks
+# that header)
+LOSS_SIGNATURES = {
+    "dc_lpips_dgrad_weight_floats": [],
+    "dc_lpips_keep_ws_bytes": [i32, i32, i32],
+    "dc_lpips_train_ws_bytes": [i32, i32, i32, i32],
+    "dc_lpips_alex_keep": [vp, vp, POINTER(i64), i32, i32, i32, i32, vp, vp, vp, vp],
+    "dc_lpips_alex_backward": [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp],
+    "dc_lpips_tail_grad": [i32, vp, i32, i32, i32, vp, vp, vp, vp],
+    "dc_lpips_conv_dgrad": [i32, vp, i32, i32, i32, vp, vp, vp, vp, vp],
+    "dc_lpips_pool_grad": [vp, vp, vp, i32, i32, i32, vp, vp],
+    "dc_lpips_conv1_dgrad": [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp],
+    "dc_sobel_edge_ws_bytes": [i32, i32, i32, i32],
+    "dc_sobel_edge_loss": [vp, vp, POINTER(i64), i32, i32, i32, i32, i32, vp, vp, vp, vp],
+    "dc_sobel_edge_grad": [vp, vp, POINTER(i64), i32, i32, i32, i32, i32, vp, i32, f32, vp, vp],
+}
+
 _lib = None
 
 
@@ -148,10 +165,11 @@ def load():
         fn.argtypes = args
         fn.restype = c_longlong if name.endswith("_ws_bytes") else c_int
     lib.dc_gn_stats_chunks.restype = c_int
-    for name, args in FLOW_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.argtypes = args
-        fn.restype = c_longlong if name.endswith("_ws_bytes") else c_int
+    for table in (FLOW_SIGNATURES, LOSS_SIGNATURES):
+        for name, args in table.items():
+            fn = getattr(lib, name)
+            fn.argtypes = args
+            fn.restype = c_longlong if name.endswith("_ws_bytes") else c_int
     _lib = lib
     return lib
 
