@@ -4,7 +4,8 @@
     model = HipCMP.from_state_dict(torch.load(checkpoint), config["model"]["module"])
     logits = model(image, sparse)            # [N, 2 nbins, h, w]                      CMP.forward
     flow = model.flow(image, sparse)         # [N, 2, H, W] in pixels                  CMP.eval without its loss
-    source = PropagatedFlowSource(DirectorySource(...), model, stride=32)
+    source = PropagatedFlowSource(DirectorySource(...), model, stride=32)                  # 'grid' guide points
+    source = PropagatedFlowSource(DirectorySource(...), model, stride=80, nms_ks=15)      # 'grid' and 'watershed'
     decode_clip(pipe, source, ..., score=True)
 
 Inference only, eval mode, exact fp32: BatchNorm is folded on the host in fp64 to one fma per channel.  No weights ship with the
@@ -15,6 +16,7 @@ import ctypes
 import torch
 
 from . import lib
+from .guide_points import sample_watershed, stride_from_bg_ratio, watershed_points  # noqa: F401  (the other guide samplers)
 from .metrics import fold_bn
 
 DATA_MEAN = (123.675, 116.28, 103.53)       # data_mean / data_div of every reference config (RGB, 0..255 scale)
@@ -434,10 +436,13 @@ class PropagatedFlowSource:
     of its 'grid' samples (one every `stride` pixels) conditioned on the previous anchor cond[:, :3], and flow[:, 2:] by the
     propagation of its samples conditioned on the next anchor cond[:, 3:].  The model is fed the anchors as uint8 frames
     re-quantised from `cond` (`anchors_u8`: cond * 255, rounded, clamped), which for a source that loaded 8-bit frames are the
-    frames' own bytes.  Everything else of the inner source (ground_truth, warp, with_warp, noise, ...) passes through."""
+    frames' own bytes.  With `nms_ks` the samples are the reference configs' ['grid', 'watershed'] pair (`sample_watershed` with
+    that NMS window) instead of the grid alone.  Everything else of the inner source (ground_truth, warp, with_warp, noise, ...)
+    passes through."""
 
-    def __init__(self, source, model, stride=32):
+    def __init__(self, source, model, stride=32, nms_ks=None):
         self.source, self.model, self.stride = source, model, int(stride)
+        self.nms_ks = None if nms_ks is None else int(nms_ks)
 
     def __getattr__(self, name):                                          # only reached for what this class does not define
         return getattr(self.source, name)
@@ -447,6 +452,7 @@ class PropagatedFlowSource:
         a_prev, a_next = anchors_u8(cond)
         B = cond.shape[0]
         flow = flow.float()
-        sparse = sample_grid(torch.cat([flow[:, :2], flow[:, 2:]], 0), self.stride)
+        both = torch.cat([flow[:, :2], flow[:, 2:]], 0)
+        sparse = sample_grid(both, self.stride) if self.nms_ks is None else sample_watershed(both, self.nms_ks, stride=self.stride)
         dense = self.model.flow(torch.cat([a_prev, a_next], 0), sparse)  # one batch: the result does not depend on the batching
         return cond, torch.cat([dense[:B], dense[B:]], 1).to(flow.dtype)

@@ -143,6 +143,17 @@ LOSS_SIGNATURES = {
     "dc_sobel_edge_grad": [vp, vp, POINTER(i64), i32, i32, i32, i32, i32, vp, i32, f32, vp, vp],
 }
 
+# name -> argtypes of include/diffcodec_guide_hip.h (csrc/guide_points.hip; tests/test_guide_ref.py cross-checks that header)
+GUIDE_SIGNATURES = {
+    "dc_guide_ws_bytes": [i32, i32, i32],
+    "dc_guide_edge": [vp, i32, i32, i32, vp, vp, vp, vp],
+    "dc_guide_edt": [vp, i32, i32, i32, vp, vp, vp],
+    "dc_guide_nms": [vp, i32, i32, i32, i32, vp, vp, vp],
+    "dc_guide_select": [vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp],
+    "dc_guide_scatter": [vp, i32, i32, i32, i32, vp, vp, i32, vp, vp],
+    "dc_guide_watershed": [vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp],
+}
+
 _lib = None
 
 
@@ -165,7 +176,7 @@ def load():
         fn.argtypes = args
         fn.restype = c_longlong if name.endswith("_ws_bytes") else c_int
     lib.dc_gn_stats_chunks.restype = c_int
-    for table in (FLOW_SIGNATURES, LOSS_SIGNATURES):
+    for table in (FLOW_SIGNATURES, LOSS_SIGNATURES, GUIDE_SIGNATURES):
         for name, args in table.items():
             fn = getattr(lib, name)
             fn.argtypes = args
