@@ -35,6 +35,13 @@ def _ptr(t):
     return 0 if t is None else t.data_ptr()
 
 
+def _scratch(shape, device, what):
+    """The fp32 scratch of one dc_conv_igemm_bf16 launch that `conv` owns: what = "splitk" (the split-K slabs, splitk_ws: the bytes
+    dc_conv_igemm_ws_bytes states), "ln_scratch" (the (mean, rstd) of a finalize-first launch) or "gn_part" (the GroupNorm partials
+    out).  Any contents.  One function so that the tests can hand out guarded buffers."""
+    return torch.empty(shape, device=device, dtype=F32)
+
+
 def _chk(t, dtype, name):
     if not t.is_cuda:
         raise ValueError(f"{name}: expected a device tensor (the HIP path has no CPU fallback)")
@@ -319,18 +326,18 @@ def conv(x1, pc, *, x2=None, gn_ab=None, gn_silu=False, row_add=None, residual=N
             tile3 = k == 3 and stride == 1 and conv_route(d).kernel == "conv3x3_tile"
             splitk = _pick_splitk(m, pc.cout, kt, pc.cin // 64 if tile3 else None, rows_per_image=ho * wo)
         d.splitk = int(splitk)
-    ws = torch.empty((splitk, m, pc.cout), device=x1.device, dtype=F32) if splitk > 1 else None
+    ws = _scratch((splitk, m, pc.cout), x1.device, "splitk") if splitk > 1 else None
     d.splitk_ws = _ptr(ws)
     if ln_parts > 0 and conv_route(d).ln_first:
         # scratch for (mean, rstd) only where the dispatcher runs the finalize pass first (the row-panel kernel finalizes in its
         # prologue): the library's own routing decides, not a Python restatement of it
-        ln_scratch = torch.empty((m, 2), device=x1.device, dtype=F32)
+        ln_scratch = _scratch((m, 2), x1.device, "ln_scratch")
         d.ln_scratch = ln_scratch.data_ptr()
     part = None
     if gn_part and GN_EPILOGUE_STATS and not out_f32 and not pc.geglu and splitk == 1 and ln_stats is None:
         chunks = lib.load().dc_conv_gn_part_chunks(d)
         if chunks > 0:
-            part = torch.empty((chunks, n, pc.cout, 2), device=x1.device, dtype=F32)
+            part = _scratch((chunks, n, pc.cout, 2), x1.device, "gn_part")
             d.gn_part_out = part.data_ptr()
     meta = None
     if lib.TIMER is not None:

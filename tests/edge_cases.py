@@ -7,6 +7,10 @@ Plain module (imported by tests/test_edge_coverage.py on the CPU and tests/test_
   kernel never writes stays non-finite (L.check treats it as infinitely wrong); `bad()` lists every guard element that no longer
   holds the pattern, compared as integers.  A uint8 buffer holds the byte 0xA5 instead: a legitimate output value, so `unwritten()`
   means nothing for it and such an output is compared in full.  float64 (the metric outputs) holds a NaN compared as int64.
+* `run_on_fills`: one launcher on a guarded workspace of exactly its dc_*_ws_bytes, under three fills of the workspace (the NaN
+  pattern, zeros, what a launch on other inputs left): guards, nothing unwritten, finite, bitwise equal outputs.  The GPU test of
+  every launcher that takes a caller-owned workspace goes through it (tests/test_edge_coverage.py keeps the census).
+  `CONV_SCRATCH_CASES` / `conv_scratch_kinds`: the conv cases whose launch is handed a scratch by ops.conv (ops._scratch).
 * `conv_key` / `attention_key`: the kernel instance a launch runs, from the dispatcher's own queries (dc_conv_route and
   dc_conv_instance, dc_attention_route).
 * `f32_conv_key`: the same for the fp32 extractor conv (dc_conv3x3_f32_route).
@@ -84,6 +88,88 @@ def _signed(bits, dtype):
         return bits
     w = {torch.bfloat16: 16, torch.float32: 32, torch.float64: 64}[dtype]
     return bits - (1 << w) if bits >= 1 << (w - 1) else bits
+
+
+# ------------------------------------------------------------------------------------------ caller-owned workspaces
+WS_FILLS = ("nan", "zeros", "stale")
+_STORE = {torch.int32: torch.float32, torch.int64: torch.float64}       # integer outputs live in a guarded float buffer of their width
+
+
+def ws_bits(t):
+    """the bits of a tensor as integers (uint8 as it is): NaN payloads compare"""
+    t = t.contiguous()
+    return t if not t.dtype.is_floating_point else t.view({2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
+
+
+def guarded_output(shape, dtype, device):
+    """-> (Guarded, view of `dtype`): an output buffer holding the NaN pattern; int32 / int64 outputs are views of a guarded
+    float32 / float64 buffer (the pattern read as an integer is 2141562277 / 9221788429789668773, no count or index here)"""
+    g = Guarded(tuple(shape), _STORE.get(dtype, dtype), device)
+    return g, (g.view.view(dtype) if dtype in _STORE else g.view)
+
+
+def run_on_fills(launch, nbytes, outputs, what, operands=(), device="cuda", elem=torch.float32, finite=True, keep=False):
+    """Hold one launcher to the two promises its header makes about a caller-owned workspace: it is `nbytes` (the launcher's
+    dc_*_ws_bytes) long and may hold any contents.
+
+    launch(ws, outs, prime): ws = the workspace, a 1-d `elem` view of exactly nbytes (its address: ws.data_ptr()); outs = one fresh
+    tensor per (shape, dtype) of `outputs`, each inside its own Guarded holding the NaN pattern; prime = False for the launch under
+    test, True for a launch of the same shape on different input values (it only dirties the workspace; its outputs are held to the
+    same guards).  operands = the Guarded buffers the closure reads.  elem = float32 (its guard pattern is a NaN, which no product
+    with a zero weight hides; a uint8 workspace would hold 0xA5 bytes = -2.9e-16 as floats, finite and invisible) or float64 for
+    workspaces of double partials.
+
+    The launch under test runs three times, the workspace interior holding: 'nan' the pattern as allocated; 'zeros'; 'stale' what
+    a prime launch left.  After every launch (the prime one too): every guard of the workspace, the outputs and the operands is
+    intact, no output element holds the pattern (uint8 outputs excepted: 0xA5 is a value), and with finite=True every floating
+    output is finite.  The three sets of outputs are bitwise equal.
+
+    keep=True: the buffer is itself a result that a later launch reads (dc_lpips_alex_keep's maps).  Every element the 'nan' run
+    wrote must then hold the same bits after the other two runs, and a copy of the buffer after the 'nan' run (the pattern still
+    in what nobody wrote) is appended to the outputs returned.
+    -> (the outputs of the 'nan' run, the share of workspace elements still holding the pattern after it)"""
+    size = torch.empty((), dtype=elem).element_size()
+    assert elem in (torch.float32, torch.float64), elem
+    assert nbytes > 0, f"{what}: dc_*_ws_bytes = {nbytes}"
+    assert nbytes % size == 0, f"{what}: dc_*_ws_bytes = {nbytes} is no multiple of {size}"
+    ws = Guarded((nbytes // size,), elem, device)
+    on_gpu = ws.view.is_cuda
+    if on_gpu:                                   # the alignment the cmp, guide and loss entries demand (a host allocation has 64)
+        assert ws.view.data_ptr() % 256 == 0, f"{what}: the guarded workspace is not 256-byte aligned"
+
+    def one(tag, prime):
+        held = [guarded_output(shape, dtype, device) for shape, dtype in outputs]
+        launch(ws.view, [v for _, v in held], prime)
+        if on_gpu:
+            torch.cuda.synchronize()
+        ws.assert_intact(f"{what} [{tag}] workspace of {nbytes} bytes")
+        for k, g in enumerate(operands):
+            g.assert_intact(f"{what} [{tag}] operand {k}")
+        for k, (g, v) in enumerate(held):
+            g.assert_intact(f"{what} [{tag}] output {k}")
+            if g.dtype != torch.uint8:
+                assert g.unwritten() == 0, f"{what} [{tag}] output {k}: {g.unwritten()} of {v.numel()} elements never written"
+            if finite and v.dtype.is_floating_point:
+                bad = int((~torch.isfinite(v)).sum())
+                assert bad == 0, f"{what} [{tag}] output {k}: {bad} of {v.numel()} elements are not finite"
+        return [v for _, v in held] + ([ws.view.clone()] if keep and not prime else [])
+
+    got = {"nan": one("nan", False)}
+    share = ws.unwritten() / ws.view.numel()
+    ws.view.zero_()
+    got["zeros"] = one("zeros", False)
+    one("prime", True)
+    got["stale"] = one("stale", False)
+    written = ws_bits(got["nan"][-1]) != _signed(NAN_BITS[elem], elem) if keep else None
+    for tag in WS_FILLS[1:]:
+        for k, (a, b) in enumerate(zip(got["nan"], got[tag])):
+            diff = ws_bits(a) != ws_bits(b)
+            if keep and k == len(outputs):
+                diff &= written
+            diff = int(diff.sum())
+            assert diff == 0, (f"{what}: output {k} under the '{tag}' fill differs from the 'nan' fill in {diff} of {a.numel()} elements: "
+                               "the launch reads workspace memory it never wrote")
+    return got["nan"], share
 
 
 # ------------------------------------------------------------------------------------------ conv / linear instances
@@ -405,6 +491,18 @@ CONV_CASES = (
     + _tile(8, (1026, 8, 8, 128, 128), 4, narrow=True, gn_opts=(False,))  # two 8x8 images per tile, 128-column tiles
     + _tile(8, (514, 8, 8, 128, 320), 5, narrow=True, gn_opts=(False,))   # two 8x8 images per tile
 )
+
+
+def conv_scratch_kinds(c, gn_part_out):
+    """the scratches ops.conv allocates (ops._scratch) for a case, by its own rules: the split-K slabs when it splits (never with a
+    folded LayerNorm or row statistics out), (mean, rstd) when the route finalizes the LayerNorm first (key[4]), the GroupNorm
+    partials when the launch emits them (`gn_part_out`: dc_conv_gn_part_chunks > 0, known only with the library)"""
+    split = c.splitk > 1 and c.ln is None and not c.stats_out
+    return ["splitk"] * split + ["ln_scratch"] * bool(c.key[4]) + ["gn_part"] * bool(gn_part_out)
+
+
+# the cases whose launch is handed a scratch by ops.conv (a GroupNorm-partials request the launch cannot honour asks for none)
+CONV_SCRATCH_CASES = [i for i, c in enumerate(CONV_CASES) if conv_scratch_kinds(c, c.gn_part)]
 
 
 # ------------------------------------------------------------------------------------------ attention instances

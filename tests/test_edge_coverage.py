@@ -1,6 +1,8 @@
 """CPU: the edge-case tables of tests/edge_cases.py cover every kernel instance the dispatchers can reach, every case routes to the
 instance it declares, and the checks the GPU edge tests rely on (guarded buffers, the flat and peaked attention input families held
-to oracle/launch_ref.py) reject the faults they are there to catch."""
+to oracle/launch_ref.py) reject the faults they are there to catch.  Caller-owned workspaces: E.run_on_fills rejects an overrun, a
+read of an unwritten slot and an unwritten output; every dc_*_ws_bytes of the four signature tables has a guarding GPU module
+(WS_QUERY_TESTS) and grows with N no faster than N; ops.conv asks for the scratch the library states."""
 import functools
 import json
 import math
@@ -735,3 +737,311 @@ def test_removing_a_census_entry_names_the_launcher():
     broken = dict(LAUNCHER_TESTS, dc_psnr=("test_gpu_ops", "dc_psnr"), dc_fid_maps=("test_gpu_fid", "maps", "FrechetInceptionDistance.features"),
                   dc_fvd_features=("test_gpu_lpips", "endpoints", "FrechetVideoDistance.features"))
     assert [g.split(":")[0] for g in launcher_census(broken)] == ["dc_psnr", "dc_fid_maps", "dc_fvd_features"]
+
+
+# ------------------------------------------------------------------------------------------ caller-owned workspaces: the helper
+def _past(t, k):
+    """element k of the storage counted from the first element of the 1-d view t (k < 0 or >= t.numel(): outside it)"""
+    return torch.as_strided(t, (1,), (1,), t.storage_offset() + k)
+
+
+def _fake(fault=None):
+    """a launch on CPU tensors: the workspace's first 8 elements hold a 'map' of the input, the output is 2 x map[:4] (+ one
+    element of the workspace nobody wrote, with fault = 'reads')"""
+    def launch(ws, outs, prime):
+        ws[:8] = 5.0 if prime else 1.0
+        outs[0][:] = 2 * ws[:4]
+        if fault == "past":
+            _past(ws, ws.numel())[0] = 0.0
+        elif fault == "before":
+            _past(ws, -1)[0] = 0.0
+        elif fault == "reads":
+            outs[0][3] = outs[0][3] + 0.0 * ws[9]          # a padded tap: "a finite value times 0", true only on fresh memory
+        elif fault == "reads_plain":
+            outs[0][3] = ws[9]
+        elif fault == "unwritten":
+            outs[0][2] = torch.tensor(E.NAN_BITS[torch.float32], dtype=torch.int32).view(torch.float32)
+        elif fault == "out_past":
+            _past(outs[0], 4)[0] = 0.0
+    return launch
+
+
+def test_run_on_fills_passes_an_honest_launch_and_reports_the_unwritten_share():
+    (out,), share = E.run_on_fills(_fake(), 64, [((4,), torch.float32)], "honest", device="cpu")
+    assert out.tolist() == [2.0] * 4 and share == 0.5
+    (out, kept), share = E.run_on_fills(_fake(), 64, [((4,), torch.float32)], "honest", device="cpu", keep=True)
+    assert kept[:8].tolist() == [1.0] * 8 and bool(torch.isnan(kept[8:]).all())
+    (cnt,), _ = E.run_on_fills(lambda ws, outs, prime: outs[0].fill_(3), 8, [((5,), torch.int32)], "integers", device="cpu", elem=torch.float64)
+    assert cnt.dtype == torch.int32 and cnt.tolist() == [3] * 5
+
+
+@pytest.mark.parametrize("fault,finite,match", [
+    ("past", True, r"\[nan\] workspace of 64 bytes: guard elements overwritten.*'after', 16"),
+    ("before", True, r"\[nan\] workspace of 64 bytes: guard elements overwritten.*'before', -1"),
+    ("out_past", True, r"\[nan\] output 0: guard elements overwritten.*'after', 4"),
+    ("reads", True, r"\[nan\] output 0: 1 of 4 elements are not finite"),
+    ("reads", False, r"output 0 under the 'zeros' fill differs from the 'nan' fill in 1 of 4 elements"),
+    ("reads_plain", False, r"\[nan\] output 0: 1 of 4 elements never written"),
+    ("unwritten", True, r"\[nan\] output 0: 1 of 4 elements never written"),
+])
+def test_run_on_fills_rejects_what_it_exists_to_catch(fault, finite, match):
+    with pytest.raises(AssertionError, match=match):
+        E.run_on_fills(_fake(fault), 64, [((4,), torch.float32)], "fake", device="cpu", finite=finite)
+
+
+def test_run_on_fills_rejects_a_stale_read_that_zeros_and_nan_agree_on():
+    """an output that takes the sign of a workspace element nobody wrote this launch: NaN and 0 both give 0, the 5.0 a launch on
+    other inputs left there does not"""
+    def launch(ws, outs, prime):
+        if prime:
+            ws[:] = 5.0
+        ws[:8] = 1.0
+        outs[0][:] = 2 * ws[:4]
+        outs[0][1] = float(ws[12] > 0)
+
+    with pytest.raises(AssertionError, match="under the 'stale' fill differs"):
+        E.run_on_fills(launch, 64, [((4,), torch.float32)], "fake", device="cpu")
+
+
+def test_run_on_fills_rejects_a_kept_buffer_that_depends_on_the_fill_and_refuses_odd_sizes():
+    def launch(ws, outs, prime):
+        if prime:
+            ws[:] = 5.0
+        ws[:8] = 1.0
+        ws[4] = ws[12].nan_to_num(0.0) + 1.0                # a kept element that takes what the buffer held
+        outs[0][:] = 2.0
+
+    with pytest.raises(AssertionError, match="output 1 under the 'stale' fill differs from the 'nan' fill in 1 of 16"):
+        E.run_on_fills(launch, 64, [((4,), torch.float32)], "fake", device="cpu", keep=True)
+    for nbytes in (0, -1, 62):
+        with pytest.raises(AssertionError, match="dc_\\*_ws_bytes"):
+            E.run_on_fills(_fake(), nbytes, [((4,), torch.float32)], "fake", device="cpu")
+    with pytest.raises(AssertionError, match="no multiple of 8"):
+        E.run_on_fills(_fake(), 60, [((4,), torch.float32)], "fake", device="cpu", elem=torch.float64)
+
+
+# ------------------------------------------------------------------------------------------ ops.conv's scratch and the library's figure
+def _conv_on_the_host(monkeypatch, c):
+    """ops.conv of a case with host tensors of the right shapes and the launch replaced by a recorder ->
+    (the descriptor it built, [(what, bytes)] it asked ops._scratch for)"""
+    import types
+    from diffcodec_amd import ops
+    asked, descs = [], []
+    monkeypatch.setattr(ops, "_chk", lambda *a: None)
+    monkeypatch.setattr(ops, "_stream", lambda: 0)
+
+    def scratch(shape, device, what):
+        asked.append((what, 4 * math.prod(shape)))
+        return torch.empty(shape, dtype=torch.float32)
+
+    def call(name, d, *rest, meta=None):
+        assert name == "dc_conv_igemm_bf16"
+        descs.append(type(d).from_buffer_copy(d))
+
+    monkeypatch.setattr(ops, "_scratch", scratch)
+    monkeypatch.setattr(ops.lib, "call", call)
+    bf, f32 = torch.bfloat16, torch.float32
+    cin = c.c1 + c.c2
+    pc = types.SimpleNamespace(cout=c.cout, cin=cin, ksize=c.k, geglu=c.geglu, kind="igemm", ln_eps=1e-5 if c.ln is not None else None,
+                               w=torch.empty(c.cout, c.k * c.k, cin, dtype=bf), bias=torch.empty(c.cout), colsum=torch.empty(c.cout))
+    kw = dict(stride=c.stride, pad=c.pad, upsample=c.up, out_scale=c.out_scale, out_f32=c.out_f32, splitk=c.splitk, act=c.act,
+              gn_part=c.gn_part)
+    if c.c2:
+        kw["x2"] = torch.empty(c.n, c.h, c.w, c.c2, dtype=bf)
+    if c.gn:
+        kw.update(gn_ab=torch.empty(c.n, cin, 2), gn_silu=c.gn_silu)
+    if c.row_add:
+        kw["row_add"] = torch.empty(c.n, c.cout)
+    if c.residual:
+        kw["residual"] = torch.empty(c.n, c.ho, c.wo, c.cout, dtype=bf)
+    if c.ln == "pairs":
+        kw["ln_stats"] = torch.empty(c.m, 2)
+    elif c.ln is not None:
+        kw["ln_partials"] = (torch.empty(c.m, c.ln, 2), 1e-5)
+    if c.stats_out:
+        kw["stats_out"] = torch.empty(c.m, ops.row_stats_parts(c.cout), 2)
+    ops.conv(torch.empty(c.n, c.h, c.w, c.c1, dtype=bf), pc, **kw)
+    monkeypatch.undo()
+    assert len(descs) == 1
+    return descs[0], asked
+
+
+@pytest.mark.parametrize("i", E.CONV_SCRATCH_CASES, ids=[E.CONV_CASES[i].label() for i in E.CONV_SCRATCH_CASES])
+def test_conv_asks_for_the_scratch_the_library_states(lib, monkeypatch, i):
+    """ops.conv sizes the split-K workspace itself (splitk x M x Cout floats): pinned here to dc_conv_igemm_ws_bytes of the
+    descriptor it built, for every case that is handed a scratch; the (mean, rstd) scratch is M pairs and the GroupNorm partials
+    dc_conv_gn_part_chunks x N x Cout pairs, asked for exactly when the route finalizes first / the launch emits them"""
+    from diffcodec_amd import ops
+    c = E.CONV_CASES[i]
+    d, asked = _conv_on_the_host(monkeypatch, c)
+    assert E.conv_key(d) == c.key
+    L_ = lib.load()
+    r = ops.conv_route(d)
+    want = []
+    if d.splitk > 1:
+        assert d.splitk_ws and r.splitk > 1 and L_.dc_conv_igemm_ws_bytes(d) > 0
+        want.append(("splitk", L_.dc_conv_igemm_ws_bytes(d)))
+    else:
+        assert not d.splitk_ws and L_.dc_conv_igemm_ws_bytes(d) == 0
+    if r.ln_first:
+        assert d.ln_scratch
+        want.append(("ln_scratch", c.m * 2 * 4))
+    else:
+        assert not d.ln_scratch
+    if d.gn_part_out:
+        want.append(("gn_part", L_.dc_conv_gn_part_chunks(d) * c.n * c.cout * 2 * 4))
+    assert asked == want and want, (c.label(), asked, want)
+    assert [w for w, _ in want] == E.conv_scratch_kinds(c, bool(d.gn_part_out))
+
+
+def test_conv_scratch_cases_are_every_case_that_is_handed_one(lib):
+    from diffcodec_amd import ops
+    for i, c in enumerate(E.CONV_CASES):
+        d = E.case_desc(c)
+        r = ops.conv_route(d)
+        handed = r.splitk > 1 or r.ln_first or bool(d.gn_part_out)
+        assert handed == (i in E.CONV_SCRATCH_CASES), c.label()
+    kinds = {k for i in E.CONV_SCRATCH_CASES for k in E.conv_scratch_kinds(E.CONV_CASES[i], bool(E.case_desc(E.CONV_CASES[i]).gn_part_out))}
+    assert kinds == {"splitk", "ln_scratch", "gn_part"}
+
+
+# ------------------------------------------------------------------------------------------ the census of workspace queries
+_HELPER = "run_on_fills"
+_OWN_GUARDS = "Guarded"            # the module's own guard code around the workspace, written before the shared helper
+# dc_*_ws_bytes -> [(test module, the token it must name: the shared helper or, for the exceptions below, E.Guarded, the launchers
+# that consume the workspace and that the module must launch)].  A consumer is a literal lib.call of the C name, or, for
+# dc_conv_igemm_bf16, the wrapper that builds its descriptor.
+WS_QUERY_TESTS = {
+    "dc_ssim_ws_bytes": [("test_gpu_metrics", _HELPER, ("dc_ssim", "dc_ms_ssim"))],
+    "dc_psnr_ws_bytes": [("test_gpu_metrics", _HELPER, ("dc_psnr",))],
+    "dc_lpips_ws_bytes": [("test_gpu_lpips", _HELPER, ("dc_lpips_alex",))],
+    "dc_lpips_features_ws_bytes": [("test_gpu_lpips", _HELPER, ("dc_lpips_alex_features",))],
+    "dc_fid_ws_bytes": [("test_gpu_fid", _HELPER, ("dc_fid_features",))],
+    "dc_fvd_ws_bytes": [("test_gpu_fvd", _HELPER, ("dc_fvd_features", "dc_fvd_endpoints"))],
+    "dc_cmp_ws_bytes": [("test_gpu_cmp", _HELPER, ("dc_cmp_forward", "dc_cmp_flow", "dc_cmp_endpoints"))],
+    "dc_lpips_keep_ws_bytes": [("test_gpu_losses", _HELPER, ("dc_lpips_alex_keep", "dc_lpips_alex_backward"))],
+    "dc_lpips_train_ws_bytes": [("test_gpu_losses", _HELPER, ("dc_lpips_alex_backward",))],
+    "dc_guide_ws_bytes": [("test_gpu_guide_points", _HELPER, ("dc_guide_edge", "dc_guide_edt", "dc_guide_nms", "dc_guide_select",
+                                                              "dc_guide_watershed"))],
+    # through the seam of ops.conv (ops._scratch), handed guarded buffers for every case of E.CONV_SCRATCH_CASES
+    "dc_conv_igemm_ws_bytes": [("test_gpu_edges", "CONV_SCRATCH_CASES", ("conv",))],
+    # the exceptions: guarded workspaces of the declared size from before the helper
+    "dc_splat_ws_bytes": [("test_gpu_edges", _OWN_GUARDS, ("dc_splat_soft_f32", "dc_splat_sum_f32")),
+                          ("test_gpu_softsplat", _OWN_GUARDS, ("dc_splat_norm_f32", "dc_splat_ingrad_f32", "dc_splat_flowgrad_f32"))],
+    "dc_resample_ws_bytes": [("test_gpu_resample", "guard", ("dc_resample_u8",))],      # guard bytes of its own around obuf and wbuf
+    "dc_sobel_edge_ws_bytes": [("test_gpu_losses", _OWN_GUARDS, ("dc_sobel_edge_loss",))],
+}
+WS_EXCEPTIONS = ("dc_splat_ws_bytes", "dc_resample_ws_bytes", "dc_sobel_edge_ws_bytes", "dc_conv_igemm_ws_bytes")
+
+
+def _all_signatures():
+    from diffcodec_amd import lib as l
+    out = {}
+    for table in (l.SIGNATURES, l.FLOW_SIGNATURES, l.LOSS_SIGNATURES, l.GUIDE_SIGNATURES):
+        out.update(table)
+    return out
+
+
+def ws_census(table, signatures=None):
+    """-> the complaints, one per dc_*_ws_bytes of the four signature tables whose entry is missing or does not hold"""
+    sigs = _all_signatures() if signatures is None else signatures
+    out = []
+    for name in sigs:
+        if not name.endswith("_ws_bytes"):
+            continue
+        if name not in table:
+            out.append(f"{name}: no entry in WS_QUERY_TESTS")
+            continue
+        for module, token, consumers in table[name]:
+            path = os.path.join(ROOT, "tests", module + ".py")
+            if not os.path.exists(path):
+                out.append(f"{name}: tests/{module}.py does not exist")
+                break
+            used = _names_used(path)
+            if name not in used:
+                out.append(f"{name}: tests/{module}.py never names the query")
+            elif token not in used:
+                out.append(f"{name}: tests/{module}.py never names {token}")
+            elif token != _HELPER and name not in WS_EXCEPTIONS:
+                out.append(f"{name}: guarded by {token}, not by the shared helper, and not a listed exception")
+            else:
+                missing = [c for c in consumers if c not in _lib_calls_cached(path) and c not in used]
+                if not consumers or any(c not in sigs and c != "conv" for c in consumers):
+                    out.append(f"{name}: tests/{module}.py is given no consumer of the four signature tables")
+                elif missing:
+                    out.append(f"{name}: tests/{module}.py never launches {', '.join(missing)}")
+                else:
+                    continue
+            break
+    out += [f"{name}: an entry for something that is no dc_*_ws_bytes of the four signature tables" for name in table
+            if name not in sigs or not name.endswith("_ws_bytes")]
+    return out
+
+
+def test_every_workspace_query_has_a_guarding_gpu_test():
+    assert ws_census(WS_QUERY_TESTS) == []
+
+
+def test_removing_a_workspace_census_entry_names_the_query():
+    sigs = _all_signatures()
+    assert sorted(n for n in sigs if n.endswith("_ws_bytes")) == sorted(WS_QUERY_TESTS)
+    for name in WS_QUERY_TESTS:
+        got = ws_census({k: v for k, v in WS_QUERY_TESTS.items() if k != name})
+        assert len(got) == 1 and got[0].startswith(name + ":"), (name, got)
+    got = ws_census(WS_QUERY_TESTS, dict(sigs, dc_new_ws_bytes=[]))                 # a new export without an entry
+    assert got == ["dc_new_ws_bytes: no entry in WS_QUERY_TESTS"]
+    broken = dict(WS_QUERY_TESTS, dc_fid_ws_bytes=[("test_gpu_fvd", _HELPER, ("dc_fid_features",))],
+                  dc_fvd_ws_bytes=[("test_gpu_fvd", _HELPER, ("dc_fvd_features", "dc_fvd_preprocess_none"))],
+                  dc_cmp_ws_bytes=[("test_gpu_cmp", _OWN_GUARDS, ("dc_cmp_flow",))],
+                  dc_lpips_ws_bytes=[("test_gpu_lpips", _HELPER, ("dc_lpips_alex", "dc_lpips_alex_backward"))])
+    assert [g.split(":")[0] for g in ws_census(broken)] == ["dc_lpips_ws_bytes", "dc_fid_ws_bytes", "dc_fvd_ws_bytes", "dc_cmp_ws_bytes"]
+
+
+# ------------------------------------------------------------------------------------------ the size queries in N
+# query -> [arguments with N left out (None)]: the shapes of the GPU workspace tests
+WS_IN_N = {
+    "dc_lpips_ws_bytes": [(None, 31, 31), (None, 67, 95)],
+    "dc_lpips_features_ws_bytes": [(None, 31, 31), (None, 67, 95)],
+    "dc_lpips_keep_ws_bytes": [(None, 31, 31), (None, 67, 95)],
+    "dc_lpips_train_ws_bytes": [(None, 31, 31, 3)] + [(None, 67, 95, s) for s in (1, 2, 3)],
+    "dc_fid_ws_bytes": [(None, 1, 1), (None, 64, 48)],
+    "dc_fvd_ws_bytes": [(None, 9, 64, 48), (None, 11, 32, 32)],
+    "dc_cmp_ws_bytes": [(a, None, h, w) for a in (0, 1) for h, w in ((64, 88), (72, 64))],
+    "dc_guide_ws_bytes": [(None, 37, 53), (None, 24, 801)],
+    "dc_ssim_ws_bytes": [(None, 3, 161, 161, 11, 5), (None, 2, 33, 35, 3, 5)],
+    "dc_psnr_ws_bytes": [(None,)],
+    "dc_splat_ws_bytes": [(None, 7, 9), (None, 24, 40)],
+    "dc_resample_ws_bytes": [(None, 37, 53, 3)],
+    "dc_sobel_edge_ws_bytes": [(None, 3, 17, 70)],
+}
+
+
+@pytest.mark.parametrize("name", sorted(WS_IN_N))
+def test_workspace_sizes_grow_with_n_and_never_faster_than_n(lib, name):
+    """strictly increasing in N, and at most N x the size for one item: what _PackedNet._step relies on when it chunks a batch by
+    the size for one item"""
+    q = getattr(lib.load(), name)
+    for args in WS_IN_N[name]:
+        size = [q(*[n if a is None else a for a in args]) for n in range(1, 18)]
+        assert size[0] > 0, (name, args, size[0])
+        for n in range(2, 18):
+            assert size[n - 2] < size[n - 1] <= n * size[0], (name, args, n, size[n - 2], size[n - 1], size[0])
+
+
+# dc_guide_ws_bytes and dc_ssim_ws_bytes round the total up to a granule (256 / 512 bytes), so below one granule per item they
+# cannot grow with every N: there the size never shrinks and stays within N x the size for one
+WS_BELOW_A_GRANULE = {"dc_guide_ws_bytes": [(None, 1, 1)], "dc_ssim_ws_bytes": [(None, 1, 33, 35, 3, 1), (None, 1, 1, 1, 1, 8)]}
+
+
+@pytest.mark.parametrize("name", sorted(WS_BELOW_A_GRANULE))
+def test_rounded_workspace_sizes_never_shrink_with_n(lib, name):
+    q = getattr(lib.load(), name)
+    for args in WS_BELOW_A_GRANULE[name]:
+        size = [q(*[n if a is None else a for a in args]) for n in range(1, 600)]
+        assert size[0] > 0 and size[-1] > size[0], (name, args, size[0], size[-1])
+        for n in range(2, 600):
+            assert size[n - 2] <= size[n - 1] <= n * size[0], (name, args, n, size[n - 2], size[n - 1], size[0])
+
+
+def test_every_n_taking_workspace_query_is_held_to_it():
+    assert sorted(WS_IN_N) == sorted(n for n in _all_signatures() if n.endswith("_ws_bytes") and n != "dc_conv_igemm_ws_bytes")

@@ -443,6 +443,77 @@ def test_flow_is_graph_capturable(arch, size):
     assert torch.equal(out, fy) and not torch.equal(fx, fy)
 
 
+# ------------------------------------------------------------------------------------------- the caller-owned workspace
+# (N, H, W, image form): an odd batch at the size whose 1/8 map (8 x 11) is ragged, as normalised fp32 NCHW; H / 8 = 9 odd (the
+# decoder pools 9 -> 4 -> 2 leave a remainder), as a uint8 NHWC window cropped from a larger frame
+WS_CASES = [(3, 64, 88, "f32"), (2, 72, 64, "u8_view")]
+
+
+def _ws_inputs(N, H, W, form, seed):
+    """(what keeps the storage alive, image operand on the device, its element strides (n, c, h, w), sparse on the device)"""
+    u8, sparse = R.inputs(N, H, W, seed)
+    if form == "f32":
+        img = R.normalise(u8, torch.float32).contiguous().to(DEV)
+        return img, img, img.stride(), sparse.to(DEV)
+    base = torch.full((N, H + 4, W + 5, 3), 77, dtype=torch.uint8)
+    base[:, 2:2 + H, 3:3 + W] = u8
+    bdev = base.to(DEV)
+    img = bdev[:, 2:2 + H, 3:3 + W, :]
+    return bdev, img, (img.stride(0), img.stride(3), img.stride(1), img.stride(2)), sparse.to(DEV)
+
+
+@pytest.mark.parametrize("N,H,W,form", WS_CASES, ids=[f"n{c[0]}_{c[1]}x{c[2]}_{c[3]}" for c in WS_CASES])
+@pytest.mark.parametrize("arch", ["skip", "plain"])
+def test_chain_on_a_guarded_workspace_of_any_contents(record, arch, N, H, W, form):
+    """dc_cmp_forward, dc_cmp_flow and dc_cmp_endpoints on a guarded workspace of exactly dc_cmp_ws_bytes under the NaN, zero and
+    stale fills, every map pointer a guarded output: the bits HipCMP's __call__ / flow / endpoints return (the wrapper keeps one
+    torch.empty workspace from call to call)"""
+    import edge_cases as E
+    from diffcodec_amd import lib
+    from diffcodec_amd.flow_propagation import stage_sizes
+    model = model_of(arch)
+    sets = [_ws_inputs(N, H, W, form, seed) for seed in (900 + H + W + N, 977)]
+    s2, s4, s8 = stage_sizes(model.config, H, W)
+    top = s2 if model.skip else s8
+    f32 = torch.float32
+    maps = [(16, s8), (256, s8), (64, s2), (256, s4)] + ([(256, s8), (128, s4), (64, s2)] if model.skip else [(384, s8)])
+    shape = lambda c, hw: ((N, c, hw[0], hw[1]), f32)
+    names = R.ENDPOINTS[arch]
+    nbytes = lib.load().dc_cmp_ws_bytes(model.arch, N, H, W)
+
+    def head(ws, prime):
+        _, img, strides, sparse = sets[int(prime)]
+        return (model.arch, img.data_ptr(), int(form != "f32"), _i64(strides), sparse.data_ptr(), N, H, W, model.nbins, model.fmax,
+                model.weights.data_ptr(), ws.data_ptr())
+
+    def forward(ws, outs, prime):
+        lib.call("dc_cmp_forward", *head(ws, prime), outs[0].data_ptr(), outs[1].data_ptr(), _stream())
+
+    def flow(ws, outs, prime):
+        lib.call("dc_cmp_flow", *head(ws, prime), outs[0].data_ptr(), _stream())
+
+    def endpoints(ws, outs, prime):
+        ptrs = (ctypes.c_void_p * len(maps))(*[o.data_ptr() for o in outs[:len(maps)]])
+        lib.call("dc_cmp_endpoints", *head(ws, prime), ptrs, *[o.data_ptr() for o in outs[len(maps):]], _stream())
+
+    tag = f"{arch} {N}x{H}x{W} {form}"
+    _, img, _, sparse = sets[0]
+    want = model.endpoints(img, sparse)
+    assert list(want) == list(names)
+    (lg, fl), share = E.run_on_fills(forward, nbytes, [shape(2 * model.nbins, top), shape(2, top)], f"dc_cmp_forward {tag}", device=DEV)
+    record(f"ws_unwritten_share[dc_cmp_forward {tag}]", share)
+    assert torch.equal(E.ws_bits(lg), E.ws_bits(model(img, sparse))) and torch.equal(E.ws_bits(fl), E.ws_bits(want["flow"]))
+    (up,), share = E.run_on_fills(flow, nbytes, [shape(2, (H, W))], f"dc_cmp_flow {tag}", device=DEV)
+    record(f"ws_unwritten_share[dc_cmp_flow {tag}]", share)
+    assert torch.equal(E.ws_bits(up), E.ws_bits(model.flow(img, sparse)))
+    outputs = [shape(c, hw) for c, hw in maps] + [shape(2 * model.nbins, top), shape(2, top), shape(2, (H, W))]
+    outs, share = E.run_on_fills(endpoints, nbytes, outputs, f"dc_cmp_endpoints {tag}", device=DEV)
+    record(f"ws_unwritten_share[dc_cmp_endpoints {tag}]", share)
+    assert len(outs) == len(names)
+    for name, o in zip(names, outs):
+        assert torch.equal(E.ws_bits(o), E.ws_bits(want[name])), (tag, name)
+
+
 def test_sizes_are_refused_on_the_device_too():
     model = model_of("skip")
     for h in (68, 56):

@@ -64,11 +64,8 @@ def _capture(lib):
     return seen, real, call
 
 
-@pytest.mark.parametrize("i", range(len(E.CONV_CASES)), ids=[c.label() for c in E.CONV_CASES])
-def test_conv_edge(ops, record, i):
-    from diffcodec_amd import lib
-    c = E.CONV_CASES[i]
-    assert E.conv_key(E.case_desc(c)) == c.key, c.label()
+def _conv_operands(ops, c, i):
+    """(packed weights, {name: guarded operand}, guarded x1, keyword arguments of ops.conv) of case i of E.CONV_CASES (seed 1000 + i)"""
     gen = torch.Generator().manual_seed(1000 + i)
     cin = c.c1 + c.c2
     ho, wo, m = c.ho, c.wo, c.m
@@ -107,6 +104,17 @@ def test_conv_edge(ops, record, i):
         bounds = [(p * cin) // parts for p in range(parts + 1)]
         pr = torch.stack([torch.stack([xr[:, lo:hi].sum(1), (xr[:, lo:hi] ** 2).sum(1)], 1) for lo, hi in zip(bounds, bounds[1:])], 1)
         kw["ln_partials"] = (guards.setdefault("ln_partials", _g((m, parts, 2), F32, pr.float())).view, 1e-5)
+    return pc, guards, x1, kw
+
+
+@pytest.mark.parametrize("i", range(len(E.CONV_CASES)), ids=[c.label() for c in E.CONV_CASES])
+def test_conv_edge(ops, record, i):
+    from diffcodec_amd import lib
+    c = E.CONV_CASES[i]
+    assert E.conv_key(E.case_desc(c)) == c.key, c.label()
+    ho, wo, m = c.ho, c.wo, c.m
+    cout_eff = c.cout // 2 if c.geglu else c.cout
+    pc, guards, x1, kw = _conv_operands(ops, c, i)
     outs = []
     seen, real, call = _capture(lib)
     for rep in range(2):
@@ -144,6 +152,56 @@ def test_conv_edge(ops, record, i):
     if gp is not None:
         tr, ts = L.gn_part_totals_ref(og.view)
         _note(record, c.key + ("gn_part",), L.check(gp.to(torch.float64).sum(0), tr, ts, F32), c.label())
+
+
+@pytest.mark.parametrize("i", E.CONV_SCRATCH_CASES, ids=[E.CONV_CASES[i].label() for i in E.CONV_SCRATCH_CASES])
+def test_conv_scratch_of_any_contents(ops, monkeypatch, i):
+    """every split-K, finalize-first and GroupNorm-partials case again with the scratch ops.conv allocates (ops._scratch) handed out
+    as guarded buffers, holding the NaN pattern and then zeros: guards intact, the output (and the partials) finite, fully written
+    and bit for bit those of the unpatched launch"""
+    from diffcodec_amd import lib
+    c = E.CONV_CASES[i]
+    cout_eff = c.cout // 2 if c.geglu else c.cout
+    pc, guards, x1, kw = _conv_operands(ops, c, i)
+    handed = []
+    fill = [None]
+    seen, real, call = _capture(lib)
+    monkeypatch.setattr(lib, "call", call)
+
+    def scratch(shape, device, what):
+        g = E.Guarded(tuple(shape), F32, DEV)
+        if fill[0] == "zeros":
+            g.view.zero_()
+        handed.append((what, g))
+        return g.view
+
+    runs = {}
+    for tag in ("plain", "nan", "zeros"):
+        fill[0] = tag
+        if tag != "plain":
+            monkeypatch.setattr(ops, "_scratch", scratch)
+        del handed[:]
+        og = _g((c.n, c.ho, c.wo, cout_eff), F32 if c.out_f32 else BF)
+        sog = _g((c.m, ops.row_stats_parts(c.cout), 2), F32) if c.stats_out else None
+        y = ops.conv(x1.view, pc, out=og.view, stats_out=None if sog is None else sog.view, **kw)
+        torch.cuda.synchronize()
+        what = f"{c.label()} [{tag}]"
+        for name, g in list(guards.items()) + [("out", og)] + ([("stats_out", sog)] if sog is not None else []) + handed:
+            g.assert_intact(f"{what} {name}")
+        assert og.unwritten() == 0 and bool(torch.isfinite(og.view).all()), what
+        gp = getattr(y, "gn_part", None)
+        if tag != "plain":
+            assert sorted(w for w, _ in handed) == sorted(E.conv_scratch_kinds(c, gp is not None)), (what, [w for w, _ in handed])
+            slabs = sum(g.view.numel() * 4 for w, g in handed if w == "splitk")          # what ops.conv sized, against the library's figure
+            assert slabs == lib.load().dc_conv_igemm_ws_bytes(seen[-1]), (what, slabs)
+            for w, g in handed:
+                if w == "gn_part":
+                    assert g.unwritten() == 0 and bool(torch.isfinite(g.view).all()), what
+        runs[tag] = [og.view] + ([sog.view] if sog is not None else []) + ([gp] if gp is not None else [])
+    for tag in ("nan", "zeros"):
+        assert len(runs[tag]) == len(runs["plain"]), (c.label(), tag)
+        for k, (a, b) in enumerate(zip(runs["plain"], runs[tag])):
+            assert _same_bits(a, b), f"{c.label()}: result {k} with the scratch holding '{tag}' differs from the plain launch"
 
 
 @pytest.mark.parametrize("i", range(len(E.SMALL_CASES)), ids=[c.label() for c in E.SMALL_CASES])

@@ -369,3 +369,36 @@ def test_world2_gloo_gathers_feature_rows_on_rank0(small, models, tmp_path):
     assert res[0][2] == ref["scores"] and all(sorted(s) == ["ms_ssim", "psnr"] for s in ref["scores"].values())
     assert res[0][3] == ref["fid"] and ref["fid"] > 1e-3                  # the same bits
     assert res[1][3] is None and res[1][4] == [2] and res[0][4] == [1, 2, 3]
+
+
+# ------------------------------------------------------------------------------------------- the caller-owned workspace
+# (N, H, W): a one-pixel image (every bilinear tap clamps) and an odd batch; the maps are 299 -> 149 -> 147 -> 73 whatever the input
+WS_CASES = [(1, 1, 1), (3, 64, 48)]
+
+
+@pytest.mark.parametrize("n,h,w", WS_CASES, ids=[f"n{c[0]}_{c[1]}x{c[2]}" for c in WS_CASES])
+def test_features_on_a_guarded_workspace_of_any_contents(models, record, n, h, w):
+    """dc_fid_features on a guarded workspace of exactly dc_fid_ws_bytes under the NaN, zero and stale fills: the rows are the
+    bits FrechetInceptionDistance.features returns"""
+    import ctypes
+    import edge_cases as E
+    from diffcodec_amd import lib, metrics
+    model = models["u8"]
+    wts = model._weights(torch.device(DEV))
+    sets = []
+    for seed in (h * 7 + w + n, 977):
+        u = torch.randint(0, 256, (n, h, w, 3), generator=torch.Generator().manual_seed(seed), dtype=torch.uint8)
+        g = E.Guarded((n, h, w, 3), torch.uint8, DEV)
+        sets.append((g, g.fill(u.to(DEV))))
+    strides = (ctypes.c_longlong * 4)(h * w * 3, 1, w * 3, 3)
+    st = torch.cuda.current_stream().cuda_stream
+
+    def launch(ws, outs, prime):
+        lib.call("dc_fid_features", sets[int(prime)][1].data_ptr(), 1, strides, n, h, w, wts.data_ptr(), ws.data_ptr(),
+                 outs[0].data_ptr(), st)
+
+    what = f"dc_fid_features {n}x{h}x{w}"
+    (out,), share = E.run_on_fills(launch, lib.load().dc_fid_ws_bytes(n, h, w), [((n, metrics.FID_FEATURES), torch.float32)], what,
+                                   operands=[s[0] for s in sets], device=DEV)
+    record(f"ws_unwritten_share[{what}]", share)
+    assert torch.equal(E.ws_bits(out), E.ws_bits(model.features(sets[0][1]))), what

@@ -309,6 +309,52 @@ def test_features_are_graph_capturable(model):
     assert torch.equal(out, fy) and not torch.equal(fx, fy)
 
 
+# ------------------------------------------------------------------------------------------- the caller-owned workspace
+# (N, T, H, W): T = 9, the shortest video (T1 = 5, T4 = 3, T5 = 2), two of them; T = 11 makes T1 = 6 even and T4 = 3 odd
+WS_CASES = [(2, 9, 64, 48), (1, 11, 32, 32)]
+
+
+@pytest.mark.parametrize("entry", ["dc_fvd_features", "dc_fvd_endpoints"])
+@pytest.mark.parametrize("n,t,h,w", WS_CASES, ids=[f"n{c[0]}_t{c[1]}_{c[2]}x{c[3]}" for c in WS_CASES])
+def test_on_a_guarded_workspace_of_any_contents(model, record, n, t, h, w, entry):
+    """dc_fvd_features / dc_fvd_endpoints on a guarded workspace of exactly dc_fvd_ws_bytes under the NaN, zero and stale fills
+    (the sixteen maps guarded outputs too): the bits FrechetVideoDistance.features / .endpoints return"""
+    import ctypes
+    import edge_cases as E
+    from diffcodec_amd import lib, metrics
+    wts = model._weights(torch.device(DEV))
+    sets = []
+    for seed in (t * 7 + h + n, 977):
+        u = torch.randint(0, 256, (n, t, h, w, 3), generator=torch.Generator().manual_seed(seed), dtype=torch.uint8)
+        g = E.Guarded((n, t, h, w, 3), torch.uint8, DEV)
+        sets.append((g, g.fill(u.to(DEV))))
+    strides = (ctypes.c_longlong * 5)(t * h * w * 3, h * w * 3, 1, w * 3, 3)            # (n, t, c, h, w)
+    rh, rw = metrics.fvd_resized_size(h, w)
+    st = torch.cuda.current_stream().cuda_stream
+    feat = ((n, metrics.FVD_FEATURES), torch.float32)
+    if entry == "dc_fvd_features":
+        outputs = [feat]
+
+        def launch(ws, outs, prime):
+            lib.call("dc_fvd_features", sets[int(prime)][1].data_ptr(), 1, 1, strides, n, t, h, w, rh, rw, wts.data_ptr(), ws.data_ptr(),
+                     outs[0].data_ptr(), st)
+    else:
+        outputs = [((n,) + s, torch.float32) for s in metrics.fvd_endpoint_shapes(t)] + [feat]
+
+        def launch(ws, outs, prime):
+            maps = (ctypes.c_void_p * 16)(*[o.data_ptr() for o in outs[:16]])
+            lib.call("dc_fvd_endpoints", sets[int(prime)][1].data_ptr(), 1, 1, strides, n, t, h, w, rh, rw, wts.data_ptr(), ws.data_ptr(),
+                     maps, outs[16].data_ptr(), st)
+
+    what = f"{entry} {n}x{t}x{h}x{w}"
+    outs, share = E.run_on_fills(launch, lib.load().dc_fvd_ws_bytes(n, t, h, w), outputs, what, operands=[s[0] for s in sets], device=DEV)
+    record(f"ws_unwritten_share[{what}]", share)
+    assert torch.equal(E.ws_bits(outs[-1]), E.ws_bits(model.features(sets[0][1]))), what
+    if entry == "dc_fvd_endpoints":
+        for k, (o, e) in enumerate(zip(outs[:16], model.endpoints(sets[0][1]))):
+            assert torch.equal(E.ws_bits(o), E.ws_bits(e)), (what, metrics.FVD_ENDPOINTS[k])
+
+
 # ------------------------------------------------------------------------------------------- clip scoring
 from test_gpu_metrics import KW, _write_clip, small  # noqa: E402,F401  (the clip fixtures of the PSNR / MS-SSIM tests)
 

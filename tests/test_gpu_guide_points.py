@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 import torch
 
+import edge_cases as E
 import guide_ref as G
 from diffcodec_amd import lib
 from diffcodec_amd import guide_points as GP
@@ -34,9 +35,17 @@ def _stream():
 
 
 def _ws(N, H, W):
+    """a guarded fp32 workspace of exactly dc_guide_ws_bytes holding the NaN pattern; `_done` checks its guards"""
     nbytes = lib.load().dc_guide_ws_bytes(N, H, W)
-    assert nbytes > 0
-    return torch.empty(nbytes, dtype=torch.uint8, device=DEV)
+    assert nbytes > 0 and nbytes % 4 == 0
+    ws = E.Guarded((nbytes // 4,), torch.float32, DEV)
+    assert ws.view.data_ptr() % 256 == 0
+    return ws
+
+
+def _done(ws, what):
+    torch.cuda.synchronize()
+    ws.assert_intact(f"{what}: workspace")
 
 
 # ------------------------------------------------------------------------------------------------ the stage entries
@@ -48,8 +57,8 @@ def dev_edge(flow):
     mag = torch.full((N, h, w), -1.0, dtype=torch.float32, device=DEV)
     edge = torch.full((N, h, w), 7, dtype=torch.uint8, device=DEV)
     ws = _ws(N, H, W)
-    lib.call("dc_guide_edge", flow.data_ptr(), N, H, W, ws.data_ptr(), mag.data_ptr(), edge.data_ptr(), _stream())
-    torch.cuda.synchronize()
+    lib.call("dc_guide_edge", flow.data_ptr(), N, H, W, ws.view.data_ptr(), mag.data_ptr(), edge.data_ptr(), _stream())
+    _done(ws, "dc_guide_edge")
     return mag.cpu(), edge.cpu()
 
 
@@ -58,8 +67,8 @@ def dev_edt(edge):
     N, h, w = edge.shape
     d2 = torch.full((N, h, w), -1, dtype=torch.int32, device=DEV)
     ws = _ws(N, h, w)
-    lib.call("dc_guide_edt", edge.data_ptr(), N, h, w, ws.data_ptr(), d2.data_ptr(), _stream())
-    torch.cuda.synchronize()
+    lib.call("dc_guide_edt", edge.data_ptr(), N, h, w, ws.view.data_ptr(), d2.data_ptr(), _stream())
+    _done(ws, "dc_guide_edt")
     return d2.cpu().numpy()
 
 
@@ -68,8 +77,8 @@ def dev_nms(d2, ks):
     N, h, w = d2.shape
     cand = torch.full((N, h, w), 7, dtype=torch.uint8, device=DEV)
     ws = _ws(N, h, w)
-    lib.call("dc_guide_nms", d2.data_ptr(), N, h, w, ks, ws.data_ptr(), cand.data_ptr(), _stream())
-    torch.cuda.synchronize()
+    lib.call("dc_guide_nms", d2.data_ptr(), N, h, w, ks, ws.view.data_ptr(), cand.data_ptr(), _stream())
+    _done(ws, "dc_guide_nms")
     return cand.cpu().numpy()
 
 
@@ -80,8 +89,8 @@ def dev_select(cand, ks, scale=1, slack=0):
     counts = torch.full((N,), -7, dtype=torch.int32, device=DEV)
     points = torch.full((N, cap, 2), -7, dtype=torch.int32, device=DEV)
     ws = _ws(N, h, w)
-    lib.call("dc_guide_select", cand.data_ptr(), N, h, w, ks, scale, ws.data_ptr(), counts.data_ptr(), points.data_ptr(), cap, _stream())
-    torch.cuda.synchronize()
+    lib.call("dc_guide_select", cand.data_ptr(), N, h, w, ks, scale, ws.view.data_ptr(), counts.data_ptr(), points.data_ptr(), cap, _stream())
+    _done(ws, "dc_guide_select")
     return counts.cpu().numpy(), points.cpu().numpy()
 
 
@@ -403,3 +412,82 @@ def test_propagated_flow_source_passes_the_watershed_operand_on():
     assert int(model.sparse[:, 2].sum()) > int(sample_grid(both, 16)[:, 2].sum())
     PropagatedFlowSource(inner, model, stride=16).controls(1, 0, 2)
     assert torch.equal(model.sparse, sample_grid(both, 16))
+
+
+# ------------------------------------------------------------------------------------------------ the caller-owned workspace
+# (N, H, W, ks, stride): odd H and W that are multiples of neither the grid stride nor the NMS window; the 1 x 1 working image
+WS_CASES = [(3, 37, 53, 5, 8), (2, 1, 1, 3, 2)]
+
+
+def _ws_flows(N, H, W, seed):
+    if H == 1:
+        return torch.randn(N, 2, H, W, generator=torch.Generator().manual_seed(seed))
+    return torch.stack([_flow(H, W, seed + i, 4) for i in range(N)])
+
+
+@pytest.mark.parametrize("N,H,W,ks,stride", WS_CASES, ids=[f"n{c[0]}_{c[1]}x{c[2]}_ks{c[3]}" for c in WS_CASES])
+def test_every_entry_on_a_guarded_workspace_of_any_contents(record, N, H, W, ks, stride):
+    """the five stage entries, each fed the stage before it, and dc_guide_watershed, each on a guarded workspace of exactly
+    dc_guide_ws_bytes under the NaN, zero and stale fills (the stale one left by the same entry on other flows): integer-exact, so
+    equality under the fills covers the counts, the points and the scattered map; the chain's and the fused entry's outputs are the
+    bits watershed_points / sample_watershed return.  (dc_guide_scatter takes no workspace: it runs under the same guards.)"""
+    ds, h, w = GP.working_size(H, W)
+    assert ds == 1
+    cap = GP.max_points(h, w, ks)
+    nbytes = lib.load().dc_guide_ws_bytes(N, H, W)
+    flows = [_ws_flows(N, H, W, seed).to(DEV).contiguous() for seed in (70, 170)]
+    # the other flows' stage outputs, through the stage entries on their own workspaces: what each prime launch is fed
+    _, edge_p = dev_edge(flows[1].cpu())
+    d2_p = dev_edt(edge_p.numpy())
+    cand_p = dev_nms(d2_p, ks)
+    counts_p, points_p = dev_select(cand_p, ks, ds)
+    fed = {"edge": [flows[0], flows[1]], "edt": [None, edge_p.to(DEV)], "nms": [None, torch.from_numpy(d2_p).to(DEV)],
+           "select": [None, torch.from_numpy(cand_p).to(DEV)],
+           "scatter": [None, (torch.from_numpy(counts_p).to(DEV), torch.from_numpy(points_p).to(DEV))]}
+    tag = f"{N}x{H}x{W} ks{ks}"
+
+    def run(name, launch, outputs):
+        outs, share = E.run_on_fills(launch, nbytes, outputs, f"dc_guide_{name} {tag}", device=DEV)
+        record(f"ws_unwritten_share[dc_guide_{name} {tag}]", share)
+        return outs
+
+    def edge(ws, outs, prime):
+        lib.call("dc_guide_edge", fed["edge"][int(prime)].data_ptr(), N, H, W, ws.data_ptr(), outs[0].data_ptr(), outs[1].data_ptr(), _stream())
+
+    _, e = run("edge", edge, [((N, h, w), torch.float32), ((N, h, w), torch.uint8)])
+    fed["edt"][0] = e
+
+    def edt(ws, outs, prime):
+        lib.call("dc_guide_edt", fed["edt"][int(prime)].data_ptr(), N, h, w, ws.data_ptr(), outs[0].data_ptr(), _stream())
+
+    fed["nms"][0], = run("edt", edt, [((N, h, w), torch.int32)])
+
+    def nms(ws, outs, prime):
+        lib.call("dc_guide_nms", fed["nms"][int(prime)].data_ptr(), N, h, w, ks, ws.data_ptr(), outs[0].data_ptr(), _stream())
+
+    fed["select"][0], = run("nms", nms, [((N, h, w), torch.uint8)])
+
+    def select(ws, outs, prime):
+        lib.call("dc_guide_select", fed["select"][int(prime)].data_ptr(), N, h, w, ks, ds, ws.data_ptr(), outs[0].data_ptr(),
+                 outs[1].data_ptr(), cap, _stream())
+
+    counts, points = run("select", select, [((N,), torch.int32), ((N, cap, 2), torch.int32)])
+    fed["scatter"][0] = (counts, points)
+
+    def scatter(ws, outs, prime):
+        c, p = fed["scatter"][int(prime)]
+        lib.call("dc_guide_scatter", flows[int(prime)].data_ptr(), N, H, W, stride, c.data_ptr(), p.data_ptr(), cap, outs[0].data_ptr(), _stream())
+
+    sparse, = run("scatter", scatter, [((N, 4, H, W), torch.float32)])
+
+    def fused(ws, outs, prime):
+        lib.call("dc_guide_watershed", flows[int(prime)].data_ptr(), N, H, W, ks, stride, ws.data_ptr(), outs[0].data_ptr(), outs[1].data_ptr(),
+                 cap, outs[2].data_ptr(), _stream())
+
+    fc, fp, fs = run("watershed", fused, [((N,), torch.int32), ((N, cap, 2), torch.int32), ((N, 4, H, W), torch.float32)])
+    wc, wp = GP.watershed_points(flows[0], ks)
+    wsparse = GP.sample_watershed(flows[0], ks, stride=stride)
+    for got in ((counts, points, sparse), (fc, fp, fs)):
+        assert torch.equal(got[0], wc) and torch.equal(got[1], wp) and torch.equal(E.ws_bits(got[2]), E.ws_bits(wsparse))
+    if H > 1:
+        assert int(wc.sum()) > 0 and int(counts_p.sum()) > 0                                      # both sets of flows have points

@@ -271,6 +271,72 @@ def test_operand_forms(lib):
         assert m(c["x"].clone().requires_grad_(True), c["y"]).grad_fn is None
 
 
+# ------------------------------------------------------------------------------------------------ the caller-owned buffers
+# (N, H, W, sides): the ragged pooled maps (16x23 -> 7x11 -> 3x5) of an odd batch for each operand and for both (M = N and 2N
+# images in the backward), and the minimum size.  The stage entries (dc_lpips_tail_grad, _conv_dgrad, _pool_grad, _conv1_dgrad)
+# take no workspace.
+KEEP_CASES = [(3, 67, 95, 1), (3, 67, 95, 2), (3, 67, 95, 3), (1, 31, 31, 3)]
+
+
+@pytest.mark.parametrize("n,h,w,sides", KEEP_CASES, ids=[f"{c[0]}x{c[1]}x{c[2]}_sides{c[3]}" for c in KEEP_CASES])
+def test_keep_and_backward_on_guarded_buffers_of_any_contents(lib, record, n, h, w, sides):
+    """dc_lpips_alex_keep into a guarded keep buffer of exactly dc_lpips_keep_ws_bytes, then dc_lpips_alex_backward from that
+    buffer (still holding the NaN pattern wherever the forward wrote nothing) on a guarded workspace of exactly
+    dc_lpips_train_ws_bytes, each under the NaN, zero and stale fills: the kept bits do not depend on the fill, the backward
+    leaves them untouched, and the value and the gradients are the bits NormFixLPIPS returns through autograd"""
+    m = model()
+    dev = torch.device(DEV)
+    wts, dwts = m._weights(dev), m._dgrad_weights(dev)
+    sets = []
+    for seed in (SEED + 40 + n, 977):
+        x, y, g = R.loss_inputs(n, h, w, seed)
+        gx, gy = guarded(x), guarded(y)
+        sets.append(dict(gx=gx, gy=gy, x=gx.view, y=gy.view, g=g.to(DEV, F32)))
+    s = (3 * h * w, h * w, w, 1)
+    strides = (ctypes.c_longlong * 8)(*s, *s)
+    ops = [c[k] for c in sets for k in ("gx", "gy")]
+
+    def keep_launch(ws, outs, prime):
+        c = sets[int(prime)]
+        lib.call("dc_lpips_alex_keep", c["x"].data_ptr(), c["y"].data_ptr(), strides, n, h, w, 0, wts.data_ptr(), ws.data_ptr(),
+                 outs[0].data_ptr(), stream())
+
+    tag = f"{n}x{h}x{w} sides={sides}"
+    L_ = lib.load()
+    (out, kept), share = E.run_on_fills(keep_launch, L_.dc_lpips_keep_ws_bytes(n, h, w), [((6, n), F64)], f"dc_lpips_alex_keep {tag}",
+                                        operands=ops, device=DEV, keep=True)
+    record(f"ws_unwritten_share[dc_lpips_alex_keep {tag}]", share)
+    # the backward's operands: the kept maps of each input set in guarded buffers, g [5][N] as the wrapper forms it
+    keeps = []
+    for c in sets:
+        gk = E.Guarded(tuple(kept.shape), F32, DEV)
+        if c is sets[0]:
+            gk.view.copy_(kept)
+        else:
+            lib.call("dc_lpips_alex_keep", c["x"].data_ptr(), c["y"].data_ptr(), strides, n, h, w, 0, wts.data_ptr(), gk.view.data_ptr(),
+                     torch.empty(6 * n, dtype=F64, device=DEV).data_ptr(), stream())
+        keeps.append(gk)
+    g5 = [c["g"].view(1, n).repeat(5, 1).contiguous() for c in sets]
+    before = E.ws_bits(keeps[0].view).clone()
+
+    def backward(ws, outs, prime):
+        d = iter(outs)
+        dx = next(d).data_ptr() if sides & 1 else None
+        dy = next(d).data_ptr() if sides & 2 else None
+        lib.call("dc_lpips_alex_backward", keeps[int(prime)].view.data_ptr(), g5[int(prime)].data_ptr(), n, h, w, 0, sides, wts.data_ptr(),
+                 dwts.data_ptr(), ws.data_ptr(), dx, dy, stream())
+
+    what = f"dc_lpips_alex_backward {tag}"
+    got, share = E.run_on_fills(backward, L_.dc_lpips_train_ws_bytes(n, h, w, sides), [((n, 3, h, w), F32)] * bin(sides).count("1"), what,
+                                operands=keeps, device=DEV)
+    record(f"ws_unwritten_share[{what}]", share)
+    assert torch.equal(E.ws_bits(keeps[0].view), before), f"{what}: the backward wrote into the keep buffer"
+    c = sets[0]
+    val, *want = grads(m, c["x"], c["y"], c["g"], {1: "x", 2: "y", 3: "xy"}[sides])
+    assert torch.equal(E.ws_bits(out.float()[5].reshape(n, 1, 1, 1)), E.ws_bits(val))
+    assert len(got) == len(want) and all(torch.equal(E.ws_bits(a), E.ws_bits(b)) for a, b in zip(got, want))
+
+
 # ------------------------------------------------------------------------------------------------ exactness
 def test_value_under_grad_has_the_bits_of_the_metric(lib):
     from diffcodec_amd import metrics

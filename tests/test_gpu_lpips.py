@@ -245,6 +245,79 @@ def test_reproducible_graph_capturable_and_host_tensors(model, sd):
     assert all(not t.is_cuda for t in fh)
 
 
+# ------------------------------------------------------------------------------------------- the caller-owned workspace
+# (N, H, W, operand form): the minimum size (every map of relu3..5 is one pixel) and an odd batch of ragged pooled maps (16x23 ->
+# 7x11 -> 3x5), one on each operand form
+WS_CASES = [(1, 31, 31, "f1"), (3, 67, 95, "u8")]
+
+
+def _ws_operands(n, h, w, form, seed):
+    """(x, y) of one operand form inside guarded buffers on the device -> (guards, tensors, element strides (n, c, h, w))"""
+    import edge_cases as E
+    guards, tensors = [], []
+    for t in _pair_u8(n, h, w, seed):
+        t = _form(t, form)
+        g = E.Guarded(tuple(t.shape), t.dtype, DEV)
+        guards.append(g)
+        tensors.append(g.fill(t.to(DEV)))
+    strides = (h * w * 3, 1, w * 3, 3) if form == "u8" else (3 * h * w, h * w, w, 1)
+    return guards, tensors, strides
+
+
+@pytest.mark.parametrize("normfix", [False, True], ids=["plain", "normfix"])
+@pytest.mark.parametrize("n,h,w,form", WS_CASES, ids=[f"n{c[0]}_{c[1]}x{c[2]}_{c[3]}" for c in WS_CASES])
+def test_value_on_a_guarded_workspace_of_any_contents(sd, record, n, h, w, form, normfix):
+    """dc_lpips_alex on a guarded workspace of exactly dc_lpips_ws_bytes under the NaN, zero and stale fills: the six rows are the
+    bits LPIPS.__call__ returns"""
+    import ctypes
+    import edge_cases as E
+    from diffcodec_amd import lib, metrics
+    m = metrics.LPIPS.from_state_dict(sd, normfix=normfix).to(DEV)
+    wts = m._weights(torch.device(DEV))
+    sets = [_ws_operands(n, h, w, form, seed) for seed in (h * 7 + w + n, 977)]
+    st = torch.cuda.current_stream().cuda_stream
+
+    def launch(ws, outs, prime):
+        _, (x, y), s = sets[int(prime)]
+        lib.call("dc_lpips_alex", x.data_ptr(), y.data_ptr(), int(form == "u8"), (ctypes.c_longlong * 8)(*s, *s), n, h, w, 0, int(normfix),
+                 wts.data_ptr(), ws.data_ptr(), outs[0].data_ptr(), st)
+
+    what = f"dc_lpips_alex {n}x{h}x{w} {form} normfix={int(normfix)}"
+    (out,), share = E.run_on_fills(launch, lib.load().dc_lpips_ws_bytes(n, h, w), [((6, n), torch.float64)], what,
+                                   operands=sets[0][0] + sets[1][0], device=DEV)
+    record(f"ws_unwritten_share[{what}]", share)
+    val, layers = m(sets[0][1][0], sets[0][1][1], retPerLayer=True)
+    got = out.float()
+    assert torch.equal(E.ws_bits(got[5].reshape(n, 1, 1, 1)), E.ws_bits(val)), what
+    for l in range(5):
+        assert torch.equal(E.ws_bits(got[l].reshape(n, 1, 1, 1)), E.ws_bits(layers[l])), (what, l)
+
+
+@pytest.mark.parametrize("n,h,w,form", WS_CASES, ids=[f"n{c[0]}_{c[1]}x{c[2]}_{c[3]}" for c in WS_CASES])
+def test_features_on_a_guarded_workspace_of_any_contents(model, record, n, h, w, form):
+    """dc_lpips_alex_features on a guarded workspace of exactly dc_lpips_features_ws_bytes under the three fills: the five maps
+    are the bits LPIPS.features returns"""
+    import ctypes
+    import edge_cases as E
+    from diffcodec_amd import lib, metrics
+    wts = model._weights(torch.device(DEV))
+    sets = [_ws_operands(n, h, w, form, seed) for seed in (h * 7 + w + n, 977)]
+    st = torch.cuda.current_stream().cuda_stream
+    shapes = [((n, co) + s, torch.float32) for co, s in zip(metrics.LPIPS_CHANNELS, metrics.lpips_map_sizes(h, w))]
+
+    def launch(ws, outs, prime):
+        _, (x, _), s = sets[int(prime)]
+        lib.call("dc_lpips_alex_features", x.data_ptr(), int(form == "u8"), (ctypes.c_longlong * 4)(*s), n, h, w, 0, wts.data_ptr(),
+                 ws.data_ptr(), *[o.data_ptr() for o in outs], st)
+
+    what = f"dc_lpips_alex_features {n}x{h}x{w} {form}"
+    outs, share = E.run_on_fills(launch, lib.load().dc_lpips_features_ws_bytes(n, h, w), shapes, what,
+                                 operands=sets[0][0] + sets[1][0], device=DEV)
+    record(f"ws_unwritten_share[{what}]", share)
+    for l, (o, f) in enumerate(zip(outs, model.features(sets[0][1][0]))):
+        assert torch.equal(E.ws_bits(o), E.ws_bits(f)), (what, l)
+
+
 # ------------------------------------------------------------------------------------------- clip scoring
 from test_gpu_metrics import KW, _free_port, _write_clip, small  # noqa: E402,F401  (the clip fixtures of the PSNR / MS-SSIM tests)
 
