@@ -356,11 +356,14 @@ class StableDiffusionDualFlowControlNetPipeline:
             self._graphs.clear()
         st["lat"].copy_(latents)
         st["step"].zero_()
-        # text context: cached per tensor identity inside the modules (cross-attention K/V are step-invariant)
-        if st.get("ctx_src") is None or st["ctx_src"][0] is not pe or st["ctx_src"][1] is not npe:
+        # text context: cached inside the modules (cross-attention K/V are step-invariant).  Keyed like their caches on pointer,
+        # shape and in-place version of both embeddings — `is` alone would keep the previous prompt after `pe.copy_(other)`; the
+        # tensors are kept alive so that a freed pointer cannot come back under the same key
+        ctx_key = tuple((t.data_ptr(), tuple(t.shape), t._version) for t in (pe, npe) if t is not None)
+        if st.get("ctx_key") != ctx_key:
             ctx = torch.cat([npe, pe], 0) if do_cfg else pe
             st["ctx"] = ctx.to(device=device, dtype=torch.bfloat16).contiguous()
-            st["ctx_src"] = (pe, npe)
+            st["ctx_key"], st["ctx_src"] = ctx_key, (pe, npe)
         unet.set_context(st["ctx"])
         for cn in nets:
             cn.set_context(st["ctx"])

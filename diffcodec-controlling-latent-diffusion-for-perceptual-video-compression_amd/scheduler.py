@@ -59,6 +59,10 @@ class DDIMScheduler:
         self.num_inference_steps = num_inference_steps
         ratio = self.num_train_timesteps // num_inference_steps
         ts = (np.arange(0, num_inference_steps) * ratio).round()[::-1].copy().astype(np.int64) + self.steps_offset
+        # leading spacing with a steps_offset can ask for t = num_train_timesteps (1000 steps of 1000 with offset 1: t = 1000 .. 1),
+        # which alphas_cumprod does not hold; indexing it failed in `coefficients()`.  The schedule is served where the table
+        # exists: it starts at the last entry (every sparser schedule starts below it too), `len(timesteps)` steps are run
+        ts = ts[ts < self.num_train_timesteps].copy()
         self.timesteps = torch.from_numpy(ts)
         self._coef_dev = None
 
@@ -106,7 +110,9 @@ class DDIMScheduler:
         `noise_dtype`: the dtype the variance noise is DRAWN in.  diffusers draws it in `model_output.dtype`, and in the reference the
         CFG combine stays in the model dtype (pipeline.py:370-372), so that is the U-Net's output dtype (bf16 / fp16 at configs[1]);
         this repo's CFG combine is fp32, so the pipeline passes the U-Net's dtype here explicitly — a CPU generator yields a different
-        stream for a bf16 draw than for an fp32 one.  Default: `model_output.dtype`.  Parity unpinned (diffusers not importable)."""
+        stream for a bf16 draw than for an fp32 one.  Default: `model_output.dtype`.  The eta = 0 arithmetic is held to the exact ODE of a Gaussian prior (DESIGN.md section
+        15: first-order convergence, exact on a point mass, the rows are DPM-Solver-1); the schedule itself (betas, leading spacing,
+        steps_offset) and the eta > 0 branch stay recalled from diffusers, which is not importable."""
         idx = (self.timesteps == int(timestep)).nonzero()
         if idx.numel() == 0:
             raise ValueError(f"timestep {timestep} is not in the current schedule")
@@ -139,7 +145,9 @@ class UniPCMultistepScheduler:
     """The scheduler the reference actually instantiates (validation.py:37, `UniPCMultistepScheduler.from_pretrained(base,
     subfolder="scheduler")`): diffusers' UniPC with its defaults on top of the SD-1.5 scheduler_config — solver_order 2,
     bh2, predict_x0, lower_order_final, epsilon prediction, leading spacing, steps_offset 1, final sigma 0 [recalled; the
-    reference holds no fixture -> parity unpinned].  All coefficients are host scalars; every tensor update is one
+    reference holds no fixture].  The solver's arithmetic is held to the exact ODE of a Gaussian prior (orders
+    1 / 2 / 2 / 3 for predictor and corrector, exact on a point mass through the infinite last step); the schedule itself (betas,
+    leading spacing, steps_offset) stays recalled.  All coefficients are host scalars; every tensor update is one
     `dc_lincomb4_f32` launch on fp32 state."""
     order = 1
     init_noise_sigma = 1.0
