@@ -34,6 +34,8 @@ __device__ __forceinline__ bf16_t dc_f2bf(float v) { return (bf16_t)v; }   // v_
 // v_div_scale / v_div_fmas / v_div_fixup sequence per element, which made the GroupNorm-apply pass and every GN-on-load halo
 // VALU-bound (gn_apply ran at 3.1 TB/s); the result is rounded to bf16 right after, 2^-16 below its last bit.
 __device__ __forceinline__ float dc_silu(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
+// the sigmoid inside dc_silu, spelled the same way: the SiLU gradient (conv_f32_grad.hip) evaluates it as the forward does
+__device__ __forceinline__ float dc_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 // dc_conv_desc.act: 1 = SiLU, 2 = quick-GELU x * sigmoid(1.702 x) (CLIP text MLP)
 __device__ __forceinline__ float dc_act(float x, int act) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(act == 2 ? -1.702f * x : -x)); }
 // erf by Abramowitz-Stegun 7.1.26 (|abs err| <= 1.5e-7, far below the bf16 output rounding): 1 rcp + 1 exp + 7 fma

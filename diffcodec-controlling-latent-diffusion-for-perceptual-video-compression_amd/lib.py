@@ -154,6 +154,15 @@ GUIDE_SIGNATURES = {
     "dc_guide_watershed": [vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp],
 }
 
+# name -> argtypes of include/diffcodec_train_hip.h (csrc/conv_f32_grad.hip; tests/test_train_abi.py cross-checks that header)
+TRAIN_SIGNATURES = {
+    "dc_silu_grad_f32": [vp, vp, vp, i64, vp],
+    "dc_conv3x3_f32_dgrad": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
+    "dc_conv3x3_f32_wgrad_ws_bytes": [i32, i32, i32, i32, i32, i32],
+    "dc_conv3x3_f32_wgrad": [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
+    "dc_conv3x3_f32_grad_route": [i32, i32, i32, i32, i32, i32, i32, POINTER(i32)],
+}
+
 _lib = None
 
 
@@ -176,7 +185,7 @@ def load():
         fn.argtypes = args
         fn.restype = c_longlong if name.endswith("_ws_bytes") else c_int
     lib.dc_gn_stats_chunks.restype = c_int
-    for table in (FLOW_SIGNATURES, LOSS_SIGNATURES, GUIDE_SIGNATURES):
+    for table in (FLOW_SIGNATURES, LOSS_SIGNATURES, GUIDE_SIGNATURES, TRAIN_SIGNATURES):
         for name, args in table.items():
             fn = getattr(lib, name)
             fn.argtypes = args
