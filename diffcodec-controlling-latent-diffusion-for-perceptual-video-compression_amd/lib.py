@@ -1,4 +1,4 @@
-"""ctypes binding of the C-ABI declared in include/diffcodec_hip.h.
+"""ctypes binding of the C-ABI declared in the headers under include/ (`ABI` lists them).
 
 The product path has no CPU fallback: if the shared object is missing or a launcher returns non-zero, this
 module raises.  (Loading the library and resolving symbols needs no GPU; launching does.)"""
@@ -26,7 +26,7 @@ class ConvDesc(ctypes.Structure):
     ]
 
 
-# name -> argtypes (every symbol include/diffcodec_hip.h declares; tests/test_abi.py cross-checks the header)
+# name -> argtypes (every symbol include/diffcodec_hip.h declares; tests/test_abi.py cross-checks every table below with its header)
 SIGNATURES = {
     "dc_splat_soft_f32": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
     "dc_splat_sum_f32": [vp, vp, vp, vp, i32, i32, i32, i32, vp],
@@ -110,7 +110,7 @@ SIGNATURES = {
     "dc_resample_u8": [vp, POINTER(i64), i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp],
 }
 
-# name -> argtypes of include/diffcodec_flow_hip.h (csrc/cmp.hip; tests/test_cmp_abi.py cross-checks that header)
+# name -> argtypes of include/diffcodec_flow_hip.h (csrc/cmp.hip)
 FLOW_SIGNATURES = {
     "dc_cmp_conv": [vp, i32, POINTER(i64), POINTER(f32), i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, i32, vp, i32, i32, vp],
     "dc_cmp_maxpool": [vp, i32, i32, i32, i32, i32, i32, vp, vp],
@@ -126,8 +126,7 @@ FLOW_SIGNATURES = {
     "dc_cmp_endpoints": [i32, vp, i32, POINTER(i64), vp, i32, i32, i32, i32, f32, vp, vp, POINTER(vp), vp, vp, vp, vp],
 }
 
-# name -> argtypes of include/diffcodec_loss_hip.h (csrc/lpips_grad.hip, csrc/edge_loss.hip; tests/test_loss_abi.py cross-checks
-# that header)
+# name -> argtypes of include/diffcodec_loss_hip.h (csrc/lpips_grad.hip, csrc/edge_loss.hip)
 LOSS_SIGNATURES = {
     "dc_lpips_dgrad_weight_floats": [],
     "dc_lpips_keep_ws_bytes": [i32, i32, i32],
@@ -143,7 +142,7 @@ LOSS_SIGNATURES = {
     "dc_sobel_edge_grad": [vp, vp, POINTER(i64), i32, i32, i32, i32, i32, vp, i32, f32, vp, vp],
 }
 
-# name -> argtypes of include/diffcodec_guide_hip.h (csrc/guide_points.hip; tests/test_guide_ref.py cross-checks that header)
+# name -> argtypes of include/diffcodec_guide_hip.h (csrc/guide_points.hip)
 GUIDE_SIGNATURES = {
     "dc_guide_ws_bytes": [i32, i32, i32],
     "dc_guide_edge": [vp, i32, i32, i32, vp, vp, vp, vp],
@@ -154,7 +153,7 @@ GUIDE_SIGNATURES = {
     "dc_guide_watershed": [vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp],
 }
 
-# name -> argtypes of include/diffcodec_train_hip.h (csrc/conv_f32_grad.hip; tests/test_train_abi.py cross-checks that header)
+# name -> argtypes of include/diffcodec_train_hip.h (csrc/conv_f32_grad.hip)
 TRAIN_SIGNATURES = {
     "dc_silu_grad_f32": [vp, vp, vp, i64, vp],
     "dc_conv3x3_f32_dgrad": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
@@ -162,6 +161,33 @@ TRAIN_SIGNATURES = {
     "dc_conv3x3_f32_wgrad": [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "dc_conv3x3_f32_grad_route": [i32, i32, i32, i32, i32, i32, i32, POINTER(i32)],
 }
+
+# the whole C surface: (header under include/, its table), one pair per launcher family.  load() binds what is listed here and
+# tests/test_abi.py holds every pair to its header; a new family adds a header, a table and one line here.
+ABI = (
+    ("diffcodec_hip.h", SIGNATURES),
+    ("diffcodec_flow_hip.h", FLOW_SIGNATURES),
+    ("diffcodec_loss_hip.h", LOSS_SIGNATURES),
+    ("diffcodec_guide_hip.h", GUIDE_SIGNATURES),
+    ("diffcodec_train_hip.h", TRAIN_SIGNATURES),
+)
+
+
+def signatures():
+    """name -> argtypes over every table of ABI; a name in two tables is an error"""
+    out = {}
+    for header, table in ABI:
+        twice = sorted(set(out) & set(table))
+        if twice:
+            raise ValueError(f"{twice} of {header} are already in an earlier table of lib.ABI")
+        out.update(table)
+    return out
+
+
+def restype_of(name):
+    """the C return type by the ABI's naming rule: a byte count is a long long, everything else an int"""
+    return c_longlong if name.endswith("_ws_bytes") else c_int
+
 
 _lib = None
 
@@ -180,16 +206,10 @@ def load():
         raise HipLibraryMissing(f"{path} not built: run `python -c 'import __graft_entry__ as g; g.build()'`. "
                                 "There is no CPU fallback on the product path.")
     lib = ctypes.CDLL(path)
-    for name, args in SIGNATURES.items():
+    for name, args in signatures().items():
         fn = getattr(lib, name)          # AttributeError if the symbol is missing
         fn.argtypes = args
-        fn.restype = c_longlong if name.endswith("_ws_bytes") else c_int
-    lib.dc_gn_stats_chunks.restype = c_int
-    for table in (FLOW_SIGNATURES, LOSS_SIGNATURES, GUIDE_SIGNATURES, TRAIN_SIGNATURES):
-        for name, args in table.items():
-            fn = getattr(lib, name)
-            fn.argtypes = args
-            fn.restype = c_longlong if name.endswith("_ws_bytes") else c_int
+        fn.restype = restype_of(name)
     _lib = lib
     return lib
 
@@ -242,3 +262,13 @@ def call(name, *args, meta=None):
         t.records.append((name, meta, e0, e1))
     if rc != 0:
         raise HipLaunchError(f"{name} returned {rc} ({'invalid argument' if rc == -1 else 'launch failure'})")
+
+
+def query(name, n_info, *args):
+    """Call a routing query (`*_route`, `*_instance`) whose last parameter is an int[n_info] it fills; -> the entries as a tuple.
+    Host code only: needs the library, not a GPU.  Raises HipLaunchError for what the launch would refuse."""
+    info = (ctypes.c_int * n_info)()
+    rc = getattr(load(), name)(*args, info)
+    if rc != 0:
+        raise HipLaunchError(f"{name} returned {rc} (invalid argument)")
+    return tuple(info)

@@ -199,11 +199,7 @@ class ConvRoute(tuple):
 def conv_route(d):
     """The dispatcher's decision for a ConvDesc, without launching (host code only: needs the library, not a GPU).  Raises
     HipLaunchError for a descriptor the launch would refuse."""
-    info = (ctypes.c_int * 5)()
-    rc = lib.load().dc_conv_route(d, info)
-    if rc != 0:
-        raise lib.HipLaunchError(f"dc_conv_route returned {rc} (invalid argument)")
-    return ConvRoute(tuple(info))
+    return ConvRoute(lib.query("dc_conv_route", 5, d))
 
 
 # template arguments of each kernel's instance, in the order dc_conv_instance reports them
@@ -215,10 +211,7 @@ INSTANCE_ARGS = {"gemm_dma": ("TM", "TN", "NST", "EPI"), "gemm_wide": ("TN", "EP
 def conv_instance(d):
     """The kernel instance dc_conv_igemm_bf16 launches for a ConvDesc (dc_conv_instance): {"kernel": name, template argument: value}.
     Raises as conv_route does."""
-    info = (ctypes.c_int * 9)()
-    rc = lib.load().dc_conv_instance(d, info)
-    if rc != 0:
-        raise lib.HipLaunchError(f"dc_conv_instance returned {rc} (invalid argument)")
+    info = lib.query("dc_conv_instance", 9, d)
     kernel = ROUTE_NAMES[info[0]]
     return dict(zip(INSTANCE_ARGS[kernel], info[1:]), kernel=kernel)
 
@@ -389,10 +382,7 @@ def conv3x3_f32_route(cin, h, w, cout, stride):
     """The kernel instance `conv3x3_nchw_f32` launches for Cin x H x W -> Cout at `stride`, without launching (host code only:
     needs the library, not a GPU): form 'mfma' | 'blk' | 'direct', its STRIDE, its output channels and pixels per workgroup and
     the pixel tile's columns x rows (dc_conv3x3_f32_route).  Raises HipLaunchError for a shape the launch would refuse."""
-    info = (ctypes.c_int * 6)()
-    rc = lib.load().dc_conv3x3_f32_route(int(cin), int(h), int(w), int(cout), int(stride), info)
-    if rc != 0:
-        raise lib.HipLaunchError(f"dc_conv3x3_f32_route returned {rc} (invalid argument)")
+    info = lib.query("dc_conv3x3_f32_route", 6, int(cin), int(h), int(w), int(cout), int(stride))
     return F32ConvRoute(F32CONV_FORMS[info[0]], *info[1:])
 
 
@@ -520,11 +510,7 @@ class AttentionRoute(tuple):
 def attention_route(b, heads, nq, nk, d):
     """The form `attention` launches for B x heads x Nq x Nk at head dim d, without launching (host code only: needs the library,
     not a GPU).  Raises HipLaunchError for a shape the launch would refuse."""
-    info = (ctypes.c_int * 5)()
-    rc = lib.load().dc_attention_route(int(b), int(heads), int(nq), int(nk), int(d), info)
-    if rc != 0:
-        raise lib.HipLaunchError(f"dc_attention_route returned {rc} (invalid argument)")
-    return AttentionRoute(tuple(info))
+    return AttentionRoute(lib.query("dc_attention_route", 5, int(b), int(heads), int(nq), int(nk), int(d)))
 
 
 def attention_causal(q, k, v, heads, scale=None):

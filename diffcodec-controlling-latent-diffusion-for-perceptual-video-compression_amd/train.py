@@ -9,7 +9,6 @@ goes through; its output has the bits of the inference call `ops.conv3x3_nchw_f3
 summation order and no float atomics: bitwise reproducible, the data gradient of an image independent of its position in the
 batch, and every launch only enqueues on the current stream (graph-capturable).  The weight is read in checkpoint layout on every
 call, so an optimiser step needs no repacking.  There is no double backward and no CPU path."""
-import ctypes
 from collections import namedtuple
 
 import torch
@@ -28,10 +27,7 @@ def conv3x3_f32_grad_route(kind, n, cin, h, w, cout, stride):
     """The kernel instance the data gradient (kind 'dgrad') or the weight gradient ('wgrad') launches for a shape, without launching
     (host code only: needs the library, not a GPU): form 'mfma' | 'valu', the MFMA form's STRIDE and channels per workgroup, its pixel
     tile, and for wgrad the K partition (dc_conv3x3_f32_grad_route).  Raises HipLaunchError for a shape the launch would refuse."""
-    info = (ctypes.c_int * 8)()
-    rc = lib.load().dc_conv3x3_f32_grad_route(GRAD_KINDS[kind], int(n), int(cin), int(h), int(w), int(cout), int(stride), info)
-    if rc != 0:
-        raise lib.HipLaunchError(f"dc_conv3x3_f32_grad_route returned {rc} (invalid argument)")
+    info = lib.query("dc_conv3x3_f32_grad_route", 8, GRAD_KINDS[kind], int(n), int(cin), int(h), int(w), int(cout), int(stride))
     return GradRoute(GRAD_FORMS[info[0]], *info[1:])
 
 

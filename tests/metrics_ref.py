@@ -21,9 +21,10 @@ def window(ws=11, sigma=1.5):
 
 
 def as_nchw64(t):
-    """uint8 NHWC frames or float NCHW images -> fp64 NCHW on the CPU."""
+    """uint8 NHWC frames or float NCHW images -> fp64 NCHW on the CPU (dense NCHW either way: a permuted view would let torch sum
+    in the order of its strides, and the last bit would depend on where the frames came from)."""
     t = t.detach().cpu()
-    return t.permute(0, 3, 1, 2).double() if t.dtype == torch.uint8 else t.double()
+    return t.permute(0, 3, 1, 2).double().contiguous() if t.dtype == torch.uint8 else t.double()
 
 
 def gaussian_filter(x, g):

@@ -1,7 +1,7 @@
 """CPU: the edge-case tables of tests/edge_cases.py cover every kernel instance the dispatchers can reach, every case routes to the
 instance it declares, and the checks the GPU edge tests rely on (guarded buffers, the flat and peaked attention input families held
 to oracle/launch_ref.py) reject the faults they are there to catch.  Caller-owned workspaces: E.run_on_fills rejects an overrun, a
-read of an unwritten slot and an unwritten output; every dc_*_ws_bytes of the four signature tables has a guarding GPU module
+read of an unwritten slot and an unwritten output; every dc_*_ws_bytes of the signature tables has a guarding GPU module
 (WS_QUERY_TESTS) and grows with N no faster than N; ops.conv asks for the scratch the library states."""
 import functools
 import json
@@ -12,6 +12,7 @@ import re
 import pytest
 import torch
 
+import abi_check as A
 import edge_cases as E
 from oracle import launch_ref as L
 
@@ -21,11 +22,7 @@ F64 = torch.float64
 
 @pytest.fixture(scope="module")
 def lib():
-    import __graft_entry__ as g
-    from diffcodec_amd import lib as l
-    if not os.path.exists(l.LIB_PATH):
-        g.build()
-    return l
+    return A.built_lib()
 
 
 # ------------------------------------------------------------------------------------------ conv / linear routes
@@ -453,23 +450,10 @@ def test_elementwise_table_names_every_launcher_and_passes_one_grid():
     assert bool((x < -1).any()) and bool((x > 1).any()) and bool((x == 1).any()) and bool((x == -1).any())
 
 
-def _lib_calls(path):
-    """C names that are the literal first argument of a `lib.call(...)` expression in a test module (from its syntax tree: a name
-    in a comment or in an unused string does not count)"""
-    import ast
-    names = set()
-    for node in ast.walk(ast.parse(open(path).read())):
-        if isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr == "call" and \
-                isinstance(node.func.value, ast.Name) and node.func.value.id == "lib" and node.args and \
-                isinstance(node.args[0], ast.Constant) and isinstance(node.args[0].value, str):
-            names.add(node.args[0].value)
-    return names
-
-
 def test_every_control_and_elementwise_launcher_has_an_edge_test():
     """tests/test_gpu_edges.py holds a `lib.call` of every one of them by its C name"""
     from diffcodec_amd import lib as l
-    called = _lib_calls(os.path.join(ROOT, "tests", "test_gpu_edges.py"))
+    called = A.lib_calls(A.module_source("test_gpu_edges"))
     c_name = {"splat_soft": "dc_splat_soft_f32", "splat_sum": "dc_splat_sum_f32", "occlusion_mask": "dc_occlusion_mask_f32",
               "flow_resize_normalize": "dc_flow_resize_normalize_f32", "flow_resize_divide": "dc_flow_resize_divide_f32",
               "fuse_warped": "dc_fuse_warped_f32", "lincomb": "dc_lincomb4_f32", "freeu_lowfreq": "dc_freeu_lowfreq_nhwc_bf16",
@@ -693,8 +677,8 @@ def _package_holders(cname):
 
 
 @functools.lru_cache(maxsize=None)
-def _lib_calls_cached(path):
-    return frozenset(_lib_calls(path))
+def _literal_calls_in(path):
+    return frozenset(A.lib_calls(open(path).read()))
 
 
 def launcher_census(table):
@@ -712,7 +696,7 @@ def launcher_census(table):
         if not os.path.exists(path):
             out.append(f"{name}: tests/{module}.py does not exist")
         elif token == name:
-            if name not in _lib_calls_cached(path):
+            if name not in _literal_calls_in(path):
                 out.append(f"{name}: no literal lib.call in tests/{module}.py")
         elif not holder or holder[0] not in _package_holders(name):
             out.append(f"{name}: the package function {holder[0] if holder else '?'} holds no literal lib.call of it")
@@ -923,6 +907,7 @@ WS_QUERY_TESTS = {
     "dc_lpips_train_ws_bytes": [("test_gpu_losses", _HELPER, ("dc_lpips_alex_backward",))],
     "dc_guide_ws_bytes": [("test_gpu_guide_points", _HELPER, ("dc_guide_edge", "dc_guide_edt", "dc_guide_nms", "dc_guide_select",
                                                               "dc_guide_watershed"))],
+    "dc_conv3x3_f32_wgrad_ws_bytes": [("test_gpu_conv_grad", _HELPER, ("dc_conv3x3_f32_wgrad",))],
     # through the seam of ops.conv (ops._scratch), handed guarded buffers for every case of E.CONV_SCRATCH_CASES
     "dc_conv_igemm_ws_bytes": [("test_gpu_edges", "CONV_SCRATCH_CASES", ("conv",))],
     # the exceptions: guarded workspaces of the declared size from before the helper
@@ -934,17 +919,10 @@ WS_QUERY_TESTS = {
 WS_EXCEPTIONS = ("dc_splat_ws_bytes", "dc_resample_ws_bytes", "dc_sobel_edge_ws_bytes", "dc_conv_igemm_ws_bytes")
 
 
-def _all_signatures():
-    from diffcodec_amd import lib as l
-    out = {}
-    for table in (l.SIGNATURES, l.FLOW_SIGNATURES, l.LOSS_SIGNATURES, l.GUIDE_SIGNATURES):
-        out.update(table)
-    return out
-
-
 def ws_census(table, signatures=None):
-    """-> the complaints, one per dc_*_ws_bytes of the four signature tables whose entry is missing or does not hold"""
-    sigs = _all_signatures() if signatures is None else signatures
+    """-> the complaints, one per dc_*_ws_bytes of the signature tables (lib.signatures()) whose entry is missing or does not hold"""
+    from diffcodec_amd import lib as l
+    sigs = l.signatures() if signatures is None else signatures
     out = []
     for name in sigs:
         if not name.endswith("_ws_bytes"):
@@ -965,15 +943,15 @@ def ws_census(table, signatures=None):
             elif token != _HELPER and name not in WS_EXCEPTIONS:
                 out.append(f"{name}: guarded by {token}, not by the shared helper, and not a listed exception")
             else:
-                missing = [c for c in consumers if c not in _lib_calls_cached(path) and c not in used]
+                missing = [c for c in consumers if c not in _literal_calls_in(path) and c not in used]
                 if not consumers or any(c not in sigs and c != "conv" for c in consumers):
-                    out.append(f"{name}: tests/{module}.py is given no consumer of the four signature tables")
+                    out.append(f"{name}: tests/{module}.py is given no consumer of the signature tables")
                 elif missing:
                     out.append(f"{name}: tests/{module}.py never launches {', '.join(missing)}")
                 else:
                     continue
             break
-    out += [f"{name}: an entry for something that is no dc_*_ws_bytes of the four signature tables" for name in table
+    out += [f"{name}: an entry for something that is no dc_*_ws_bytes of the signature tables" for name in table
             if name not in sigs or not name.endswith("_ws_bytes")]
     return out
 
@@ -983,7 +961,8 @@ def test_every_workspace_query_has_a_guarding_gpu_test():
 
 
 def test_removing_a_workspace_census_entry_names_the_query():
-    sigs = _all_signatures()
+    from diffcodec_amd import lib as l
+    sigs = l.signatures()
     assert sorted(n for n in sigs if n.endswith("_ws_bytes")) == sorted(WS_QUERY_TESTS)
     for name in WS_QUERY_TESTS:
         got = ws_census({k: v for k, v in WS_QUERY_TESTS.items() if k != name})
@@ -1013,6 +992,7 @@ WS_IN_N = {
     "dc_splat_ws_bytes": [(None, 7, 9), (None, 24, 40)],
     "dc_resample_ws_bytes": [(None, 37, 53, 3)],
     "dc_sobel_edge_ws_bytes": [(None, 3, 17, 70)],
+    "dc_conv3x3_f32_wgrad_ws_bytes": [(None, 32, 48, 48, 32, 1), (None, 64, 6, 10, 32, 2)],     # two of conv_grad_ref.CASES
 }
 
 
@@ -1044,4 +1024,6 @@ def test_rounded_workspace_sizes_never_shrink_with_n(lib, name):
 
 
 def test_every_n_taking_workspace_query_is_held_to_it():
-    assert sorted(WS_IN_N) == sorted(n for n in _all_signatures() if n.endswith("_ws_bytes") and n != "dc_conv_igemm_ws_bytes")
+    from diffcodec_amd import lib as l
+    queries = {n for n in l.signatures() if n.endswith("_ws_bytes") and n != "dc_conv_igemm_ws_bytes"}
+    assert set(WS_IN_N) == queries, f"in WS_IN_N or among the exports, not both: {sorted(set(WS_IN_N) ^ queries)}"

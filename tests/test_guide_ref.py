@@ -2,17 +2,16 @@
 recorded from the reference's own flow_sampler by tools/make_guide_goldens.py, it reproduces every final mask under the recorded
 seed, every candidate mask and every edge map; where scipy imports, the candidates also equal a direct scipy computation.  The
 deterministic elimination rule gives a set with no two survivors in one box and an earlier survivor in the box of everything
-removed.  Then the C surface: include/diffcodec_guide_hip.h, lib.GUIDE_SIGNATURES and the built library agree, argument kinds
-included; the three older headers and tables carry none of the new names; the refusals return -1 before any launch; and a
-census: every launcher has a literal lib.call in tests/test_gpu_guide_points.py or in diffcodec_amd/guide_points.py."""
-import ast
+removed.  Then what is specific to the guide family's C surface (include/diffcodec_guide_hip.h, lib.GUIDE_SIGNATURES;
+tests/test_abi.py holds the pair to its header and to the built library): its name set; the refusals return -1 before any launch;
+and a census: every launcher has a literal lib.call in tests/test_gpu_guide_points.py or in diffcodec_amd/guide_points.py."""
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import abi_check as A
 import guide_ref as G
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -159,86 +158,33 @@ def test_python_surface_rules_need_no_gpu(monkeypatch):
 
 
 # ------------------------------------------------------------------------------------------------ the C surface
-def _symbols(header):
-    src = open(os.path.join(ROOT, "include", header)).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return src, sorted(set(re.findall(r"\b(dc_[a-z0-9_]+)\s*\(", src)))
-
-
-def _arg_kinds(src, name):
-    """'p' for a pointer parameter, else the scalar type's last word"""
-    decl = re.search(r"\b(?:int|long long)\s+" + name + r"\s*\((.*?)\)\s*;", src, flags=re.S).group(1)
-    args = [" ".join(x.split()) for x in decl.split(",")]
-    return [] if args == ["void"] else ["p" if "*" in a else a.split()[-2] for a in args]
-
-
 @pytest.fixture(scope="module")
 def lib():
-    import __graft_entry__ as g
-    from diffcodec_amd import lib as l
-    if not os.path.exists(l.LIB_PATH):
-        g.build()
-    return l
+    return A.built_lib()
 
 
-def test_guide_header_is_what_the_binding_binds():
+def test_guide_names():
     from diffcodec_amd import lib
-    src, hdr = _symbols("diffcodec_guide_hip.h")
-    assert sorted(lib.GUIDE_SIGNATURES) == hdr, set(hdr) ^ set(lib.GUIDE_SIGNATURES)
-    assert all(n.startswith("dc_guide_") for n in hdr) and set(hdr) == STAGES | {"dc_guide_watershed", "dc_guide_ws_bytes"}
-    kind = {lib.vp: "p", lib.i32: "int", lib.i64: "long", lib.f32: "float", lib.f64: "double"}
-    for name, args in lib.GUIDE_SIGNATURES.items():
-        got = [kind.get(a, "p") for a in args]
-        assert got == _arg_kinds(src, name), (name, got, _arg_kinds(src, name))
-
-
-def test_older_headers_and_tables_carry_none_of_the_new_names():
-    from diffcodec_amd import lib
-    new = set(lib.GUIDE_SIGNATURES)
-    for header in ("diffcodec_hip.h", "diffcodec_flow_hip.h", "diffcodec_loss_hip.h"):
-        names = _symbols(header)[1]
-        assert not new & set(names) and not [n for n in names if n.startswith("dc_guide_")], header
-    for table in (lib.SIGNATURES, lib.FLOW_SIGNATURES, lib.LOSS_SIGNATURES):
-        assert not new & set(table) and not [n for n in table if n.startswith("dc_guide_")]
-
-
-def test_library_exports_the_guide_symbols(lib):
-    l = lib.load()
-    for name, args in lib.GUIDE_SIGNATURES.items():
-        assert hasattr(l, name) and getattr(l, name).argtypes == args, name
-    assert l.dc_guide_ws_bytes.restype is lib.c_longlong
-
-
-def _lib_calls(source):
-    """C names that are the literal first argument of a `lib.call(...)` expression (from the syntax tree)"""
-    names = set()
-    for node in ast.walk(ast.parse(source)):
-        if isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr == "call" and \
-                isinstance(node.func.value, ast.Name) and node.func.value.id == "lib" and node.args and \
-                isinstance(node.args[0], ast.Constant) and isinstance(node.args[0].value, str):
-            names.add(node.args[0].value)
-    return names
+    names = set(lib.GUIDE_SIGNATURES)
+    assert all(n.startswith("dc_guide_") for n in names) and names == STAGES | {"dc_guide_watershed", "dc_guide_ws_bytes"}
+    assert set(QUERIES) <= names
 
 
 def census(signatures):
     """-> (launchers with no literal lib.call in tests/test_gpu_guide_points.py or guide_points.py, queries guide_points.py never asks)"""
     from diffcodec_amd import guide_points
-    tests = open(os.path.join(ROOT, "tests", "test_gpu_guide_points.py")).read()
-    product = open(guide_points.__file__).read()
-    called = _lib_calls(tests) | _lib_calls(product)
-    uncalled = sorted(set(signatures) - set(QUERIES) - called)
-    unnamed = sorted(q for q in QUERIES if q in signatures and (q + "(") not in product)
-    return uncalled, unnamed, _lib_calls(tests), _lib_calls(product)
+    return A.family_census(signatures, QUERIES, A.module_source("test_gpu_guide_points"), open(guide_points.__file__).read())
 
 
 def test_every_launcher_is_called_by_the_gpu_tests_or_by_the_product():
-    from diffcodec_amd import lib
-    uncalled, unnamed, tests, product = census(lib.GUIDE_SIGNATURES)
+    from diffcodec_amd import guide_points, lib
+    uncalled, unnamed = census(lib.GUIDE_SIGNATURES)
     assert not uncalled, f"no literal lib.call in tests/test_gpu_guide_points.py or guide_points.py: {uncalled}"
     assert not unnamed, f"guide_points.py never asks: {unnamed}"
     assert census(dict(lib.GUIDE_SIGNATURES, dc_guide_imaginary=[]))[0] == ["dc_guide_imaginary"]
+    tests = A.lib_calls(A.module_source("test_gpu_guide_points"))
     assert STAGES <= tests, STAGES - tests                                    # the per-stage entries are what the edge tests call
-    assert "dc_guide_watershed" in product
+    assert "dc_guide_watershed" in A.lib_calls(open(guide_points.__file__).read())
 
 
 def test_launchers_refuse_before_any_launch(lib):

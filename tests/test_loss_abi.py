@@ -1,85 +1,29 @@
-"""CPU: include/diffcodec_loss_hip.h, lib.LOSS_SIGNATURES and the built library agree, argument kinds included; the first two
-headers and tables carry none of the new names; the size queries refuse what the launchers refuse; and a census: every launcher
-of LOSS_SIGNATURES has a literal lib.call in tests/test_gpu_losses.py or in diffcodec_amd/losses.py."""
-import ast
-import os
-import re
-
+"""CPU: what is specific to the loss family (include/diffcodec_loss_hip.h, lib.LOSS_SIGNATURES; tests/test_abi.py holds the pair to
+its header and to the built library, and keeps the families disjoint): its name set; the size queries refuse what the launchers
+refuse; and a census: every launcher of LOSS_SIGNATURES has a literal lib.call in tests/test_gpu_losses.py or in
+diffcodec_amd/losses.py."""
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import abi_check as A
+
 QUERIES = ("dc_lpips_dgrad_weight_floats", "dc_lpips_keep_ws_bytes", "dc_lpips_train_ws_bytes", "dc_sobel_edge_ws_bytes")
-
-
-def _symbols(header):
-    src = open(os.path.join(ROOT, "include", header)).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return src, sorted(set(re.findall(r"\b(dc_[a-z0-9_]+)\s*\(", src)))
-
-
-def _arg_kinds(src, name):
-    """'p' for a pointer parameter, else the scalar type's last word; [] for (void)"""
-    decl = re.search(r"\b(?:int|long long)\s+" + name + r"\s*\((.*?)\)\s*;", src, flags=re.S).group(1)
-    args = [" ".join(x.split()) for x in decl.split(",")]
-    return [] if args == ["void"] else ["p" if "*" in a else a.split()[-2] for a in args]
 
 
 @pytest.fixture(scope="module")
 def lib():
-    import __graft_entry__ as g
-    from diffcodec_amd import lib as l
-    if not os.path.exists(l.LIB_PATH):
-        g.build()
-    return l
+    return A.built_lib()
 
 
-def test_loss_header_is_what_the_binding_binds():
+def test_loss_names():
     from diffcodec_amd import lib
-    src, hdr = _symbols("diffcodec_loss_hip.h")
-    assert sorted(lib.LOSS_SIGNATURES) == hdr, set(hdr) ^ set(lib.LOSS_SIGNATURES)
-    assert all(n.startswith(("dc_lpips_", "dc_sobel_")) for n in hdr) and len(hdr) == 12
-    kind = {lib.vp: "p", lib.i32: "int", lib.i64: "long", lib.f32: "float", lib.f64: "double"}
-    for name, args in lib.LOSS_SIGNATURES.items():
-        got = [kind.get(a, "p") for a in args]                       # POINTER(...) types are pointers
-        assert got == _arg_kinds(src, name), (name, got, _arg_kinds(src, name))
-
-
-def test_first_two_headers_and_tables_carry_none_of_the_new_names():
-    from diffcodec_amd import lib
-    new = set(lib.LOSS_SIGNATURES)
-    for header in ("diffcodec_hip.h", "diffcodec_flow_hip.h"):
-        assert not new & set(_symbols(header)[1]), header
-    assert not new & set(lib.SIGNATURES) and not new & set(lib.FLOW_SIGNATURES)
-
-
-def test_library_exports_the_loss_symbols(lib):
-    l = lib.load()
-    for name, args in lib.LOSS_SIGNATURES.items():
-        assert hasattr(l, name) and getattr(l, name).argtypes == args, name
-    for name in QUERIES:
-        assert name in lib.LOSS_SIGNATURES
-
-
-def _lib_calls(source):
-    """C names that are the literal first argument of a `lib.call(...)` expression (from the syntax tree)"""
-    names = set()
-    for node in ast.walk(ast.parse(source)):
-        if isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr == "call" and \
-                isinstance(node.func.value, ast.Name) and node.func.value.id == "lib" and node.args and \
-                isinstance(node.args[0], ast.Constant) and isinstance(node.args[0].value, str):
-            names.add(node.args[0].value)
-    return names
+    assert all(n.startswith(("dc_lpips_", "dc_sobel_")) for n in lib.LOSS_SIGNATURES) and len(lib.LOSS_SIGNATURES) == 12
+    assert set(QUERIES) <= set(lib.LOSS_SIGNATURES)
 
 
 def census(signatures):
     """-> (launchers with no literal lib.call in tests/test_gpu_losses.py or losses.py, queries losses.py never asks)"""
     from diffcodec_amd import losses
-    tests = open(os.path.join(ROOT, "tests", "test_gpu_losses.py")).read()
-    product = open(losses.__file__).read()
-    called = _lib_calls(tests) | _lib_calls(product)
-    uncalled = sorted(set(signatures) - set(QUERIES) - called)
-    unnamed = sorted(q for q in QUERIES if q in signatures and (q + "(") not in product)
-    return uncalled, unnamed
+    return A.family_census(signatures, QUERIES, A.module_source("test_gpu_losses"), open(losses.__file__).read())
 
 
 def test_every_launcher_is_called_by_the_gpu_tests_or_by_the_product():
@@ -90,7 +34,7 @@ def test_every_launcher_is_called_by_the_gpu_tests_or_by_the_product():
     uncalled, _ = census(dict(lib.LOSS_SIGNATURES, dc_lpips_imaginary=[]))
     assert uncalled == ["dc_lpips_imaginary"]
     stages = {"dc_lpips_tail_grad", "dc_lpips_conv_dgrad", "dc_lpips_pool_grad", "dc_lpips_conv1_dgrad"}
-    tests = _lib_calls(open(os.path.join(ROOT, "tests", "test_gpu_losses.py")).read())
+    tests = A.lib_calls(A.module_source("test_gpu_losses"))
     assert stages <= tests, stages - tests                            # the per-stage entries are what the edge tests call
 
 

@@ -1,101 +1,48 @@
-"""CPU: include/diffcodec_train_hip.h, lib.TRAIN_SIGNATURES and the built library agree, argument kinds included; the four older
-headers and tables carry none of the new names; every launcher has a literal lib.call in tests/test_gpu_conv_grad.py or in
-diffcodec_amd/train.py; the size query refuses bad shapes and grows as its header says; the routing: the production layers take the
-MFMA form for both gradients, the query refuses what the launch refuses, and the case table of tests/conv_grad_ref.py reaches every
-instance the route can choose at batch 2 and at batch 3; and the module surface of diffcodec_amd.train."""
-import ast
+"""CPU: what is specific to the train family (include/diffcodec_train_hip.h, lib.TRAIN_SIGNATURES; tests/test_abi.py holds the pair
+to its header and to the built library, and keeps the five names out of the other families): its name set; every launcher has a
+literal lib.call in tests/test_gpu_conv_grad.py or in diffcodec_amd/train.py; the size query refuses bad shapes and grows as its
+header says; the routing: the production layers take the MFMA form for both gradients, the query refuses what the launch refuses,
+and the case table of tests/conv_grad_ref.py reaches every instance the route can choose at batch 2 and at batch 3; and the module
+surface of diffcodec_amd.train."""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
 
+import abi_check as A
 import conv_grad_ref as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("dc_silu_grad_f32", "dc_conv3x3_f32_dgrad", "dc_conv3x3_f32_wgrad", "dc_conv3x3_f32_wgrad_ws_bytes", "dc_conv3x3_f32_grad_route")
 QUERIES = ("dc_conv3x3_f32_wgrad_ws_bytes", "dc_conv3x3_f32_grad_route")
-OLDER = {"diffcodec_hip.h": "SIGNATURES", "diffcodec_flow_hip.h": "FLOW_SIGNATURES", "diffcodec_loss_hip.h": "LOSS_SIGNATURES",
-         "diffcodec_guide_hip.h": "GUIDE_SIGNATURES"}
-
-
-def _symbols(header):
-    src = open(os.path.join(ROOT, "include", header)).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return src, sorted(set(re.findall(r"\b(dc_[a-z0-9_]+)\s*\(", src)))
-
-
-def _arg_kinds(src, name):
-    """'p' for a pointer parameter, else the scalar type's last word; [] for (void)"""
-    decl = re.search(r"\b(?:int|long long)\s+" + name + r"\s*\((.*?)\)\s*;", src, flags=re.S).group(1)
-    args = [" ".join(x.split()) for x in decl.split(",")]
-    return [] if args == ["void"] else ["p" if "*" in a else a.split()[-2] for a in args]
 
 
 @pytest.fixture(scope="module")
 def lib():
-    import __graft_entry__ as g
-    from diffcodec_amd import lib as l
-    if not os.path.exists(l.LIB_PATH):
-        g.build()
-    return l
+    return A.built_lib()
 
 
-# ------------------------------------------------------------------------------------------ ABI
-def test_train_header_is_what_the_binding_binds():
+# ------------------------------------------------------------------------------------------ names and census
+def test_train_names():
     from diffcodec_amd import lib
-    src, hdr = _symbols("diffcodec_train_hip.h")
-    assert sorted(lib.TRAIN_SIGNATURES) == hdr == sorted(NAMES), set(hdr) ^ set(lib.TRAIN_SIGNATURES)
-    kind = {lib.vp: "p", lib.i32: "int", lib.i64: "long", lib.f32: "float", lib.f64: "double"}
-    for name, args in lib.TRAIN_SIGNATURES.items():
-        got = [kind.get(a, "p") for a in args]                       # POINTER(...) types are pointers
-        assert got == _arg_kinds(src, name), (name, got, _arg_kinds(src, name))
-
-
-def test_older_headers_and_tables_carry_none_of_the_new_names():
-    from diffcodec_amd import lib
-    for header, table in OLDER.items():
-        assert not set(NAMES) & set(_symbols(header)[1]), header
-        assert not set(NAMES) & set(getattr(lib, table)), table
-
-
-def test_library_exports_the_train_symbols(lib):
-    l = lib.load()
-    for name, args in lib.TRAIN_SIGNATURES.items():
-        fn = getattr(l, name)
-        assert fn.argtypes == args, name
-        assert fn.restype == (ctypes.c_longlong if name.endswith("_ws_bytes") else ctypes.c_int), name
-
-
-def _lib_calls(source):
-    """C names that are the literal first argument of a `lib.call(...)` expression (from the syntax tree)"""
-    names = set()
-    for node in ast.walk(ast.parse(source)):
-        if isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr == "call" and \
-                isinstance(node.func.value, ast.Name) and node.func.value.id == "lib" and node.args and \
-                isinstance(node.args[0], ast.Constant) and isinstance(node.args[0].value, str):
-            names.add(node.args[0].value)
-    return names
+    assert sorted(lib.TRAIN_SIGNATURES) == sorted(NAMES) and set(QUERIES) <= set(NAMES)
 
 
 def census(signatures):
     """-> (launchers with no literal lib.call in tests/test_gpu_conv_grad.py or train.py, queries train.py never asks)"""
     from diffcodec_amd import train
-    tests = open(os.path.join(ROOT, "tests", "test_gpu_conv_grad.py")).read()
-    product = open(train.__file__).read()
-    called = _lib_calls(tests) | _lib_calls(product)
-    uncalled = sorted(set(signatures) - set(QUERIES) - called)
-    unnamed = sorted(q for q in QUERIES if q in signatures and (q + "(") not in product)
-    return uncalled, unnamed
+    return A.family_census(signatures, QUERIES, A.module_source("test_gpu_conv_grad"), open(train.__file__).read())
 
 
 def test_every_launcher_is_called_by_the_gpu_tests_or_by_the_product():
     from diffcodec_amd import lib
     assert census(lib.TRAIN_SIGNATURES) == ([], [])
     assert census(dict(lib.TRAIN_SIGNATURES, dc_conv3x3_imaginary=[]))[0] == ["dc_conv3x3_imaginary"]
-    tests = _lib_calls(open(os.path.join(ROOT, "tests", "test_gpu_conv_grad.py")).read())
+    tests = A.lib_calls(A.module_source("test_gpu_conv_grad"))
     assert set(NAMES) - set(QUERIES) <= tests                         # the edge tests call every launcher by hand
+    from diffcodec_amd import train
+    product = open(train.__file__).read()                             # the route is asked through lib.query, the size by its C name
+    assert A.lib_calls(product, "query") == {"dc_conv3x3_f32_grad_route"} and "dc_conv3x3_f32_wgrad_ws_bytes(" in product
+    assert A.family_census(lib.TRAIN_SIGNATURES, QUERIES, "", "lib.call('dc_conv3x3_f32_grad_route')")[1] == sorted(QUERIES)
 
 
 # ------------------------------------------------------------------------------------------ the size query
