@@ -162,6 +162,13 @@ TRAIN_SIGNATURES = {
     "dc_conv3x3_f32_grad_route": [i32, i32, i32, i32, i32, i32, i32, POINTER(i32)],
 }
 
+# name -> argtypes of include/diffcodec_pyramid_hip.h (csrc/pyramid_grad.hip)
+PYRAMID_SIGNATURES = {
+    "dc_pyramid_exp_f32": [vp, vp, i64, vp],
+    "dc_pyramid_fuse_grad_f32": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
+    "dc_pyramid_warp_grad_f32": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
+}
+
 # the whole C surface: (header under include/, its table), one pair per launcher family.  load() binds what is listed here and
 # tests/test_abi.py holds every pair to its header; a new family adds a header, a table and one line here.
 ABI = (
@@ -170,6 +177,7 @@ ABI = (
     ("diffcodec_loss_hip.h", LOSS_SIGNATURES),
     ("diffcodec_guide_hip.h", GUIDE_SIGNATURES),
     ("diffcodec_train_hip.h", TRAIN_SIGNATURES),
+    ("diffcodec_pyramid_hip.h", PYRAMID_SIGNATURES),
 )
 
 
