@@ -393,7 +393,62 @@ int splitk_fixpoint(int splitk, int units)
     }
 }
 
-// Descriptor checks, normalisation (split-K fixpoint, row_add_stride) and kernel choice: the one routing function of
+int conv_route(const dc_conv_desc& in, dc_conv_desc& d, dc_route& r);
+
+// The smallest divisor s of `units` (at most 20, at least 8 of the `kt` K steps per split) with tiles * s >= target workgroups; the
+// largest such divisor when none reaches the target.  An even partition is preferred, so the split is a divisor of `units`.
+int splitk_smallest_divisor(long long tiles, int units, int kt, int target)
+{
+    int last = 1;
+    for (int s = 1; s <= units && s <= 20; ++s) {
+        if (units % s || kt / s < 8) continue;
+        if (tiles * s >= target) return s;
+        last = s;
+    }
+    return last;
+}
+
+// The split-K the library picks for dc_conv_desc.splitk = DC_SPLITK_AUTO.  Split the K loop over workgroups when the output has
+// too few tiles to fill 256 CUs and K is long (the weight-streaming layers at 8x8 / 16x16).  Each split stores its partial tile
+// into its own fp32 slab and a finish pass sums the slabs (M*Cout*4 bytes written and read once per split: cheap next to the
+// weight stream, and deterministic).
+int splitk_pick(const dc_conv_desc& d)
+{
+    // the folded LayerNorm / row statistics and GEGLU live in the unsplit bf16 epilogue; a Cout that is no multiple of 16 runs on
+    // the halo-tile kernel unsplit only (conv_route refuses every other split of it)
+    if (d.ln_stats || d.stats_out || d.epilogue == 1 || (d.Cout & 15)) return 1;
+    const long long m = (long long)d.N * d.Ho * d.Wo;
+    const int nkc = (d.C1 + d.C2) >> 6, kt = (d.ksize == 3 ? 9 : 1) * nkc;
+    const int bn = dc_n_tile(d);
+    const long long tiles = ((m + 63) / 64) * ((d.Cout + bn - 1) / bn);
+    // The stride-2 Downsample2D convs (gather GEMM, 64-row tiles): measured per shape (tools/experiments/bench_down.py, model batches
+    // 32 and 2) the best split is the smallest divisor of the K steps that yields ~1024 workgroups with at least 8 steps each —
+    // 1 / 2 / 4 at the three levels of a 16-frame step (the general rule gave 1 / 1 / 3: 136 -> 109 us at 32x32x640), 5 at the top
+    // level of a one-frame decode (53 -> 25 us), which the general rule leaves unsplit because its K loop is short.
+    if (d.ksize == 3 && d.stride == 2) return splitk_smallest_divisor(tiles, kt, kt, 1024);
+    // what the launched kernel partitions: 64-channel chunks for the halo-tile 3x3 kernel, 64-wide K steps otherwise
+    bool tile3 = false;
+    if (d.ksize == 3 && d.stride == 1) {
+        dc_conv_desc q = d, n;
+        dc_route r;
+        q.splitk = 1;
+        q.gn_part_out = nullptr;
+        tile3 = conv_route(q, n, r) == DC_OK && r.kernel == DC_ROUTE_CONV3X3_TILE;
+    }
+    // (per-shape sweep of every decode shape at model batches 32 and 2, round 3: short K loops are split only at tiny m, where
+    // nothing else fills the chip; a 1x1 launch with >= 2048 rows needs >= 128 K steps before a split pays)
+    if (tiles >= 512 || (kt < 64 && (m >= 2048 || kt < 32)) || (!tile3 && m >= 2048 && kt < 128)) return 1;
+    int target = m >= 2048 ? 1024 : 256;     // measured (tools/bench_splitk.py): ~1 workgroup per CU at small m, 2+ above
+    // 32x32 and 64x64 maps of a one- or two-frame decode (the halo-tile kernel's own pixel tiles already give 64-256 workgroups):
+    // one workgroup per CU, not four (38 -> 26 us at 2x32x32x640)
+    if (tile3 && (long long)d.Ho * d.Wo >= 1024) target = 256;
+    return splitk_smallest_divisor(tiles, tile3 ? nkc : kt, kt, target);
+}
+
+// dc_conv_desc.splitk as the caller means it: DC_SPLITK_AUTO is the library's pick, any other value below 1 is 1
+int splitk_asked(const dc_conv_desc& d) { return d.splitk == DC_SPLITK_AUTO ? splitk_pick(d) : d.splitk < 1 ? 1 : d.splitk; }
+
+// Descriptor checks, normalisation (split-K pick and fixpoint, row_add_stride) and kernel choice: the one routing function of
 // dc_conv_igemm_bf16, dc_conv_route, dc_conv_instance and dc_conv_gn_part_chunks.  `d` receives the normalised descriptor the kernels
 // are launched with.  Each family is asked once, in priority order: the 1x1 GEMMs, the halo-tile 3x3 kernel, the gather GEMM.
 int conv_route(const dc_conv_desc& in, dc_conv_desc& d, dc_route& r)
@@ -416,7 +471,7 @@ int conv_route(const dc_conv_desc& in, dc_conv_desc& d, dc_route& r)
     }
     if (d.gn_ab && d.gn_batch <= 0) return DC_ERR_INVALID;
     if (d.act < 0 || d.act > 2) return DC_ERR_INVALID;
-    if (d.splitk < 1) d.splitk = 1;
+    d.splitk = splitk_asked(d);                                         // from here on an ordinary explicit request
     if (d.row_add_stride == 0) d.row_add_stride = d.Cout;
     if (d.epilogue == 1 && (d.splitk > 1 || (d.Cout & 31) || d.residual || d.row_add || d.out_f32)) return DC_ERR_INVALID;
     const int asked = d.splitk, nkc = Cin >> 6;
@@ -441,9 +496,11 @@ int conv_route(const dc_conv_desc& in, dc_conv_desc& d, dc_route& r)
 
 extern "C" int dc_conv_gn_part_chunks(const dc_conv_desc* dp)
 {
-    if (!dp || dp->splitk > 1) return 0;
+    if (!dp) return 0;
     // the launch decision must be the one dc_conv_igemm_bf16 takes with gn_part_out set (the host sizes the buffer from here)
     dc_conv_desc q = *dp, d;
+    q.splitk = splitk_asked(q);
+    if (q.splitk > 1) return 0;
     if (!q.gn_part_out) q.gn_part_out = (float*)(uintptr_t)16;
     dc_route r;
     return conv_route(q, d, r) == DC_OK ? r.gn_chunks : 0;
@@ -451,8 +508,9 @@ extern "C" int dc_conv_gn_part_chunks(const dc_conv_desc* dp)
 
 extern "C" long long dc_conv_igemm_ws_bytes(const dc_conv_desc* d)
 {
-    if (!d || d->splitk <= 1) return 0;
-    return (long long)d->N * d->Ho * d->Wo * d->Cout * 4 * d->splitk;
+    if (!d) return 0;
+    const int splitk = splitk_asked(*d);
+    return splitk > 1 ? (long long)d->N * d->Ho * d->Wo * d->Cout * 4 * splitk : 0;
 }
 
 extern "C" int dc_conv_route(const dc_conv_desc* dp, int* info)

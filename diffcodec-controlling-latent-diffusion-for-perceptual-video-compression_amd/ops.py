@@ -4,7 +4,7 @@ Activations are NHWC bf16 tensors of shape [N,H,W,C] (a [B,L,C] token sequence i
 No arithmetic happens in torch on this path; every function below ends in exactly one or more `lib.call`s."""
 import collections
 import ctypes
-import math
+import functools
 
 import torch
 
@@ -118,44 +118,6 @@ class PackedConvF32:
 
 
 # ------------------------------------------------------------------------------------------ conv / linear
-def _pick_splitk(m, cout, kt, units=None, rows_per_image=0):
-    """Split the K loop over workgroups when the output has too few tiles to fill 256 CUs and K is long (the
-    weight-streaming layers at 8x8 / 16x16).  Each split stores its partial tile into its own fp32 slab and a finish
-    pass sums the slabs (m*cout*4 bytes written and read once per split: cheap next to the weight stream, and
-    deterministic).  `units` = what the launched kernel partitions (64-channel chunks for the halo-tile 3x3 kernel,
-    64-wide K steps otherwise); an even partition is preferred, so the split is a divisor of `units`."""
-    tile3 = units is not None
-    units = kt if units is None else units
-    bn = 160 if cout % 160 == 0 else 128
-    tiles = math.ceil(m / 64) * math.ceil(cout / bn)
-    # (per-shape sweep of every decode shape at model batches 32 and 2, round 3: short K loops are split only at tiny m, where nothing
-    # else fills the chip; a 1x1 launch with >= 2048 rows needs >= 128 K steps before a split pays)
-    if tiles >= 512 or (kt < 64 and (m >= 2048 or kt < 32)) or (not tile3 and m >= 2048 and kt < 128):
-        return 1
-    divs = [s for s in range(1, min(units, 20) + 1) if units % s == 0 and kt // s >= 8]
-    target = 1024 if m >= 2048 else 256      # measured (tools/bench_splitk.py): ~1 workgroup per CU at small m, 2+ above
-    if tile3 and rows_per_image >= 1024:     # 32x32 and 64x64 maps of a one- or two-frame decode (the halo-tile kernel's own pixel tiles
-        target = 256                         # already give 64-256 workgroups): one workgroup per CU, not four (38 -> 26 us at 2x32x32x640)
-    for s in divs:
-        if tiles * s >= target:
-            return s
-    return divs[-1] if divs else 1
-
-
-def _pick_splitk_strided(m, cout, kt):
-    """The stride-2 Downsample2D convs (gather GEMM, 64-row tiles): measured per shape (tools/ab/bench_down.py, model batches 32 and 2) the
-    best split is the smallest divisor of the K steps that yields ~1024 workgroups with at least 8 steps each — 1 / 2 / 4 at the three
-    levels of a 16-frame step (the general rule gave 1 / 1 / 3: 136 -> 109 us at 32x32x640), 5 at the top level of a one-frame decode
-    (53 -> 25 us), which the general rule leaves unsplit because its K loop is short."""
-    bn = 160 if cout % 160 == 0 else 128
-    tiles = math.ceil(m / 64) * math.ceil(cout / bn)
-    divs = [s for s in range(1, min(kt, 20) + 1) if kt % s == 0 and kt // s >= 8]
-    for s in divs:
-        if tiles * s >= 1024:
-            return s
-    return divs[-1] if divs else 1
-
-
 def row_stats_parts(cout):
     """Partials per row written by a 1x1 / linear launch with `stats_out` (dc_gemm_row_stats_parts)."""
     return lib.load().dc_gemm_row_stats_parts(int(cout))
@@ -183,6 +145,7 @@ def ln_finalize(partials, c, eps):
     return mr
 
 
+DC_SPLITK_AUTO = -1                         # dc_conv_desc.splitk: the library picks (include/diffcodec_hip.h)
 ROUTE_NAMES = {1: "gemm_dma", 2: "gemm_wide", 3: "gemm_p8", 4: "gemm_rowpanel", 5: "conv3x3_tile", 6: "igemm"}
 
 
@@ -216,11 +179,14 @@ def conv_instance(d):
     return dict(zip(INSTANCE_ARGS[kernel], info[1:]), kernel=kernel)
 
 
+@functools.lru_cache(maxsize=None)
 def rowpanel_takes(rows, rows_per_sample, cin, cout):
-    """Mirror of dc_gemm_rowpanel_route (csrc/gemm_rowpanel.hip) for plain / residual / folded-LN 1x1 launches: the K = 320 kernel that
-    keeps a 256-row panel in registers — the only GEMM of the family that can apply a GroupNorm affine on load (`gn_ab` without SiLU).
-    The C side stays the authority: a launch this rule admits and the library does not take fails with DC_ERR_INVALID."""
-    return cin == 320 and cout >= 320 and cout % 64 == 0 and rows >= 65536 and rows % 256 == 0 and rows_per_sample % 256 == 0
+    """Does a 1x1 launch with a bias and a GroupNorm affine on load (`gn_ab` without SiLU) go to the row-panel kernel (the K = 320
+    kernel that keeps a 256-row panel in registers, the only GEMM of the family that can apply the affine)?  The library's route
+    of a placeholder descriptor of that shape, remembered per shape."""
+    d = ConvDesc(x1=16, w=16, out=16, bias=16, gn_ab=16, N=rows // rows_per_sample, H=1, W=rows_per_sample, C1=cin, Cout=cout, ksize=1,
+                 stride=1, Ho=1, Wo=rows_per_sample, out_scale=1.0, splitk=1, gn_batch=rows // rows_per_sample)
+    return conv_route(d).kernel == "gemm_rowpanel"
 
 
 def conv(x1, pc, *, x2=None, gn_ab=None, gn_silu=False, row_add=None, residual=None, stride=1, pad=1,
@@ -274,7 +240,6 @@ def conv(x1, pc, *, x2=None, gn_ab=None, gn_silu=False, row_add=None, residual=N
         assert out.is_contiguous() and out.numel() == n * ho * wo * cout_eff and out.dtype == (F32 if out_f32 else BF16)
         out = out.view(n, ho, wo, cout_eff)
     m = n * ho * wo
-    kt = (9 if k == 3 else 1) * (pc.cin // 64)
     ln_parts, ln_eps, ln_scratch = 0, 0.0, None
     if ln_partials is not None:
         if ln_stats is not None:
@@ -285,6 +250,8 @@ def conv(x1, pc, *, x2=None, gn_ab=None, gn_silu=False, row_add=None, residual=N
         ln_parts = int(ln_stats.shape[1])
     if ln_stats is not None or stats_out is not None:
         splitk = 1                          # the folded LayerNorm / row statistics live in the unsplit bf16 epilogue
+    elif pc.geglu and splitk is None:
+        splitk = 1                          # ... and so does GEGLU
     if gn_ab is not None:
         _chk(gn_ab, F32, "gn_ab")
         assert gn_ab.shape[1] == pc.cin
@@ -307,21 +274,18 @@ def conv(x1, pc, *, x2=None, gn_ab=None, gn_silu=False, row_add=None, residual=N
                  row_add=_ptr(row_add), residual=_ptr(residual), out=out.data_ptr(), splitk_ws=0,
                  N=n, H=h, W=w, C1=c1, C2=c2, Cout=pc.cout, ksize=k, stride=stride, pad=int(pad), upsample=int(upsample),
                  Ho=ho, Wo=wo, gn_silu=int(gn_silu), epilogue=1 if pc.geglu else 0, out_f32=int(out_f32),
-                 out_scale=float(out_scale), splitk=int(splitk or 1), gn_batch=0 if gn_ab is None else gn_ab.shape[0],
-                 act=int(act), row_add_stride=int(ras), ln_stats=_ptr(ln_stats), ln_colsum=_ptr(pc.colsum if ln_stats is not None else None),
+                 out_scale=float(out_scale), splitk=DC_SPLITK_AUTO if splitk is None else int(splitk or 1),
+                 gn_batch=0 if gn_ab is None else gn_ab.shape[0], act=int(act), row_add_stride=int(ras), ln_stats=_ptr(ln_stats), ln_colsum=_ptr(pc.colsum if ln_stats is not None else None),
                  stats_out=_ptr(stats_out), gn_part_out=0, ln_parts=ln_parts, ln_eps=float(ln_eps), ln_scratch=_ptr(ln_scratch))
-    if splitk is None:
-        if k == 3 and stride == 2 and not pc.geglu:
-            splitk = _pick_splitk_strided(m, pc.cout, kt)
-        elif pc.geglu:
-            splitk = 1
-        else:                               # the halo-tile 3x3 kernel splits 64-channel chunks, the others 64-wide K steps
-            tile3 = k == 3 and stride == 1 and conv_route(d).kernel == "conv3x3_tile"
-            splitk = _pick_splitk(m, pc.cout, kt, pc.cin // 64 if tile3 else None, rows_per_image=ho * wo)
-        d.splitk = int(splitk)
+    route = None                            # the library's decision for `d`, while `d` is as it was asked
+    if splitk is None:                      # the library picks the split (csrc/igemm.hip: splitk_pick); from here on it is explicit
+        route = conv_route(d)
+        d.splitk = splitk = route.splitk
     ws = _scratch((splitk, m, pc.cout), x1.device, "splitk") if splitk > 1 else None
     d.splitk_ws = _ptr(ws)
-    if ln_parts > 0 and conv_route(d).ln_first:
+    if ln_parts > 0 and route is None:
+        route = conv_route(d)
+    if ln_parts > 0 and route.ln_first:
         # scratch for (mean, rstd) only where the dispatcher runs the finalize pass first (the row-panel kernel finalizes in its
         # prologue): the library's own routing decides, not a Python restatement of it
         ln_scratch = _scratch((m, 2), x1.device, "ln_scratch")
@@ -332,10 +296,11 @@ def conv(x1, pc, *, x2=None, gn_ab=None, gn_silu=False, row_add=None, residual=N
         if chunks > 0:
             part = _scratch((chunks, n, pc.cout, 2), x1.device, "gn_part")
             d.gn_part_out = part.data_ptr()
+            route = None                    # (asked without the statistics epilogue)
     meta = None
     if lib.TIMER is not None:
         kk = pc.cin * k * k
-        kernel = conv_route(d).kernel
+        kernel = (conv_route(d) if route is None else route).kernel
         if kernel == "conv3x3_tile":
             fam = "conv3x3_tile_kernel (3x3 stride-1 halo-tile conv)"
         elif kernel == "igemm":

@@ -146,7 +146,8 @@ typedef struct dc_conv_desc {
     int epilogue;           /* 0: linear; 1: GEGLU (weights/bias rows pre-interleaved 16 hid | 16 gate) */
     int out_f32;
     float out_scale;
-    int splitk;             /* >= 1 */
+    int splitk;             /* >= 1: an explicit split-K request (shrunk until every split owns K steps); DC_SPLITK_AUTO: the
+                             * library picks, see below; any other value below 1 means 1 (a zeroed descriptor runs unsplit) */
     int gn_batch;           /* rows of gn_ab (sample n uses row n % gn_batch) */
     int act;                /* 0 none, 1 SiLU, 2 quick-GELU x*sigmoid(1.702x) — applied after bias/row_add, before out_scale */
     long long row_add_stride; /* floats between consecutive samples of row_add (0 = Cout) */
@@ -173,6 +174,11 @@ typedef struct dc_conv_desc {
     float ln_eps;
     float* ln_scratch;
 } dc_conv_desc;
+/* dc_conv_desc.splitk = DC_SPLITK_AUTO: the library chooses the split for the launch's shape and kernel (1 wherever the route
+ * accepts no other: ln_stats, stats_out, GEGLU, a Cout that is no multiple of 16).  dc_conv_igemm_bf16, dc_conv_route (info[3] is
+ * the pick), dc_conv_instance, dc_conv_igemm_ws_bytes (the bytes of the pick) and dc_conv_gn_part_chunks (0 when the pick is above
+ * 1) resolve it the same way; a pick above 1 needs splitk_ws as an explicit split does. */
+#define DC_SPLITK_AUTO (-1)
 int dc_conv_igemm_bf16(const dc_conv_desc* desc, void* stream);
 /* The dispatcher's decision for `desc`, without launching anything: the same routing function dc_conv_igemm_bf16 runs.
  * Returns what the launch would return for its descriptor checks (0 or DC_ERR_INVALID; operand checks that do not steer the
@@ -204,7 +210,7 @@ int dc_conv_route(const dc_conv_desc* desc, int* info);
  *   igemm          igemm_kernel<2, 2, TM, TN, KS3, GN>: 3x3 gather, GroupNorm affine on load. */
 #define DC_CONV_INSTANCE_INTS 9
 int dc_conv_instance(const dc_conv_desc* desc, int* info);
-/* Workspace bytes needed for splitk>1 (0 otherwise). */
+/* Workspace bytes needed for splitk>1 (0 otherwise); under DC_SPLITK_AUTO, for the split the library picks. */
 long long dc_conv_igemm_ws_bytes(const dc_conv_desc* desc);
 /* Partials per output row that a 1x1 / linear launch with `stats_out` writes (one per wave column slice of the tile grid). */
 int dc_gemm_row_stats_parts(int Cout);

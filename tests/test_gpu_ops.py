@@ -681,6 +681,69 @@ def test_conv_tile_two_images_per_tile(ops):
     close(from_nhwc(out), ref)
 
 
+# the smallest shapes at which each arm of the split-K rule picks above 1: (n, h, w, cin, cout, k, stride), the kernel the library
+# routes the launch to and the split it picks (csrc/igemm.hip: splitk_pick; tests/splitk_rule_ref.py is the frozen statement)
+AUTO_SPLIT_CASES = [
+    ((1, 8, 8, 2560, 1280, 1, 1), "gemm_dma", 5),              # 1x1, 64 rows: K steps split, target 256 workgroups
+    ((1, 8, 8, 1280, 1280, 3, 1), "conv3x3_tile", 20),         # the halo-tile kernel splits 64-channel chunks
+    ((2, 32, 32, 640, 640, 3, 1), "conv3x3_tile", 2),          # ... and aims at one workgroup per CU on big maps
+    ((1, 32, 32, 640, 640, 3, 2), "igemm", 10),                # the stride-2 rule (no split reaches 1024 workgroups: the largest)
+    ((1, 13, 9, 1280, 128, 3, 1), "igemm", 20),                # ragged map on the gather GEMM: (tap, chunk) steps split
+]
+
+
+def _recording_scratch(ops, monkeypatch):
+    handed, real = [], ops._scratch
+
+    def scratch(shape, device, what):
+        handed.append((what, tuple(shape)))
+        return real(shape, device, what)
+    monkeypatch.setattr(ops, "_scratch", scratch)
+    return handed
+
+
+@pytest.mark.parametrize("shape,kernel,pick", AUTO_SPLIT_CASES)
+def test_conv_split_picked_by_the_library_is_the_frozen_rule_s_launch(ops, monkeypatch, shape, kernel, pick):
+    """ops.conv(splitk=None) (DC_SPLITK_AUTO) against splitk = the frozen rule's value on the same operands: the same slabs are
+    asked for, the outputs are the same bits, and they meet the launch's fp64 reference"""
+    import splitk_rule_ref
+    n, h, w, cin, cout, k, stride = shape
+    g = torch.Generator().manual_seed(19)
+    xd = nhwc(bf(torch.randn(n, cin, h, w, generator=g)))
+    pc = ops.PackedConv(bf(torch.randn(cout, cin, k, k, generator=g) / math.sqrt(cin * k * k)), torch.randn(cout, generator=g) * 0.1, DEV)
+    handed = _recording_scratch(ops, monkeypatch)
+    with capture_routes() as routes:
+        auto = ops.conv(xd, pc, stride=stride)
+    m, rows_per_image = auto.numel() // cout, auto.shape[1] * auto.shape[2]
+    assert [(r.kernel, r.splitk) for r in routes] == [(kernel, pick)], routes
+    assert handed == [("splitk", (pick, m, cout))], handed
+    assert splitk_rule_ref.pick(m, cin, cout, k, stride, rows_per_image, lambda: kernel == "conv3x3_tile") == pick
+    del handed[:]
+    with capture_routes() as routes:
+        asked = ops.conv(xd, pc, stride=stride, splitk=pick)
+    assert [(r.kernel, r.splitk) for r in routes] == [(kernel, pick)] and handed == [("splitk", (pick, m, cout))], (routes, handed)
+    assert torch.equal(auto, asked)
+    _strict(auto, lambda rows: L.conv_ref(xd, pc, rows, stride=stride), spatial=tuple(auto.shape[:3]) if k == 3 else None)
+
+
+def test_unet_conv_out_of_one_small_frame_runs_unsplit(ops, monkeypatch):
+    """UNet conv_out (320 -> 4 on the halo-tile kernel, GroupNorm + SiLU on load, fp32 out) on the 8x8 latents of one frame: the
+    frozen rule picked split 5 there, which the library refuses for a Cout that is no multiple of 16; the library's own pick is 1"""
+    g = torch.Generator().manual_seed(20)
+    n, cin, cout, hw = 1, 320, 4, 8
+    xd = nhwc(bf(torch.randn(n, cin, hw, hw, generator=g)))
+    pc = ops.PackedConv(bf(torch.randn(cout, cin, 3, 3, generator=g) / math.sqrt(cin * 9)), torch.randn(cout, generator=g) * 0.1, DEV,
+                        mfma_small_cout=True)
+    gamma, beta = 1 + 0.1 * torch.randn(cin, generator=g), 0.1 * torch.randn(cin, generator=g)
+    ab = ops.group_norm_ab(xd, gamma.to(DEV), beta.to(DEV), 32, 1e-5)
+    handed = _recording_scratch(ops, monkeypatch)
+    with capture_routes() as routes:
+        auto = ops.conv(xd, pc, gn_ab=ab, gn_silu=True, out_f32=True)
+    assert [(r.kernel, r.splitk) for r in routes] == [("conv3x3_tile", 1)] and not handed, (routes, handed)
+    assert torch.equal(auto, ops.conv(xd, pc, gn_ab=ab, gn_silu=True, out_f32=True, splitk=1))
+    _strict(auto, lambda rows: L.conv_ref(xd, pc, rows, gn_ab=ab, gn_silu=True), spatial=tuple(auto.shape[:3]))
+
+
 # ------------------------------------------------------------------------------------------- input side
 @pytest.mark.parametrize("hw,target", [((270, 480), (512, 512)), ((512, 512), (512, 512)), ((64, 96), (33, 1)), ((1, 7), (5, 9))])
 def test_flow_hw2_resize_scale(ops, hw, target):

@@ -3,6 +3,7 @@ import sys, os, math
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
 from diffcodec_amd import ops
+from diffcodec_amd.lib import ConvDesc
 g = torch.Generator().manual_seed(0)
 shapes = []
 for n in (32, 2):
@@ -33,8 +34,8 @@ for (n, h, cin, cout, k) in shapes:
             pass
     best = min((v, s) for s, v in res.items() if s is not None)
     flag = "  <-- heuristic %.0f%% slower" % (100 * (res[None] / best[0] - 1)) if res[None] > 1.06 * best[0] else ""
-    m = n * h * h; kt = (9 if k == 3 else 1) * (cin // 64)
-    tile3 = k == 3
-    pick = ops._pick_splitk(m, cout, kt, cin // 64 if tile3 else None, rows_per_image=h * h)
+    # the library's own pick for this launch (dc_conv_route on a placeholder descriptor of the shape; host code only)
+    pick = ops.conv_route(ConvDesc(x1=16, w=16, out=16, bias=16, N=n, H=h, W=h, C1=cin, Cout=cout, ksize=k, stride=1, pad=k // 2, Ho=h, Wo=h,
+                                   out_scale=1.0, splitk=ops.DC_SPLITK_AUTO)).splitk
     tab = " ".join(f"{s_}:{v:.0f}" for s_, v in sorted((a, b) for a, b in res.items() if a is not None))
     print(f"n={n} {h}x{h} {cin}->{cout} k{k}: pick {pick} = {res[None]:6.1f} us | best sk={best[1]} {best[0]:6.1f} us{flag} | {tab}", flush=True)
