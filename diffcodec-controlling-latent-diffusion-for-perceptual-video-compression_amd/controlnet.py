@@ -68,6 +68,17 @@ class BiDirFeatureExtractor:
         return outs
 
 
+def _packed_f32_tensors(obj):
+    """every weight and bias tensor of the `PackedConvF32` objects an extractor holds (in attributes, lists, tuples, dicts)"""
+    if isinstance(obj, PackedConvF32):
+        return [t for t in (obj.w, obj.bias) if t is not None]
+    if isinstance(obj, dict):
+        obj = list(obj.values())
+    elif not isinstance(obj, (list, tuple)):
+        obj = list(vars(obj).values()) if hasattr(obj, "__dict__") else []
+    return [t for o in obj for t in _packed_f32_tensors(o)]
+
+
 class HipDualFlowControlNet:
     needs_warp_cond = False                # ResControlNet (flow_resnet.py:58) overrides
 
@@ -92,6 +103,7 @@ class HipDualFlowControlNet:
         self.zero_mid = PackedConv(sd["controlnet_mid_block.weight"], sd["controlnet_mid_block.bias"], device)
         self._ctx_key = None
         self._ctrl_key = None
+        self._extractor_tensors = None         # collected at the first prepare_controls (a subclass adds extractors after this)
         self.gamma_beta = None
 
     def _make_extractor(self, sd, device):
@@ -122,10 +134,16 @@ class HipDualFlowControlNet:
 
     def prepare_controls(self, controlnet_cond, flow_cond, warp_cond=None):
         """Pyramid + FDN gamma/beta (control_utils.py:31-32) at the controls' own batch size; cached by identity
-        (pointer, shape and in-place version of EVERY control tensor, `warp_cond` of the ResControlNet included).  The
+        (pointer, shape and in-place version of EVERY control tensor, `warp_cond` of the ResControlNet included, and the in-place
+        version of every extractor weight).  The
         gamma/beta buffers keep their addresses while the batch shape stays the same (captured hipGraphs read them); a
         re-allocation bumps `blocks.BUFFER_EPOCH`, which makes the pipeline drop its graphs."""
         key = tuple((t.data_ptr(), tuple(t.shape), t._version) for t in (controlnet_cond, flow_cond, warp_cond) if t is not None)
+        # the extractors' weights can be trained in place (pyramid_train.BiDirFeatureExtractor.from_inference wraps these very
+        # tensors as parameters, which share their version counters): an optimiser step must reach the next decode
+        if self._extractor_tensors is None:
+            self._extractor_tensors = [t for name, ext in vars(self).items() if name.endswith("_extractor") for t in _packed_f32_tensors(ext)]
+        key += (tuple(t._version for t in self._extractor_tensors),)
         if key == self._ctrl_key:
             return self.gamma_beta
         pyr = self.compute_pyramid(controlnet_cond, flow_cond, warp_cond)

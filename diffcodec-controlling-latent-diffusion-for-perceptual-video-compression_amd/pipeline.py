@@ -443,7 +443,10 @@ class StableDiffusionDualFlowControlNetPipeline:
             chunk = 1
             while chunk < self._graph_chunk and i + chunk < nsteps and scales[i + chunk] == scale:
                 chunk += 1
-            gkey = (scale, float(guidance), shared, self._dual_stream, chunk, unipc)
+            # FreeU is read off the UNet: `pipe.unet.enable_freeu(...)` does not pass through this object, and a graph captured
+            # without it (or with other factors) replays the launches it was captured with
+            freeu = getattr(unet, "freeu", None)
+            gkey = (scale, float(guidance), shared, self._dual_stream, chunk, unipc, None if freeu is None else tuple(sorted(freeu.items())))
             g = self._graphs.get(gkey)
             if g is None:
                 torch.cuda.synchronize()

@@ -137,7 +137,7 @@ def decode_frame(unet_sd, cn_sd, vae_sd, unet_cfg, vae_cfg, controlnet_cond, flo
                  negative_prompt_embeds, latents, num_inference_steps=20, guidance_scale=7.5,
                  controlnet_conditioning_scale=1.0, output_type="pt", hoist=True, return_latents=False,
                  control_guidance_start=0.0, control_guidance_end=1.0, eta=0.0, generator=None, noise_dtype=torch.float32,
-                 res_cn_sd=None, warp_cond=None, res_conditioning_scale=None, scheduler="ddim", freeu=None):
+                 res_cn_sd=None, warp_cond=None, res_conditioning_scale=None, scheduler="ddim", freeu=None, guess_mode=False):
     """pipeline.py:144-404, `prompt_embeds=` path.  hoist=True computes the step-invariant pyramid once
     (identical values to recomputing it every step as the reference does, flownet.py:78)."""
     do_cfg = guidance_scale is not None and guidance_scale > 1.0            # pipeline.py:202
@@ -164,14 +164,21 @@ def decode_frame(unet_sd, cn_sd, vae_sd, unet_cfg, vae_cfg, controlnet_cond, flo
         x_in = torch.cat([latents, latents], 0) if do_cfg else latents     # :313-320
         cc = torch.cat([controlnet_cond] * 2, 0) if do_cfg else controlnet_cond
         fc = torch.cat([flow_cond] * 2, 0) if do_cfg else flow_cond
-        p = [torch.cat([q, q], 0) for q in pyr] if (pyr is not None and do_cfg) else pyr
-        down, mid = M.dualflow_controlnet_forward(cn_sd, unet_cfg, x_in, t, ctx, cc, fc,
+        guess = guess_mode and do_cfg                                       # :323-327: the nets see the conditional half alone
+        c_in, c_ctx = (latents, ctx.chunk(2)[1]) if guess else (x_in, ctx)
+        if guess:
+            cc, fc = controlnet_cond, flow_cond
+        p = [torch.cat([q, q], 0) for q in pyr] if (pyr is not None and do_cfg and not guess) else pyr
+        down, mid = M.dualflow_controlnet_forward(cn_sd, unet_cfg, c_in, t, c_ctx, cc, fc,
                                                   controlnet_conditioning_scale * keep, pyramid=p)
         if pyr2 is not None:
-            p2 = [torch.cat([q, q], 0) for q in pyr2] if do_cfg else pyr2
-            d2, m2 = M.dualflow_controlnet_forward(res_cn_sd, unet_cfg, x_in, t, ctx, cc, fc, res_conditioning_scale * keep,
+            p2 = [torch.cat([q, q], 0) for q in pyr2] if (do_cfg and not guess) else pyr2
+            d2, m2 = M.dualflow_controlnet_forward(res_cn_sd, unet_cfg, c_in, t, c_ctx, cc, fc, res_conditioning_scale * keep,
                                                    pyramid=p2, residual_variant=True)
             down, mid = [a_ + b_ for a_, b_ in zip(down, d2)], mid + m2
+        if guess:                                                           # :353-355: zeros for the unconditional half
+            down = [torch.cat([torch.zeros_like(d), d], 0) for d in down]
+            mid = torch.cat([torch.zeros_like(mid), mid], 0)
         eps = M.unet_forward(unet_sd, unet_cfg, x_in, t, ctx, down, mid, freeu=freeu)   # :358-367
         if do_cfg:
             eu, et = eps.chunk(2)

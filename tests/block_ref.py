@@ -455,7 +455,7 @@ def controlnet(sd, cfg, x, t, ctx, pyramid, scale, q=ident, fold=True, fault=Non
     return down, conv(sd, "controlnet_mid_block", sample.v, q, out_scale=scale)
 
 
-def unet(sd, cfg, x, t, ctx, q=ident, fold=True, fault=None, down_res=None, mid_res=None, controls=None):
+def unet(sd, cfg, x, t, ctx, q=ident, fold=True, fault=None, down_res=None, mid_res=None, controls=None, freeu=None):
     """HipUNet2DConditionModel.forward_nhwc.  down_res / mid_res: stored residuals, added by dc_add_bf16 (one rounding);
     controls: [(features, mid feature, the ControlNet's state dict, scale)]: zero_conv(f) * scale + skip in one epilogue."""
     g, boc = cfg["groups"], cfg["block_out_channels"]
@@ -476,12 +476,16 @@ def unet(sd, cfg, x, t, ctx, q=ident, fold=True, fault=None, down_res=None, mid_
     for _, mid_feat, csd, scale in controls:
         sc = 1.0 if fault == "control_scale_dropped" else scale
         sample = conv(csd, "controlnet_mid_block", as_act(mid_feat).v, q, out_scale=sc, residual=sample.v)
-    if not controls and mid_res is not None:
+    if not controls and mid_res is not None and fault != "mid_residual_dropped":
         sample = Act(q(sample.v + mid_res))
+    if fault == "skip_from_wrong_level":                                  # the two skips popped first change places
+        res[-1], res[-2] = res[-2], res[-1]
     for i in range(nb):
         for j in range(cfg["layers_per_block"] + 1):
             skip = res.pop()
             p = f"up_blocks.{i}.resnets.{j}."
+            if freeu is not None and (i < 2 or fault == "freeu_on_every_up_block"):
+                sample, skip = apply_freeu(min(i, 1), sample, skip, freeu, q, fault)
             sample = resnet(sd, p, sample, temb[p], g, 1e-5, q, x2=skip, fault=fault)
             if cfg["down_cross"][nb - 1 - i]:
                 sample = transformer(sd, f"up_blocks.{i}.attentions.{j}.", sample, ctx, cfg["num_heads"], g, q, fold, fault)
@@ -489,6 +493,29 @@ def unet(sd, cfg, x, t, ctx, q=ident, fold=True, fault=None, down_res=None, mid_
             sample = upsample_conv(sd, f"up_blocks.{i}.upsamplers.0.conv", sample, q, fault)
     h = gn_apply(sample.v, gn_ab(sample.pre, sd["conv_norm_out.weight"], sd["conv_norm_out.bias"], g, 1e-5), q, True)
     return conv(sd, "conv_out", h, q, f32_out=True)
+
+
+def fourier_filter(x, scale):
+    """diffusers' fourier_filter at threshold 1 (oracle/sd15_ref.fourier_filter, in the input's precision): the centred 2x2 block of
+    the shifted 2-D spectrum times `scale`."""
+    xf = torch.fft.fftshift(torch.fft.fftn(x, dim=(-2, -1)), dim=(-2, -1))
+    h, w = x.shape[-2:]
+    mask = torch.ones_like(xf.real)
+    mask[..., h // 2 - 1:h // 2 + 1, w // 2 - 1:w // 2 + 1] = scale
+    return torch.fft.ifftn(torch.fft.ifftshift(xf * mask, dim=(-2, -1)), dim=(-2, -1)).real
+
+
+def apply_freeu(idx, sample, skip, freeu, q=ident, fault=None):
+    """apply_freeu of the first two up blocks (unet.py:123-125): the first half of the backbone's channels times b (one rounding,
+    csrc/elementwise.hip freeu_backbone_kernel), the skip's four lowest frequency bins times s (x + (s - 1) / HW * low in fp32,
+    one rounding, freeu_lowfreq_kernel).  Neither output has epilogue statistics: the next GroupNorm measures the stored tensor."""
+    b, s = (freeu["b1"], freeu["s1"]) if idx == 0 else (freeu["b2"], freeu["s2"])
+    if fault == "freeu_b_s_exchanged":
+        b, s = s, b
+    sample, skip = as_act(sample).v, as_act(skip).v
+    half = sample.shape[1] // 2
+    sample = torch.cat([q(sample[:, :half] * b), sample[:, half:]], 1)
+    return Act(sample), Act(q(fourier_filter(skip, s)))
 
 
 def combine_residuals(a, b, q=ident):
@@ -565,6 +592,7 @@ def vae_attention_weights(sd, gen, p, c):
 
 QUIET = 3e-3
 PEAK = 6.0
+LOUD = 8.0                                     # standard deviation of the residuals that enter the UNet's deepest level in the loud case
 
 
 def stored(x):
@@ -614,6 +642,8 @@ BRANCHES = {
     "vae.encode": "vae.py encode_moments_nhwc, with conv_out on the VALU small-cout path and quant_conv on the small-cin path",
     "unet.plain": "unet.py decode_nhwc: no residuals",
     "unet.residuals_added": "unet.py decode_nhwc: down_res / mid_res added by dc_add_bf16",
+    "unet.residuals_loud": "unet.py decode_nhwc: the same adds with mid_res and the three 1x1-map down_res at a standard deviation of 8, "
+                           "so that the deepest level carries the output (no other launches: what the bars can see differs)",
     "unet.control_one": "unet.py decode_nhwc: one control tuple, zero-convs fused with the skip add",
     "unet.control_two": "unet.py decode_nhwc: two control tuples, their residuals add",
     "run_down.unshared": "blocks.py EncoderHalf.run_down(cfg_shared=False)",
@@ -689,6 +719,8 @@ def predicted_branches(case):
             out.add("controlnet.features_only")
         if mode == "combined2":
             out |= {"controlnet.zero_convs", "rescontrolnet.combine_residuals"}
+        if o.get("loud"):
+            out.add("unet.residuals_loud")
     return out
 
 
@@ -765,6 +797,8 @@ BLOCK_CASES += [
         _UB + ["unet.plain", "run_down.cfg_shared"]),
     _mk("unet_residuals_b2", "unet", dict(n=2, h=8, w=8), dict(mode="residuals"), "unit",
         _UB + ["unet.residuals_added", "run_down.unshared"]),
+    _mk("unet_residuals_loud_b2", "unet", dict(n=2, h=8, w=8), dict(mode="residuals", loud=LOUD), "unit",
+        _UB + ["unet.residuals_added", "unet.residuals_loud", "run_down.unshared"]),
     _mk("controlnet_b2", "controlnet", dict(n=2, h=8, w=8), dict(scale=1.7), "unit",
         ["controlnet.zero_convs", "run_down.unshared", "down.stride2", "temb.batched_slices", "resnet.temb"]),
     _mk("unet_control1_b2", "unet", dict(n=2, h=8, w=8), dict(mode="control1", scale=1.7), "unit",
@@ -794,11 +828,13 @@ FAULTS = {
     "vae_symmetric_pad": ("vae_down",), "vae_attn_scale_per_head": ("vae_attention", "vae_mid"),
     "vae_gn_eps_1e-5": ("vae_attention", "vae_down"),
     "control_scale_dropped": ("controlnet", "unet"), "second_controlnet_dropped": ("unet",), "fdn_applied_once": ("controlnet",),
+    "mid_residual_dropped": ("unet",), "skip_from_wrong_level": ("unet",),
 }
-# (mid_residual_dropped and skip_from_wrong_level are not here: at the 4 x bar of a whole UNet forward the fp64 fault moves the
-# output by 0.53 and 0.8 of the bar — nothing rejects them, DESIGN.md §18 has the figures)
+# (mid_residual_dropped and skip_from_wrong_level act at the 1x1 level: with unit residuals they move the 8x8 output by 0.53 and
+# 0.8 of the bar; the case unet_residuals_loud_b2 exists to reject them, DESIGN.md §18 has the figures)
 _MODES = {"control_scale_dropped": ("control1", "control2", "combined2"), "second_controlnet_dropped": ("control2", "combined2"),
-          "upsample_after_conv": ("plain", "residuals")}
+          "upsample_after_conv": ("plain", "residuals"), "mid_residual_dropped": ("residuals",),
+          "skip_from_wrong_level": ("residuals",)}
 FAULTS["upsample_after_conv"] = ("up", "vae_up", "unet")
 
 
@@ -890,8 +926,10 @@ def build_case(case):
                     if i != len(boc) - 1:
                         lvl += 1
                         sizes.append(lvl)
-                inp["down_res"] = [stored(_rand(gen, s["n"], c, s["h"] >> l, s["w"] >> l, std=0.5)) for c, l in zip(chans, sizes)]
-                inp["mid_res"] = stored(_rand(gen, s["n"], boc[-1], s["h"] >> lvl, s["w"] >> lvl))
+                loud = o.get("loud")                       # the mid residual and the 1x1-map skips' residuals at that standard deviation
+                inp["down_res"] = [stored(_rand(gen, s["n"], c, s["h"] >> l, s["w"] >> l, std=loud if loud and l == lvl else 0.5))
+                                   for c, l in zip(chans, sizes)]
+                inp["mid_res"] = stored(_rand(gen, s["n"], boc[-1], s["h"] >> lvl, s["w"] >> lvl, std=loud or 1.0))
     else:
         raise KeyError(case.block)
     return sd, inp
