@@ -17,7 +17,7 @@
 //
 // LDS images are row-major 128-B rows with the 16-B chunk index XORed by (row & 7): ds_write_b128 of a row piece and
 // the v_mfma_f32_16x16x32_bf16 fragment ds_read_b128 are both bank-conflict-free, and rows stay whole 128-B lines.
-#include "dc_conv_route.h"
+#include "dc_epilogue.h"
 #include <cstdlib>
 #include <utility>
 
@@ -39,12 +39,6 @@ template <int... I, class F>
 __device__ __forceinline__ void dc_static_for(std::integer_sequence<int, I...>, F&& f)
 {
     (f(std::integral_constant<int, I>{}), ...);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt()
-{
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
 // EPI: epilogue specialisation (same reasoning as gemm_dma.hip): 0 = generic run-time flags (split-K slabs, fp32 output,
@@ -491,7 +485,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_tile_kernel(const dc_conv_desc
         const int oy = dual ? (tm << 1) + fdy : oy0 + ((wm * TM + tm) << sh) + fdy, ox = ox0 + fdx;
         mrow[tm] = ((long long)n_img * d.Ho + oy) * d.Wo + ox;
     }
-    bf16x4 rr[TM][TN];
+    bf16x4 rr[TM][TN] = {};
     if (e_res) {
 #pragma unroll
         for (int tm = 0; tm < TM; ++tm)
@@ -534,23 +528,14 @@ __global__ __launch_bounds__(256, 2) void conv3x3_tile_kernel(const dc_conv_desc
                 *(f32x4*)(d.splitk_ws + (long long)blockIdx.y * slab + off) = v;
                 continue;
             }
-            if constexpr (!BIAS_INIT) v += bv[tn];
-            if (e_act) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = dc_act(v[r], e_act);
-            }
-            if (e_res) v = dc_scale_res(v, d.out_scale, rr[tm][tn]);
-            else v *= d.out_scale;
-            if (want_gn) {
-                gs[tn] += v;
-                gq[tn] += v * v;
-            }
+            // bv = bias + row_add, pre-summed per channel above: this kernel's order, not the GEMMs' (dc_epilogue.h)
+            v = dc_epi_plain(v, (BIAS_INIT ? 0 : DC_EPI_BIAS) | (e_res ? DC_EPI_RES : 0), e_act, 0.f, 0.f, f32x4{0.f, 0.f, 0.f, 0.f}, bv[tn],
+                             f32x4{0.f, 0.f, 0.f, 0.f}, d.out_scale, rr[tm][tn]);
+            if (want_gn) dc_gn_part_add(gs[tn], gq[tn], v, 1.f);
             if (e_f32) {
                 *(f32x4*)((float*)d.out + off) = v;
             } else {
-                bf16x4 pk;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) pk[r] = (bf16_t)v[r];
+                const bf16x4 pk = dc_pack_bf16x4(v);
                 if constexpr (stg) *(bf16x4*)(smem + ((wm * TM + tm) * 16 + fr) * SP + ((((wn * TN + tn) * 16 + 4 * fq) * 2) ^ dc_stage_swz(fr))) = pk;
                 else *(bf16x4*)((bf16_t*)d.out + off) = pk;
             }

@@ -14,6 +14,7 @@ typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
+typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
 
@@ -165,6 +166,11 @@ __device__ __forceinline__ float dc_wave_max(float v)
 // tiles that differ from run to run (found with tools/find_nondeterminism.py on the unrolled TM=2 tile conv).  The
 // sched_barrier keeps the step's MFMAs in front of the wait (so the wait is normally already satisfied), the compiler
 // barrier after s_barrier keeps the next step's LDS reads behind it.
+template <int N>
+__device__ __forceinline__ void wait_vmcnt()
+{
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
 template <int N>
 __device__ __forceinline__ void dc_ring_sync()
 {

@@ -9,9 +9,8 @@
 // the v_mfma_f32_16x16x32_bf16 fragment ds_read_b128 stay conflict-free.  NST LDS stages form a ring: the DMA of
 // K-step k+NST-1 is issued right after the barrier that opens step k, and a counted `s_waitcnt vmcnt(N)` (never 0 in
 // the loop) leaves NST-2 stages in flight across every raw `s_barrier` — one barrier per K-step.
-#include "dc_conv_route.h"
+#include "dc_epilogue.h"
 #include <cstdlib>
-#include <type_traits>
 
 // Developer-only phase stamps (tools/gemm_stamp.py builds this file with -DDC_STAMP into a scratch .so): s_memtime at
 // kernel entry / after the first stage landed / after the K loop / at exit, written to the (otherwise unused) split-K
@@ -34,12 +33,6 @@ namespace {
 typedef const void __attribute__((address_space(1))) * gptr_t;
 typedef void __attribute__((address_space(3))) * lptr_t;
 
-template <int N>
-__device__ __forceinline__ void wait_vmcnt()
-{
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 // EPI: epilogue specialisation chosen by the launcher from the descriptor.  With every fusion a run-time flag, the unrolled
 // (tm, tn) epilogue was 6,300 instructions in 336 basic blocks — a branch (and often a wait) per flag per 4 outputs — and took
 // 10.7k cycles per workgroup against 9k for the whole K loop at K = 320 (phase stamps, tools/gemm_stamp.py).  The common
@@ -56,6 +49,7 @@ __global__ __launch_bounds__(256, 2) void gemm_dma_kernel(const dc_conv_desc d)
     const bool e_res = GENERIC ? d.residual != nullptr : EPI == 2;
     const bool e_rowadd = GENERIC && d.row_add != nullptr;
     const int e_act = GENERIC ? d.act : 0;
+    const int e_flags = (e_ln ? DC_EPI_LN : 0) | DC_EPI_BIAS | (e_res ? DC_EPI_RES : 0);       // (+ DC_EPI_ROWADD per fragment inside Cout)
     const bool e_stats = (GENERIC || EPI == 1 || EPI == 2) && d.stats_out != nullptr;
     const bool e_gnpart = (GENERIC || EPI == 1 || EPI == 2) && d.gn_part_out != nullptr;
     constexpr int WM = 2, WN = 2;
@@ -179,19 +173,15 @@ __global__ __launch_bounds__(256, 2) void gemm_dma_kernel(const dc_conv_desc d)
     };
 
     // bias for this lane's output channels: fetched now so its latency hides under the K loop
+    const int nb0 = n0 + wn * TN * 16 + 4 * fq;        // this lane's first output channel
     f32x4 bv[TN];
-#pragma unroll
-    for (int tn = 0; tn < TN; ++tn) {
-        const int nb = n0 + (wn * TN + tn) * 16 + 4 * fq;
-        bv[tn] = (d.bias && nb < d.Cout) ? *(const f32x4*)(d.bias + nb) : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
+    dc_epi_load_cols<TN>(bv, d.bias, nb0, d.Cout);
 
     // LayerNorm folded into this linear (dc_conv_desc.ln_stats): this lane's rows' (mean, rstd) and the weight column sums,
     // fetched here next to the bias and first used in the epilogue, so the loads fly under the whole K loop (consuming them
     // here would put a full memory round trip in front of the first DMA stage of every workgroup)
-    typedef __attribute__((ext_vector_type(2))) float f32x2;
-    f32x2 ln_mr[TM];
-    f32x4 cs[TN];
+    f32x2 ln_mr[TM] = {};
+    f32x4 cs[TN] = {};
     if (e_ln) {
 #pragma unroll
         for (int tm = 0; tm < TM; ++tm) {
@@ -199,11 +189,7 @@ __global__ __launch_bounds__(256, 2) void gemm_dma_kernel(const dc_conv_desc d)
             m = m < M ? m : M - 1;
             ln_mr[tm] = *(const f32x2*)(d.ln_stats + (long long)m * 2);
         }
-#pragma unroll
-        for (int tn = 0; tn < TN; ++tn) {
-            const int nb = n0 + (wn * TN + tn) * 16 + 4 * fq;
-            cs[tn] = nb < d.Cout ? *(const f32x4*)(d.ln_colsum + nb) : f32x4{0.f, 0.f, 0.f, 0.f};
-        }
+        dc_epi_load_cols<TN>(cs, d.ln_colsum, nb0, d.Cout);
     }
 
     // ---- pipeline
@@ -220,7 +206,6 @@ __global__ __launch_bounds__(256, 2) void gemm_dma_kernel(const dc_conv_desc d)
     wait_vmcnt<0>();
     DC_STAMP_AT(2);
 
-    const long long slab = (long long)d.N * d.Ho * d.Wo * d.Cout;   // elements per split-K slab
     // ---- epilogue.  bf16 outputs go through LDS so that global stores (and residual loads) are whole 16-byte pieces of
     //      contiguous output rows: the MFMA layout gives each lane 4 channels of one pixel, i.e. 32-byte row fragments
     //      per store instruction; staged, every row leaves as BN*2 contiguous bytes.
@@ -233,19 +218,8 @@ __global__ __launch_bounds__(256, 2) void gemm_dma_kernel(const dc_conv_desc d)
         DC_STAMP_AT(4);
         // all epilogue operands are fetched up front (independent loads in flight together): issued one (tm, tn) tile at
         // a time behind `if (bias)` / `if (residual)` they serialise into ~20 dependent L2 round trips per workgroup
-        bf16x4 rr[TM][TN];
-        if (e_res && !e_geglu) {
-#pragma unroll
-            for (int tm = 0; tm < TM; ++tm) {
-                const int m = m0 + (wm * TM + tm) * 16 + fr;
-#pragma unroll
-                for (int tn = 0; tn < TN; ++tn) {
-                    const int nb = n0 + (wn * TN + tn) * 16 + 4 * fq;
-                    rr[tm][tn] = (m < M && nb < d.Cout) ? *(const bf16x4*)((const bf16_t*)d.residual + (long long)m * d.Cout + nb)
-                                                        : bf16x4{(bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f};
-                }
-            }
-        }
+        bf16x4 rr[TM][TN] = {};
+        if (e_res && !e_geglu) dc_epi_load_residual<TM, TN>(rr, d.residual, m0 + wm * TM * 16 + fr, M, nb0, d.Cout);
         f32x4 gs[TN], gq[TN];                                   // GroupNorm partials over this wave's rows (gn_part_out)
 #pragma unroll
         for (int tn = 0; tn < TN; ++tn) gs[tn] = gq[tn] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -257,17 +231,9 @@ __global__ __launch_bounds__(256, 2) void gemm_dma_kernel(const dc_conv_desc d)
             if (e_geglu) {
 #pragma unroll
                 for (int tp = 0; tp < TN / 2; ++tp) {
-                    f32x4 h = acc[2 * tp][tm], g = acc[2 * tp + 1][tm];
-                    if (e_ln) {
-                        h = dc_ln_fold(h, ln_mr[tm][0], ln_mr[tm][1], cs[2 * tp]);
-                        g = dc_ln_fold(g, ln_mr[tm][0], ln_mr[tm][1], cs[2 * tp + 1]);
-                    }
-                    h += bv[2 * tp];
-                    g += bv[2 * tp + 1];
-                    bf16x4 pk;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) pk[r] = (bf16_t)(h[r] * dc_gelu_erf(g[r]));
-                    *(bf16x4*)(smem + row * PITCH + (((((wn * TN + 2 * tp) * 16) / 2 + 4 * fq) * 2) ^ dc_stage_swz(row))) = pk;
+                    *(bf16x4*)(smem + row * PITCH + (((((wn * TN + 2 * tp) * 16) / 2 + 4 * fq) * 2) ^ dc_stage_swz(row))) =
+                        dc_epi_geglu(acc[2 * tp][tm], acc[2 * tp + 1][tm], e_flags, ln_mr[tm][0], ln_mr[tm][1], cs[2 * tp], cs[2 * tp + 1],
+                                     bv[2 * tp], bv[2 * tp + 1]);
                 }
             } else {
                 float st1 = 0.f, st2 = 0.f;                     // partial (sum, sum of squares) of this output row: stats_out
@@ -276,37 +242,18 @@ __global__ __launch_bounds__(256, 2) void gemm_dma_kernel(const dc_conv_desc d)
                 for (int tn = 0; tn < TN; ++tn) {
                     const int nl = (wn * TN + tn) * 16 + 4 * fq;
                     const int nb = n0 + nl;
-                    f32x4 v = acc[tn][tm];
-                    if (e_ln) v = dc_ln_fold(v, ln_mr[tm][0], ln_mr[tm][1], cs[tn]);
-                    v += bv[tn];
-                    if (e_rowadd && nb < d.Cout) v += *(const f32x4*)(d.row_add + (long long)nimg * d.row_add_stride + nb);
-                    if (e_act) {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) v[r] = dc_act(v[r], e_act);
-                    }
-                    if (e_res) v = dc_scale_res(v, d.out_scale, rr[tm][tn]);
-                    else v *= d.out_scale;
-                    bf16x4 pk;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) pk[r] = (bf16_t)v[r];
-                    *(bf16x4*)(smem + row * PITCH + ((nl * 2) ^ dc_stage_swz(row))) = pk;
+                    const f32x4 v = dc_epi_plain_with(
+                        acc[tn][tm], e_flags | (e_rowadd && nb < d.Cout ? DC_EPI_ROWADD : 0), e_act, ln_mr[tm][0], ln_mr[tm][1], cs[tn],
+                        [&] { return bv[tn]; }, [&] { return *(const f32x4*)(d.row_add + (long long)nimg * d.row_add_stride + nb); }, d.out_scale,
+                        [&] { return rr[tm][tn]; });
+                    *(bf16x4*)(smem + row * PITCH + ((nl * 2) ^ dc_stage_swz(row))) = dc_pack_bf16x4(v);
                     if (GENERIC || EPI == 1 || EPI == 2) {      // the sums are a handful of FMAs: always formed, stored on request
-                        const float cm = nb < d.Cout ? 1.f : 0.f;
-                        st1 += cm * ((v[0] + v[1]) + (v[2] + v[3]));
-                        st2 += cm * ((v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]));
-                        gs[tn] += rowmask * v;
-                        gq[tn] += rowmask * (v * v);
+                        dc_row_stats_add(st1, st2, v, nb < d.Cout ? 1.f : 0.f);
+                        dc_gn_part_add(gs[tn], gq[tn], v, rowmask);
                     }
                 }
-                if (e_stats) {                                  // lanes fr, fr+16, fr+32, fr+48 hold the same row: fixed-order tree
-                    st1 += __shfl_xor(st1, 16, 64);
-                    st2 += __shfl_xor(st2, 16, 64);
-                    st1 += __shfl_xor(st1, 32, 64);
-                    st2 += __shfl_xor(st2, 32, 64);
-                    if (fq == 0 && m < M) {
-                        *(f32x2*)(d.stats_out + ((long long)m * (2 * n_tiles) + tile_n * 2 + wn) * 2) = f32x2{st1, st2};
-                    }
-                }
+                if (e_stats)
+                    dc_row_stats_store(st1, st2, d.stats_out + ((long long)m * (2 * n_tiles) + tile_n * 2 + wn) * 2, fq == 0 && m < M);
             }
         }
         if (e_gnpart) {
@@ -327,74 +274,13 @@ __global__ __launch_bounds__(256, 2) void gemm_dma_kernel(const dc_conv_desc d)
         const int out_cols = e_geglu ? d.Cout >> 1 : d.Cout;
         const int col0 = e_geglu ? n0 >> 1 : n0;
         bf16_t* __restrict__ o = (bf16_t*)d.out;
-        auto store_rows = [&](auto pieces_c) {                  // 16-byte pieces per staged row: a compile-time divisor
-            constexpr int pieces = decltype(pieces_c)::value;
-            for (int i = tid; i < BM * pieces; i += 256) {
-                const int row = i / pieces, pc = i - row * pieces;
-                const int m = m0 + row, c = col0 + pc * 8;
-                if (m < M && c < out_cols) *(u32x4*)(o + (long long)m * out_cols + c) = dc_stage_unswz(*(const u32x4*)(smem + row * PITCH + pc * 16), row);
-            }
-        };
-        if (e_geglu) store_rows(std::integral_constant<int, OC / 16>{});
-        else store_rows(std::integral_constant<int, OC / 8>{});
+        if (e_geglu) dc_stage_store_rows<BM, PITCH, OC / 16, 256>(smem, o, m0, M, col0, out_cols);     // 16-byte pieces per staged
+        else dc_stage_store_rows<BM, PITCH, OC / 8, 256>(smem, o, m0, M, col0, out_cols);              // row: a compile-time divisor
         DC_STAMP_AT(3);
         return;
     }
-    // ---- direct epilogue (fp32 outputs, split-K partials): same contract as igemm.hip
-#pragma unroll
-    for (int tm = 0; tm < TM; ++tm) {
-        const int m = m0 + (wm * TM + tm) * 16 + fr;
-        if (m >= M) continue;
-        const int nimg = m / HoWo;
-        if (d.epilogue == 1) {
-            const int half = d.Cout >> 1;
-            bf16_t* __restrict__ o = (bf16_t*)d.out;
-#pragma unroll
-            for (int tp = 0; tp < TN / 2; ++tp) {
-                const int nb = n0 + (wn * TN + 2 * tp) * 16 + 4 * fq;
-                if (nb >= d.Cout) continue;
-                f32x4 h = acc[2 * tp][tm];
-                f32x4 g = acc[2 * tp + 1][tm];
-                if (d.bias) {
-                    h += *(const f32x4*)(d.bias + nb);
-                    g += *(const f32x4*)(d.bias + nb + 16);
-                }
-                const int col = ((n0 + (wn * TN + 2 * tp) * 16) >> 1) + 4 * fq;
-                bf16x4 pk;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) pk[r] = (bf16_t)(h[r] * dc_gelu_erf(g[r]));
-                *(bf16x4*)(o + (long long)m * half + col) = pk;
-            }
-            continue;
-        }
-#pragma unroll
-        for (int tn = 0; tn < TN; ++tn) {
-            const int nb = n0 + (wn * TN + tn) * 16 + 4 * fq;
-            if (nb >= d.Cout) continue;
-            f32x4 v = acc[tn][tm];
-            const long long off = (long long)m * d.Cout + nb;
-            if (d.splitk > 1) {                                   // this split's own fp32 slab: plain stores, no atomics
-                *(f32x4*)(d.splitk_ws + (long long)blockIdx.y * slab + off) = v;
-                continue;
-            }
-            if (d.bias) v += *(const f32x4*)(d.bias + nb);
-            if (d.row_add) v += *(const f32x4*)(d.row_add + (long long)nimg * d.row_add_stride + nb);
-            if (d.act) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = dc_act(v[r], d.act);
-            }
-            if (d.residual) v = dc_scale_res(v, d.out_scale, *(const bf16x4*)((const bf16_t*)d.residual + off));
-            else v *= d.out_scale;
-            if (d.out_f32) {
-                *(f32x4*)((float*)d.out + off) = v;
-            } else {
-                bf16x4 pk;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) pk[r] = (bf16_t)v[r];
-                *(bf16x4*)((bf16_t*)d.out + off) = pk;
-            }
-        }
-    }
+    // ---- direct epilogue (fp32 outputs, split-K partials): the one igemm.hip runs
+    dc_epi_direct<TM, TN>(acc, d, m0, n0, wm, wn, fr, fq);
 }
 
 template <int TM, int TN, int NST, int EPI>

@@ -25,7 +25,7 @@
 //        the barrier that closes the reading phase of either group.
 // Accumulation order over K is the tile kernels' (ascending 32-wide MFMA steps), the epilogue arithmetic is theirs
 // (dc_common.h): outputs are bit-identical with gemm_dma.hip / gemm_wide.hip.
-#include "dc_conv_route.h"
+#include "dc_epilogue.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -33,7 +33,6 @@ namespace {
 
 typedef const void __attribute__((address_space(1))) * gptr_t;
 typedef void __attribute__((address_space(3))) * lptr_t;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
 
 constexpr int P8_HALF = 128 * 128;                  // bytes of a half tile
 constexpr int P8_BUF = 4 * P8_HALF;                 // one K tile
@@ -67,6 +66,7 @@ template <int EPI>
 __global__ __launch_bounds__(512, 2) void gemm_p8_kernel(const dc_conv_desc d)
 {
     constexpr bool e_geglu = EPI >= 4, e_ln = EPI == 3 || EPI == 5;
+    constexpr int e_flags = (e_ln ? DC_EPI_LN : 0) | DC_EPI_BIAS;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -258,30 +258,24 @@ __global__ __launch_bounds__(512, 2) void gemm_p8_kernel(const dc_conv_desc d)
 #pragma unroll
             for (int tp = 0; tp < 2; ++tp) {
                 const int nl = wc * 64 + tp * 32 + 4 * fq;                      // value block; gate block = + 16
-                f32x4 h = acc[2 * tp][tm], g = acc[2 * tp + 1][tm];
+                f32x4 ch = {0.f, 0.f, 0.f, 0.f}, cg = ch;
                 if (e_ln) {
-                    h = dc_ln_fold(h, mr[0], mr[1], *(const f32x4*)(smem + P8_PAR_CS + nl * 4));
-                    g = dc_ln_fold(g, mr[0], mr[1], *(const f32x4*)(smem + P8_PAR_CS + (nl + 16) * 4));
+                    ch = *(const f32x4*)(smem + P8_PAR_CS + nl * 4);
+                    cg = *(const f32x4*)(smem + P8_PAR_CS + (nl + 16) * 4);
                 }
-                h += *(const f32x4*)(smem + P8_PAR_BIAS + nl * 4);
-                g += *(const f32x4*)(smem + P8_PAR_BIAS + (nl + 16) * 4);
-                bf16x4 pk;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) pk[r] = (bf16_t)(h[r] * dc_gelu_erf(g[r]));
-                *(bf16x4*)(smem + row * PITCH + (((wc * 32 + tp * 16 + 4 * fq) * 2) ^ dc_stage_swz(row))) = pk;
+                *(bf16x4*)(smem + row * PITCH + (((wc * 32 + tp * 16 + 4 * fq) * 2) ^ dc_stage_swz(row))) =
+                    dc_epi_geglu(acc[2 * tp][tm], acc[2 * tp + 1][tm], e_flags, mr[0], mr[1], ch, cg, *(const f32x4*)(smem + P8_PAR_BIAS + nl * 4),
+                                 *(const f32x4*)(smem + P8_PAR_BIAS + (nl + 16) * 4));
             }
         } else {
 #pragma unroll
             for (int tn = 0; tn < 4; ++tn) {
                 const int nl = wc * 64 + tn * 16 + 4 * fq;
-                f32x4 v = acc[tn][tm];
-                if (e_ln) v = dc_ln_fold(v, mr[0], mr[1], *(const f32x4*)(smem + P8_PAR_CS + nl * 4));
-                v += *(const f32x4*)(smem + P8_PAR_BIAS + nl * 4);
-                v *= d.out_scale;
-                bf16x4 pk;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) pk[r] = (bf16_t)v[r];
-                *(bf16x4*)(smem + row * PITCH + ((nl * 2) ^ dc_stage_swz(row))) = pk;
+                f32x4 cs = {0.f, 0.f, 0.f, 0.f};
+                if (e_ln) cs = *(const f32x4*)(smem + P8_PAR_CS + nl * 4);
+                const f32x4 v = dc_epi_plain(acc[tn][tm], e_flags, 0, mr[0], mr[1], cs, *(const f32x4*)(smem + P8_PAR_BIAS + nl * 4),
+                                             f32x4{0.f, 0.f, 0.f, 0.f}, d.out_scale, bf16x4{});
+                *(bf16x4*)(smem + row * PITCH + ((nl * 2) ^ dc_stage_swz(row))) = dc_pack_bf16x4(v);
             }
         }
         __builtin_amdgcn_sched_barrier(0);           // one row group at a time (register pressure)
@@ -290,12 +284,7 @@ __global__ __launch_bounds__(512, 2) void gemm_p8_kernel(const dc_conv_desc d)
     const int out_cols = e_geglu ? d.Cout >> 1 : d.Cout;
     const int col0 = e_geglu ? n0 >> 1 : n0;
     bf16_t* __restrict__ o = (bf16_t*)d.out;
-    constexpr int pieces = OC / 8;                   // 16-byte pieces per staged row
-    for (int i = tid; i < 256 * pieces; i += 512) {
-        const int row = i / pieces, pc = i - row * pieces;
-        if (col0 + pc * 8 < out_cols)
-            *(u32x4*)(o + (long long)(m0 + row) * out_cols + col0 + pc * 8) = dc_stage_unswz(*(const u32x4*)(smem + row * PITCH + pc * 16), row);
-    }
+    dc_stage_store_rows<256, PITCH, OC / 8, 512>(smem, o, m0, M, col0, out_cols);       // (M is whole tiles: the row test never fails)
 }
 
 template <int EPI>

@@ -27,7 +27,7 @@
 // vmcnt(P + T + R + 2 (F + G)) and the wait in front of the first read of the residual rows is vmcnt(P).
 // The accumulators see the same k order as gemm_dma.hip (ten 32-wide steps in sequence, v_mfma_f32_16x16x32_bf16) and the
 // epilogue arithmetic is the same expressions, so the bf16 outputs are bit-identical to the tile kernels'.
-#include "dc_conv_route.h"
+#include "dc_epilogue.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -51,7 +51,6 @@ namespace {
 
 typedef const void __attribute__((address_space(1))) * gptr_t;
 typedef void __attribute__((address_space(3))) * lptr_t;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
 
 constexpr int RP_K = 320;                          // the only K this kernel is built for
 constexpr int RP_KS = RP_K / 32;                   // 32-wide MFMA k-steps
@@ -66,12 +65,6 @@ constexpr int RP_TOUCH = 256;                      // wave-private landing pad o
 constexpr int RP_LDS = RP_NST * RP_STAGE + 8 * RP_STG + 8 * RP_TOUCH;
 static_assert(RP_LDS <= 160 * 1024, "LDS budget");
 
-template <int N>
-__device__ __forceinline__ void rp_wait_vm()
-{
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 // EPI as in gemm_dma.hip: 1 bias, 2 bias + scale + residual, 3 folded LayerNorm + bias, 4 GEGLU, 5 folded LayerNorm + GEGLU.
 // GN: GroupNorm partials of the output requested (modes 1-2) — compile-time because its stores enter the vmcnt arithmetic.
 template <int EPI, bool GN>
@@ -79,6 +72,8 @@ __global__ __launch_bounds__(512, 2) void gemm_rowpanel_kernel(const dc_conv_des
 {
     constexpr bool e_geglu = EPI >= 4, e_ln = EPI == 3 || EPI == 5, e_res = EPI == 2;
     constexpr int T = e_res ? 1 : 0, R = e_res ? 4 : 0;
+    // (the chain multiplies by out_scale even when it is 1.0f, which this kernel used to skip: x * 1.0f is x, and no register moved)
+    constexpr int e_flags = (e_ln ? DC_EPI_LN : 0) | DC_EPI_BIAS | (e_res ? DC_EPI_RES : 0);
     constexpr int F = e_geglu ? 2 : 4, G = GN ? 2 * RP_TN : 0;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -88,7 +83,6 @@ __global__ __launch_bounds__(512, 2) void gemm_rowpanel_kernel(const dc_conv_des
     const int S = d.Cout / RP_SC;                                   // stages
     const long long mw = (long long)blockIdx.x * 256 + wave * 32;   // this wave's first row
     const bool e_stats = (EPI == 1 || EPI == 2) && d.stats_out != nullptr;
-    const bool scaled = d.out_scale != 1.0f;                       // x * 1.0f is x: the multiply is skipped, not approximated
     const int extra = wave == 0 || (wave == 1 && e_ln);             // wave-uniform: one small DMA piece more per stage
 
     // ---- this wave's activation rows as MFMA B-operand fragments: xf[tm][k] = X[mw + 16 tm + fr][32 k + 8 fq .. + 8)
@@ -119,7 +113,7 @@ __global__ __launch_bounds__(512, 2) void gemm_rowpanel_kernel(const dc_conv_des
             }
         }
     }
-    f32x2 ln_mr[RP_TM];
+    f32x2 ln_mr[RP_TM] = {};
     if (e_ln) {
         if (d.ln_parts > 0) {                                       // raw partials: the finalize pass folded into this prologue — every
             dc_ln_row_partials rp[RP_TM];                           // row's pairs fetched first (loads in flight together), then summed
@@ -244,7 +238,7 @@ __global__ __launch_bounds__(512, 2) void gemm_rowpanel_kernel(const dc_conv_des
         RP_STAMP_AT(3 + 3 * s);
 
         // ---- epilogue of the stage
-        f32x4 bv[RP_TN], cs[RP_TN];
+        f32x4 bv[RP_TN], cs[RP_TN] = {};
 #pragma unroll
         for (int tn = 0; tn < RP_TN; ++tn) {
             bv[tn] = *(const f32x4*)(sb + RP_WBYTES + (tn * 16 + 4 * fq) * 4);
@@ -252,8 +246,8 @@ __global__ __launch_bounds__(512, 2) void gemm_rowpanel_kernel(const dc_conv_des
         }
         if (e_res) {                                                // this wave's residual pieces of the stage have landed
             __builtin_amdgcn_sched_barrier(0);
-            if (extra) rp_wait_vm<RP_P + 1>();
-            else rp_wait_vm<RP_P>();
+            if (extra) wait_vmcnt<RP_P + 1>();
+            else wait_vmcnt<RP_P>();
             __builtin_amdgcn_sched_barrier(0);
         }
         f32x4 gs[RP_TN], gq[RP_TN];
@@ -265,16 +259,8 @@ __global__ __launch_bounds__(512, 2) void gemm_rowpanel_kernel(const dc_conv_des
             if (e_geglu) {
 #pragma unroll
                 for (int tp = 0; tp < RP_TN / 2; ++tp) {
-                    f32x4 h = acc[2 * tp][tm], g = acc[2 * tp + 1][tm];
-                    if (e_ln) {
-                        h = dc_ln_fold(h, ln_mr[tm][0], ln_mr[tm][1], cs[2 * tp]);
-                        g = dc_ln_fold(g, ln_mr[tm][0], ln_mr[tm][1], cs[2 * tp + 1]);
-                    }
-                    h += bv[2 * tp];
-                    g += bv[2 * tp + 1];
-                    bf16x4 pk;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) pk[r] = (bf16_t)(h[r] * dc_gelu_erf(g[r]));
+                    const bf16x4 pk = dc_epi_geglu(acc[2 * tp][tm], acc[2 * tp + 1][tm], e_flags, ln_mr[tm][0], ln_mr[tm][1], cs[2 * tp],
+                                                   cs[2 * tp + 1], bv[2 * tp], bv[2 * tp + 1]);
                     const int chunk = (tp * 2 + (fq >> 1)) ^ ((row >> 1) & 3);
                     const int half = (fq & 1) ^ ((row >> 3) & 1);
                     *(bf16x4*)(stg + row * 64 + chunk * 16 + half * 8) = pk;
@@ -282,26 +268,16 @@ __global__ __launch_bounds__(512, 2) void gemm_rowpanel_kernel(const dc_conv_des
             } else {
 #pragma unroll
                 for (int tn = 0; tn < RP_TN; ++tn) {
-                    f32x4 v = acc[tn][tm];
-                    if (e_ln) v = dc_ln_fold(v, ln_mr[tm][0], ln_mr[tm][1], cs[tn]);
-                    v += bv[tn];
                     const int chunk = (tn * 2 + (fq >> 1)) ^ x7;
-                    if (e_res) v = dc_scale_res(v, d.out_scale, *(const bf16x4*)(stg + row * 128 + chunk * 16 + (fq & 1) * 8));
-                    else if (scaled) v *= d.out_scale;
-                    bf16x4 pk;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) pk[r] = (bf16_t)v[r];
+                    bf16x4 rr = {};
+                    if (e_res) rr = *(const bf16x4*)(stg + row * 128 + chunk * 16 + (fq & 1) * 8);
+                    const f32x4 v = dc_epi_plain(acc[tn][tm], e_flags, 0, ln_mr[tm][0], ln_mr[tm][1], cs[tn], bv[tn], f32x4{0.f, 0.f, 0.f, 0.f},
+                                                 d.out_scale, rr);
                     const int half = (fq & 1) ^ ((row >> 3) & 1);
-                    *(bf16x4*)(stg + row * 128 + chunk * 16 + half * 8) = pk;
+                    *(bf16x4*)(stg + row * 128 + chunk * 16 + half * 8) = dc_pack_bf16x4(v);
                     if (EPI == 1 || EPI == 2) {
-                        if (e_stats) {
-                            st1[tm] += (v[0] + v[1]) + (v[2] + v[3]);
-                            st2[tm] += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
-                        }
-                        if (GN) {
-                            gs[tn] += v;
-                            gq[tn] += v * v;
-                        }
+                        if (e_stats) dc_row_stats_add(st1[tm], st2[tm], v, 1.f);
+                        if (GN) dc_gn_part_add(gs[tn], gq[tn], v, 1.f);
                     }
                 }
             }
@@ -343,10 +319,7 @@ __global__ __launch_bounds__(512, 2) void gemm_rowpanel_kernel(const dc_conv_des
 #pragma unroll
         for (int tm = 0; tm < RP_TM; ++tm) {
             float a = st1[tm], b = st2[tm];
-            a += __shfl_xor(a, 16, 64);
-            b += __shfl_xor(b, 16, 64);
-            a += __shfl_xor(a, 32, 64);
-            b += __shfl_xor(b, 32, 64);
+            dc_row_stats_reduce(a, b);
             float* dst = d.stats_out + (mw + tm * 16 + fr) * parts * 2;
             for (int p = fq; p < parts; p += 4) *(f32x2*)(dst + p * 2) = p == 0 ? f32x2{a, b} : f32x2{0.f, 0.f};
         }

@@ -17,7 +17,7 @@
 // either group;  WAR — stage k+2 reuses the slot of stage k-1, whose last reads (group 1, I(2k-1)) are retired by that
 // same lgkmcnt(0) before the barrier that opens I(2k), the earliest interval in which a piece of stage k+2 is issued.
 // No DMA is issued past the last stage (the epilogue stages its rows through the ring's LDS), so the final waits are vmcnt(0).
-#include "dc_conv_route.h"
+#include "dc_epilogue.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -25,7 +25,6 @@ namespace {
 
 typedef const void __attribute__((address_space(1))) * gptr_t;
 typedef void __attribute__((address_space(3))) * lptr_t;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
 
 template <int N>
 __device__ __forceinline__ void wait_vm_lgkm()
@@ -65,6 +64,7 @@ __global__ __launch_bounds__(512, 2) void gemm_wide_kernel(const dc_conv_desc d)
     const int wrow = grp * 128 + wm * TM * 16;        // first row of this wave's tiles inside the workgroup tile
     static_assert(ST == 0 || EPI == 1 || EPI == 2, "statistics ride on the bias / residual epilogues only");
     constexpr bool e_stats = (ST & 1) != 0, e_gnpart = (ST & 2) != 0;
+    constexpr int e_flags = (e_ln ? DC_EPI_LN : 0) | DC_EPI_BIAS | (e_res ? DC_EPI_RES : 0);
 
     const int HoWo = d.Ho * d.Wo;
     const int M = d.N * HoWo;
@@ -153,14 +153,11 @@ __global__ __launch_bounds__(512, 2) void gemm_wide_kernel(const dc_conv_desc d)
     };
 
     // bias / LayerNorm operands for this lane's outputs: fetched now, first used in the epilogue
+    const int nb0 = n0 + wn * TN * 16 + 4 * fq;       // this lane's first output channel
     f32x4 bv[TN];
-#pragma unroll
-    for (int tn = 0; tn < TN; ++tn) {
-        const int nb = n0 + (wn * TN + tn) * 16 + 4 * fq;
-        bv[tn] = (d.bias && nb < d.Cout) ? *(const f32x4*)(d.bias + nb) : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    f32x2 ln_mr[TM];
-    f32x4 cs[TN];
+    dc_epi_load_cols<TN>(bv, d.bias, nb0, d.Cout);
+    f32x2 ln_mr[TM] = {};
+    f32x4 cs[TN] = {};
     if (e_ln) {
 #pragma unroll
         for (int tm = 0; tm < TM; ++tm) {
@@ -168,11 +165,7 @@ __global__ __launch_bounds__(512, 2) void gemm_wide_kernel(const dc_conv_desc d)
             m = m < M ? m : M - 1;
             ln_mr[tm] = *(const f32x2*)(d.ln_stats + (long long)m * 2);
         }
-#pragma unroll
-        for (int tn = 0; tn < TN; ++tn) {
-            const int nb = n0 + (wn * TN + tn) * 16 + 4 * fq;
-            cs[tn] = nb < d.Cout ? *(const f32x4*)(d.ln_colsum + nb) : f32x4{0.f, 0.f, 0.f, 0.f};
-        }
+        dc_epi_load_cols<TN>(cs, d.ln_colsum, nb0, d.Cout);
     }
     // the operand loads above are ordinary VMEM operations in front of the DMA pieces in this wave's queue: retire them now so
     // that the counted waits below see DMA pieces only
@@ -207,19 +200,8 @@ __global__ __launch_bounds__(512, 2) void gemm_wide_kernel(const dc_conv_desc d)
     constexpr int OC = BN;
     constexpr int PITCH = OC * 2 + 16;
     static_assert(BM * PITCH <= NST * STAGE, "output tile must fit in the stage buffers");
-    bf16x4 rr[TM][TN];
-    if (e_res) {
-#pragma unroll
-        for (int tm = 0; tm < TM; ++tm) {
-            const int m = m0 + wrow + tm * 16 + fr;
-#pragma unroll
-            for (int tn = 0; tn < TN; ++tn) {
-                const int nb = n0 + (wn * TN + tn) * 16 + 4 * fq;
-                rr[tm][tn] = (m < M && nb < d.Cout) ? *(const bf16x4*)((const bf16_t*)d.residual + (long long)m * d.Cout + nb)
-                                                    : bf16x4{(bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f};
-            }
-        }
-    }
+    bf16x4 rr[TM][TN] = {};
+    if (e_res) dc_epi_load_residual<TM, TN>(rr, d.residual, m0 + wrow + fr, M, nb0, d.Cout);
     f32x4 gs[TN], gq[TN];
 #pragma unroll
     for (int tn = 0; tn < TN; ++tn) gs[tn] = gq[tn] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -230,17 +212,9 @@ __global__ __launch_bounds__(512, 2) void gemm_wide_kernel(const dc_conv_desc d)
         if (e_geglu) {
 #pragma unroll
             for (int tp = 0; tp < TN / 2; ++tp) {
-                f32x4 h = acc[2 * tp][tm], g = acc[2 * tp + 1][tm];
-                if (e_ln) {
-                    h = dc_ln_fold(h, ln_mr[tm][0], ln_mr[tm][1], cs[2 * tp]);
-                    g = dc_ln_fold(g, ln_mr[tm][0], ln_mr[tm][1], cs[2 * tp + 1]);
-                }
-                h += bv[2 * tp];
-                g += bv[2 * tp + 1];
-                bf16x4 pk;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) pk[r] = (bf16_t)(h[r] * dc_gelu_erf(g[r]));
-                *(bf16x4*)(smem + row * PITCH + (((((wn * TN + 2 * tp) * 16) / 2 + 4 * fq) * 2) ^ dc_stage_swz(row))) = pk;
+                *(bf16x4*)(smem + row * PITCH + (((((wn * TN + 2 * tp) * 16) / 2 + 4 * fq) * 2) ^ dc_stage_swz(row))) =
+                    dc_epi_geglu(acc[2 * tp][tm], acc[2 * tp + 1][tm], e_flags, ln_mr[tm][0], ln_mr[tm][1], cs[2 * tp], cs[2 * tp + 1],
+                                 bv[2 * tp], bv[2 * tp + 1]);
             }
         } else {
             float st1 = 0.f, st2 = 0.f;
@@ -249,32 +223,13 @@ __global__ __launch_bounds__(512, 2) void gemm_wide_kernel(const dc_conv_desc d)
             for (int tn = 0; tn < TN; ++tn) {
                 const int nl = (wn * TN + tn) * 16 + 4 * fq;
                 const int nb = n0 + nl;
-                f32x4 v = acc[tn][tm];
-                if (e_ln) v = dc_ln_fold(v, ln_mr[tm][0], ln_mr[tm][1], cs[tn]);
-                v += bv[tn];
-                if (e_res) v = dc_scale_res(v, d.out_scale, rr[tm][tn]);
-                else v *= d.out_scale;
-                bf16x4 pk;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) pk[r] = (bf16_t)v[r];
-                *(bf16x4*)(smem + row * PITCH + ((nl * 2) ^ dc_stage_swz(row))) = pk;
-                if (e_stats) {                        // compile-time
-                    const float cm = nb < d.Cout ? 1.f : 0.f;
-                    st1 += cm * ((v[0] + v[1]) + (v[2] + v[3]));
-                    st2 += cm * ((v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]));
-                }
-                if (e_gnpart) {
-                    gs[tn] += rowmask * v;
-                    gq[tn] += rowmask * (v * v);
-                }
+                const f32x4 v = dc_epi_plain(acc[tn][tm], e_flags, 0, ln_mr[tm][0], ln_mr[tm][1], cs[tn], bv[tn], f32x4{0.f, 0.f, 0.f, 0.f},
+                                             d.out_scale, rr[tm][tn]);
+                *(bf16x4*)(smem + row * PITCH + ((nl * 2) ^ dc_stage_swz(row))) = dc_pack_bf16x4(v);
+                if (e_stats) dc_row_stats_add(st1, st2, v, nb < d.Cout ? 1.f : 0.f);      // compile-time
+                if (e_gnpart) dc_gn_part_add(gs[tn], gq[tn], v, rowmask);
             }
-            if (e_stats) {
-                st1 += __shfl_xor(st1, 16, 64);
-                st2 += __shfl_xor(st2, 16, 64);
-                st1 += __shfl_xor(st1, 32, 64);
-                st2 += __shfl_xor(st2, 32, 64);
-                if (fq == 0 && m < M) *(f32x2*)(d.stats_out + ((long long)m * (2 * n_tiles) + tile_n * 2 + wn) * 2) = f32x2{st1, st2};
-            }
+            if (e_stats) dc_row_stats_store(st1, st2, d.stats_out + ((long long)m * (2 * n_tiles) + tile_n * 2 + wn) * 2, fq == 0 && m < M);
         }
         __builtin_amdgcn_sched_barrier(0);            // one row group at a time (register pressure)
     }
@@ -293,12 +248,7 @@ __global__ __launch_bounds__(512, 2) void gemm_wide_kernel(const dc_conv_desc d)
     const int out_cols = e_geglu ? d.Cout >> 1 : d.Cout;
     const int col0 = e_geglu ? n0 >> 1 : n0;
     bf16_t* __restrict__ o = (bf16_t*)d.out;
-    constexpr int pieces = e_geglu ? OC / 16 : OC / 8;         // 16-byte pieces per staged row
-    for (int i = tid; i < BM * pieces; i += 512) {
-        const int row = i / pieces, pc = i - row * pieces;
-        const int m = m0 + row, c = col0 + pc * 8;
-        if (m < M && c < out_cols) *(u32x4*)(o + (long long)m * out_cols + c) = dc_stage_unswz(*(const u32x4*)(smem + row * PITCH + pc * 16), row);
-    }
+    dc_stage_store_rows<BM, PITCH, (e_geglu ? OC / 16 : OC / 8), 512>(smem, o, m0, M, col0, out_cols);      // 16-byte pieces per staged row
 }
 
 template <int TN, int EPI, int ST>

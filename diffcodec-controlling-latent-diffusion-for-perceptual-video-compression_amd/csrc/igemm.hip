@@ -11,7 +11,7 @@
 //   K-tile's global loads are issued before the current tile's MFMAs (one barrier per K-step).
 //   The MFMA computes the transposed tile (A-operand = weights, B-operand = pixels) so that each lane ends up
 //   with 4 consecutive output channels of one pixel -> 8-byte NHWC stores, float4 bias loads.
-#include "dc_conv_route.h"
+#include "dc_epilogue.h"
 
 namespace {
 
@@ -222,64 +222,8 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const dc_conv_desc d)
         buf ^= 1;
     }
 
-    const long long slab = (long long)d.N * d.Ho * d.Wo * d.Cout;   // elements per split-K slab
     // ---- epilogue: lane holds out[m = .. + (lane&15)][n = .. + 4*(lane>>4) + 0..3]
-    const int fr = lane & 15;
-    const int fq = lane >> 4;
-#pragma unroll
-    for (int tm = 0; tm < TM; ++tm) {
-        const int m = m0 + (wm * TM + tm) * 16 + fr;
-        if (m >= M) continue;
-        const int nimg = m / HoWo;
-        if (d.epilogue == 1) {
-            const int half = d.Cout >> 1;
-            bf16_t* __restrict__ o = (bf16_t*)d.out;
-#pragma unroll
-            for (int tp = 0; tp < TN / 2; ++tp) {
-                const int nb = n0 + (wn * TN + 2 * tp) * 16 + 4 * fq;      // packed row of the hidden half
-                if (nb >= d.Cout) continue;
-                f32x4 h = acc[2 * tp][tm];
-                f32x4 g = acc[2 * tp + 1][tm];
-                if (d.bias) {
-                    h += *(const f32x4*)(d.bias + nb);
-                    g += *(const f32x4*)(d.bias + nb + 16);
-                }
-                const int col = ((n0 + (wn * TN + 2 * tp) * 16) >> 1) + 4 * fq;
-                bf16x4 pk;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) pk[r] = (bf16_t)(h[r] * dc_gelu_erf(g[r]));
-                *(bf16x4*)(o + (long long)m * half + col) = pk;
-            }
-            continue;
-        }
-#pragma unroll
-        for (int tn = 0; tn < TN; ++tn) {
-            const int nb = n0 + (wn * TN + tn) * 16 + 4 * fq;
-            if (nb >= d.Cout) continue;
-            f32x4 v = acc[tn][tm];
-            const long long off = (long long)m * d.Cout + nb;
-            if (d.splitk > 1) {                                   // this split's own fp32 slab: plain stores, no atomics
-                *(f32x4*)(d.splitk_ws + (long long)blockIdx.y * slab + off) = v;
-                continue;
-            }
-            if (d.bias) v += *(const f32x4*)(d.bias + nb);
-            if (d.row_add) v += *(const f32x4*)(d.row_add + (long long)nimg * d.row_add_stride + nb);
-            if (d.act) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = dc_act(v[r], d.act);
-            }
-            if (d.residual) v = dc_scale_res(v, d.out_scale, *(const bf16x4*)((const bf16_t*)d.residual + off));
-            else v *= d.out_scale;
-            if (d.out_f32) {
-                *(f32x4*)((float*)d.out + off) = v;
-            } else {
-                bf16x4 pk;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) pk[r] = (bf16_t)v[r];
-                *(bf16x4*)((bf16_t*)d.out + off) = pk;
-            }
-        }
-    }
+    dc_epi_direct<TM, TN>(acc, d, m0, n0, wm, wn, lane & 15, lane >> 4);
 }
 
 // Second pass of split-K: sum of the per-split slabs -> bias / row_add / scale / residual -> output.
@@ -312,22 +256,10 @@ __global__ void splitk_finish_kernel(const dc_conv_desc d, long long total4)
         v += a3;
     }
     for (; k < d.splitk; ++k) v += *(const f32x4*)(slab + k * ss);
-    if (d.bias) v += bv;
-    if (d.row_add) v += ra;
-    if (d.act) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = dc_act(v[r], d.act);
-    }
-    if (d.residual) v = dc_scale_res(v, d.out_scale, rr);
-    else v *= d.out_scale;
-    if (d.out_f32) {
-        *(f32x4*)((float*)d.out + off) = v;
-    } else {
-        bf16x4 pk;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) pk[r] = (bf16_t)v[r];
-        *(bf16x4*)((bf16_t*)d.out + off) = pk;
-    }
+    v = dc_epi_plain(v, (d.bias ? DC_EPI_BIAS : 0) | (d.row_add ? DC_EPI_ROWADD : 0) | (d.residual ? DC_EPI_RES : 0), d.act, 0.f, 0.f, zero, bv, ra,
+                     d.out_scale, rr);
+    if (d.out_f32) *(f32x4*)((float*)d.out + off) = v;
+    else *(bf16x4*)((bf16_t*)d.out + off) = dc_pack_bf16x4(v);
 }
 
 template <int WM, int WN, int TM, int TN>

@@ -13,7 +13,9 @@ Plain module (imported by tests/test_edge_coverage.py on the CPU and tests/test_
   `CONV_SCRATCH_CASES` / `conv_scratch_kinds`: the conv cases whose launch is handed a scratch by ops.conv (ops._scratch).
 * `conv_key` / `attention_key`: the kernel instance a launch runs, from the dispatcher's own queries (dc_conv_route and
   dc_conv_instance, dc_attention_route).
-* `f32_conv_key`: the same for the fp32 extractor conv (dc_conv3x3_f32_route).
+* `conv_operands`: the seeded operands of a conv case, drawn once for tests/test_gpu_edges.py, tests/test_gpu_conv_bits.py and
+  tools/record_conv_bits.py.
+* `f32_conv_key`: the same as `conv_key` for the fp32 extractor conv (dc_conv3x3_f32_route).
 * `SPLAT_CASES`, `OCCLUSION_CASES`, `FLOW_RESIZE_CASES`, `FUSE_CASES`, `ELEMENTWISE_CASES`: the control stage (splat, occlusion
   mask, flow resize, fusion) and the plain elementwise launchers, with the generators of their inputs.
 * `SSIM_CASES`, `MS_SSIM_CASES`, `PSNR_CASES`, `METRIC_REFUSALS`: dc_ssim / dc_ms_ssim / dc_psnr at the window instances, tile,
@@ -491,6 +493,56 @@ CONV_CASES = (
     + _tile(8, (1026, 8, 8, 128, 128), 4, narrow=True, gn_opts=(False,))  # two 8x8 images per tile, 128-column tiles
     + _tile(8, (514, 8, 8, 128, 320), 5, narrow=True, gn_opts=(False,))   # two 8x8 images per tile
 )
+
+
+def conv_operands(ops, c, i, device="cuda"):
+    """(packed weights, {name: guarded operand}, guarded x1, keyword arguments of ops.conv) of case i of CONV_CASES (seed 1000 + i):
+    the one draw shared by tests/test_gpu_edges.py, tests/test_gpu_conv_bits.py and tools/record_conv_bits.py"""
+    BF, F32 = torch.bfloat16, torch.float32
+
+    def _g(shape, dtype, data, pitch=None):
+        g = Guarded(shape, dtype, device, pitch=pitch)
+        g.fill(data)
+        return g
+
+    gen = torch.Generator().manual_seed(1000 + i)
+    cin = c.c1 + c.c2
+    ho, wo, m = c.ho, c.wo, c.m
+    w = torch.randn(c.cout, cin, c.k, c.k, generator=gen) / math.sqrt(cin * c.k * c.k)
+    b = torch.randn(c.cout, generator=gen) * 0.1
+    ln = None
+    if c.ln is not None:
+        ln = (1 + 0.1 * torch.randn(cin, generator=gen), 0.1 * torch.randn(cin, generator=gen), 1e-5)
+    pc = ops.PackedConv(w, b, device, geglu=c.geglu, ln=ln, mfma_small_cout=c.cout < 16)
+    gw, gb = _g(tuple(pc.w.shape), BF, pc.w), _g(tuple(pc.bias.shape), F32, pc.bias)
+    pc.w, pc.bias = gw.view, gb.view
+    guards = {"w": gw, "bias": gb}
+    x1 = guards.setdefault("x1", _g((c.n, c.h, c.w, c.c1), BF, (torch.randn(c.n, c.h, c.w, c.c1, generator=gen) + 0.3).to(device)))
+    kw = dict(stride=c.stride, pad=c.pad, upsample=c.up, out_scale=c.out_scale, out_f32=c.out_f32, splitk=c.splitk, act=c.act,
+              gn_part=c.gn_part)
+    if c.c2:
+        kw["x2"] = guards.setdefault("x2", _g((c.n, c.h, c.w, c.c2), BF, torch.randn(c.n, c.h, c.w, c.c2, generator=gen).to(device))).view
+    if c.gn:
+        ab = torch.stack([1 + 0.2 * torch.randn(c.n, cin, generator=gen), 0.2 * torch.randn(c.n, cin, generator=gen)], 2)
+        kw["gn_ab"] = guards.setdefault("gn_ab", _g((c.n, cin, 2), F32, ab.to(device))).view
+        kw["gn_silu"] = c.gn_silu
+    if c.row_add:
+        kw["row_add"] = guards.setdefault("row_add", _g((c.n, c.cout), F32, torch.randn(c.n, c.cout, generator=gen).to(device),
+                                                          pitch=c.cout + 8)).view
+    if c.residual:
+        kw["residual"] = guards.setdefault("residual", _g((c.n, ho, wo, c.cout), BF,
+                                                          torch.randn(c.n, ho, wo, c.cout, generator=gen).to(device))).view
+    xr = x1.view.reshape(-1, c.c1).to(torch.float64)
+    if c.ln == "pairs":
+        mean = xr.mean(1)
+        rstd = 1.0 / torch.sqrt(xr.var(1, unbiased=False) + 1e-5)
+        kw["ln_stats"] = guards.setdefault("ln_stats", _g((m, 2), F32, torch.stack([mean, rstd], 1).float())).view
+    elif c.ln is not None:
+        parts = c.ln
+        bounds = [(p * cin) // parts for p in range(parts + 1)]
+        pr = torch.stack([torch.stack([xr[:, lo:hi].sum(1), (xr[:, lo:hi] ** 2).sum(1)], 1) for lo, hi in zip(bounds, bounds[1:])], 1)
+        kw["ln_partials"] = (guards.setdefault("ln_partials", _g((m, parts, 2), F32, pr.float())).view, 1e-5)
+    return pc, guards, x1, kw
 
 
 def conv_scratch_kinds(c, gn_part_out):

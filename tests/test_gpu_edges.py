@@ -64,49 +64,6 @@ def _capture(lib):
     return seen, real, call
 
 
-def _conv_operands(ops, c, i):
-    """(packed weights, {name: guarded operand}, guarded x1, keyword arguments of ops.conv) of case i of E.CONV_CASES (seed 1000 + i)"""
-    gen = torch.Generator().manual_seed(1000 + i)
-    cin = c.c1 + c.c2
-    ho, wo, m = c.ho, c.wo, c.m
-    cout_eff = c.cout // 2 if c.geglu else c.cout
-    w = torch.randn(c.cout, cin, c.k, c.k, generator=gen) / math.sqrt(cin * c.k * c.k)
-    b = torch.randn(c.cout, generator=gen) * 0.1
-    ln = None
-    if c.ln is not None:
-        ln = (1 + 0.1 * torch.randn(cin, generator=gen), 0.1 * torch.randn(cin, generator=gen), 1e-5)
-    pc = ops.PackedConv(w, b, DEV, geglu=c.geglu, ln=ln, mfma_small_cout=c.cout < 16)
-    gw, gb = _g(tuple(pc.w.shape), BF, pc.w), _g(tuple(pc.bias.shape), F32, pc.bias)
-    pc.w, pc.bias = gw.view, gb.view
-    guards = {"w": gw, "bias": gb}
-    x1 = guards.setdefault("x1", _g((c.n, c.h, c.w, c.c1), BF, (torch.randn(c.n, c.h, c.w, c.c1, generator=gen) + 0.3).to(DEV)))
-    kw = dict(stride=c.stride, pad=c.pad, upsample=c.up, out_scale=c.out_scale, out_f32=c.out_f32, splitk=c.splitk, act=c.act,
-              gn_part=c.gn_part)
-    if c.c2:
-        kw["x2"] = guards.setdefault("x2", _g((c.n, c.h, c.w, c.c2), BF, torch.randn(c.n, c.h, c.w, c.c2, generator=gen).to(DEV))).view
-    if c.gn:
-        ab = torch.stack([1 + 0.2 * torch.randn(c.n, cin, generator=gen), 0.2 * torch.randn(c.n, cin, generator=gen)], 2)
-        kw["gn_ab"] = guards.setdefault("gn_ab", _g((c.n, cin, 2), F32, ab.to(DEV))).view
-        kw["gn_silu"] = c.gn_silu
-    if c.row_add:
-        kw["row_add"] = guards.setdefault("row_add", _g((c.n, c.cout), F32, torch.randn(c.n, c.cout, generator=gen).to(DEV),
-                                                          pitch=c.cout + 8)).view
-    if c.residual:
-        kw["residual"] = guards.setdefault("residual", _g((c.n, ho, wo, c.cout), BF,
-                                                          torch.randn(c.n, ho, wo, c.cout, generator=gen).to(DEV))).view
-    xr = x1.view.reshape(-1, c.c1).to(torch.float64)
-    if c.ln == "pairs":
-        mean = xr.mean(1)
-        rstd = 1.0 / torch.sqrt(xr.var(1, unbiased=False) + 1e-5)
-        kw["ln_stats"] = guards.setdefault("ln_stats", _g((m, 2), F32, torch.stack([mean, rstd], 1).float())).view
-    elif c.ln is not None:
-        parts = c.ln
-        bounds = [(p * cin) // parts for p in range(parts + 1)]
-        pr = torch.stack([torch.stack([xr[:, lo:hi].sum(1), (xr[:, lo:hi] ** 2).sum(1)], 1) for lo, hi in zip(bounds, bounds[1:])], 1)
-        kw["ln_partials"] = (guards.setdefault("ln_partials", _g((m, parts, 2), F32, pr.float())).view, 1e-5)
-    return pc, guards, x1, kw
-
-
 @pytest.mark.parametrize("i", range(len(E.CONV_CASES)), ids=[c.label() for c in E.CONV_CASES])
 def test_conv_edge(ops, record, i):
     from diffcodec_amd import lib
@@ -114,7 +71,7 @@ def test_conv_edge(ops, record, i):
     assert E.conv_key(E.case_desc(c)) == c.key, c.label()
     ho, wo, m = c.ho, c.wo, c.m
     cout_eff = c.cout // 2 if c.geglu else c.cout
-    pc, guards, x1, kw = _conv_operands(ops, c, i)
+    pc, guards, x1, kw = E.conv_operands(ops, c, i, DEV)
     outs = []
     seen, real, call = _capture(lib)
     for rep in range(2):
@@ -162,7 +119,7 @@ def test_conv_scratch_of_any_contents(ops, monkeypatch, i):
     from diffcodec_amd import lib
     c = E.CONV_CASES[i]
     cout_eff = c.cout // 2 if c.geglu else c.cout
-    pc, guards, x1, kw = _conv_operands(ops, c, i)
+    pc, guards, x1, kw = E.conv_operands(ops, c, i, DEV)
     handed = []
     fill = [None]
     seen, real, call = _capture(lib)
