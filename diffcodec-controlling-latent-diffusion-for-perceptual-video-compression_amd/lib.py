@@ -169,6 +169,12 @@ PYRAMID_SIGNATURES = {
     "dc_pyramid_warp_grad_f32": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
 }
 
+# name -> argtypes of include/diffcodec_fdn_hip.h (csrc/fdn_grad.hip)
+FDN_SIGNATURES = {
+    "dc_fdn_f32": [vp, vp, i64, vp, i64, vp, vp, vp, i32, i32, i32, i32, f32, vp],
+    "dc_fdn_grad_f32": [vp, vp, vp, i64, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp],
+}
+
 # the whole C surface: (header under include/, its table), one pair per launcher family.  load() binds what is listed here and
 # tests/test_abi.py holds every pair to its header; a new family adds a header, a table and one line here.
 ABI = (
@@ -178,6 +184,7 @@ ABI = (
     ("diffcodec_guide_hip.h", GUIDE_SIGNATURES),
     ("diffcodec_train_hip.h", TRAIN_SIGNATURES),
     ("diffcodec_pyramid_hip.h", PYRAMID_SIGNATURES),
+    ("diffcodec_fdn_hip.h", FDN_SIGNATURES),
 )
 
 
