@@ -20,7 +20,6 @@ def _meta(family, shape, flops, nbytes):
     return (family, shape, float(flops), float(nbytes)) if lib.TIMER is not None else None
 
 
-
 GN_DIRECT_MAX_PIXELS = 256   # maps up to 16x16: one-launch GroupNorm statistics
 # GroupNorm statistics emitted by the producing conv / GEMM epilogue instead of a read pass.  These switches are plain module
 # constants: tools/ assign them for an A/B, nothing on the product path reads the environment.
@@ -179,14 +178,103 @@ def conv_instance(d):
     return dict(zip(INSTANCE_ARGS[kernel], info[1:]), kernel=kernel)
 
 
+def conv_out_hw(h, w, ksize, stride, pad, upsample):
+    """(Ho, Wo) of a k = 1 | 3 conv over an h x w map (doubled first by the fused upsample): the output-size formula, once."""
+    if ksize == 1:
+        return h, w
+    hin, win = (2 * h, 2 * w) if upsample else (h, w)
+    return (hin + (2 if pad else 1) - 3) // stride + 1, (win + (2 if pad else 1) - 3) // stride + 1
+
+
+ConvPlan = collections.namedtuple("ConvPlan", "desc out_shape out_dtype m scratch meta")
+
+
+def conv_plan(n, h, w, c1, c2=0, *, cout, ksize=1, geglu=False, ln_folded=False, bias=True, gn_batch=0, gn_silu=False,
+              row_add_stride=None, residual=False, stride=1, pad=1, upsample=False, out_scale=1.0, out_f32=False, act=0, splitk=None,
+              ln=None, ln_eps=0.0, stats_out=False, gn_part=False):
+    """Everything `conv` decides about one dc_conv_igemm_bf16 launch, from shapes and flags alone (host code only: needs the library,
+    not a GPU, and no tensors).  Of the weights: cout, ksize, geglu, ln_folded (they carry a folded LayerNorm), bias (they have one).
+    gn_batch: rows of `gn_ab`, 0 = none.  row_add_stride: None = no `row_add`.  splitk: None = the library picks.  ln: None, "pairs"
+    (`ln_stats`) or the number of raw partials per row (`ln_partials`, with their ln_eps).  residual, stats_out: the operand is there.
+    gn_part: asked for.  -> ConvPlan:
+      desc       the descriptor as the launch will have it in every non-pointer field (the split explicit); a pointer field is null
+                 or a placeholder, so `conv_route(desc)` and `conv_instance(desc)` answer for the launch
+      out_shape, out_dtype, m    the output, and its rows N * Ho * Wo
+      scratch    [(kind, shape)] to ask `_scratch` for, in this order: "splitk", "ln_scratch", "gn_part"
+      meta       the timer's (family, shape label, algorithmic FLOPs, algorithmic HBM bytes) while `lib.TIMER` is set, else None"""
+    if (ln is None) == bool(ln_folded):
+        raise ValueError("ln_stats must be given exactly when the weights carry a folded LayerNorm")
+    P = 16                                  # placeholder of a pointer the launch will fill: the queries read flags, not memory
+    ho, wo = conv_out_hw(h, w, ksize, stride, pad, upsample)
+    m = n * ho * wo
+    ln_parts = 0 if ln in (None, "pairs") else int(ln)
+    if ln is not None or stats_out or (geglu and splitk is None):
+        splitk = 1                          # the folded LayerNorm, the row statistics and GEGLU live in the unsplit bf16 epilogue
+    d = ConvDesc(x1=P, x2=P if c2 else 0, w=P, bias=P if bias else 0, gn_ab=P if gn_batch else 0, row_add=0 if row_add_stride is None else P,
+                 residual=P if residual else 0, out=P, N=n, H=h, W=w, C1=c1, C2=c2, Cout=cout, ksize=ksize, stride=stride, pad=int(pad),
+                 upsample=int(upsample), Ho=ho, Wo=wo, gn_silu=int(gn_silu), epilogue=1 if geglu else 0, out_f32=int(out_f32),
+                 out_scale=float(out_scale), splitk=DC_SPLITK_AUTO if splitk is None else int(splitk or 1), gn_batch=int(gn_batch), act=int(act),
+                 row_add_stride=int(row_add_stride or 0), ln_stats=P if ln is not None else 0, ln_colsum=P if ln is not None else 0,
+                 stats_out=P if stats_out else 0, ln_parts=ln_parts, ln_eps=float(ln_eps) if ln_parts else 0.0)
+    route = None                            # the library's decision for `d`, while `d` is as it was asked: kept for the timer's label
+    if splitk is None:                      # the library picks the split (csrc/igemm.hip: splitk_pick), from the descriptor without scratch
+        route = conv_route(d)
+        d.splitk = splitk = route.splitk
+    scratch = []
+    if splitk > 1:
+        d.splitk_ws = P
+        scratch.append(("splitk", (splitk, m, cout)))              # the bytes dc_conv_igemm_ws_bytes states
+    if ln_parts > 0:
+        # scratch for (mean, rstd) only where the dispatcher runs the finalize pass first (the row-panel kernel finalizes in its
+        # prologue): the library's own routing decides, not a Python restatement of it
+        route = route or conv_route(d)
+        if route.ln_first:
+            d.ln_scratch = P
+            scratch.append(("ln_scratch", (m, 2)))
+    if gn_part and GN_EPILOGUE_STATS and not out_f32 and not geglu and splitk == 1 and ln is None:
+        chunks = lib.load().dc_conv_gn_part_chunks(d)
+        if chunks > 0:                      # the launch can emit them; otherwise the request is ignored
+            d.gn_part_out = P
+            scratch.append(("gn_part", (chunks, n, cout, 2)))
+            route = None                    # (asked without the statistics epilogue)
+    cout_eff, meta = cout // 2 if geglu else cout, None
+    if lib.TIMER is not None:
+        route = route or conv_route(d)
+        kk = (c1 + c2) * ksize * ksize
+        fam = {"conv3x3_tile": "conv3x3_tile_kernel (3x3 stride-1 halo-tile conv)", "igemm": "igemm_kernel (strided / GN-on-load gather GEMM)"}.get(
+            route.kernel, "gemm_dma_kernel + gemm_wide_kernel + gemm_p8_kernel + gemm_rowpanel_kernel (1x1 conv / linear GEMM family)")
+        # algorithmic bytes: every operand once — activations (low-res input for the fused upsample), weights, output, residual
+        nbytes = 2.0 * (n * h * w * (c1 + c2) + cout * kk + m * cout_eff * (2 if out_f32 else 1) + (m * cout if residual else 0))
+        meta = _meta(fam, f"{ksize}x{ksize} s{stride} up{int(upsample)} M={m} N={cout} K={kk} gn={int(gn_batch > 0)} geglu={int(geglu)} "
+                          f"ln={int(ln is not None)} splitk={splitk}", 2.0 * m * cout * kk, nbytes)
+    return ConvPlan(d, (n, ho, wo, cout_eff), F32 if out_f32 else BF16, m, scratch, meta)
+
+
 @functools.lru_cache(maxsize=None)
 def rowpanel_takes(rows, rows_per_sample, cin, cout):
     """Does a 1x1 launch with a bias and a GroupNorm affine on load (`gn_ab` without SiLU) go to the row-panel kernel (the K = 320
-    kernel that keeps a 256-row panel in registers, the only GEMM of the family that can apply the affine)?  The library's route
-    of a placeholder descriptor of that shape, remembered per shape."""
-    d = ConvDesc(x1=16, w=16, out=16, bias=16, gn_ab=16, N=rows // rows_per_sample, H=1, W=rows_per_sample, C1=cin, Cout=cout, ksize=1,
-                 stride=1, Ho=1, Wo=rows_per_sample, out_scale=1.0, splitk=1, gn_batch=rows // rows_per_sample)
-    return conv_route(d).kernel == "gemm_rowpanel"
+    kernel that keeps a 256-row panel in registers, the only GEMM of the family that can apply the affine)?  The route of that
+    launch's plan, remembered per shape."""
+    n = rows // rows_per_sample
+    return conv_route(conv_plan(n, 1, rows_per_sample, cin, cout=cout, gn_batch=n, splitk=1).desc).kernel == "gemm_rowpanel"
+
+
+def _conv_small_cin(x1, pc, stride, pad, out_scale):
+    n, h, w, c1 = x1.shape
+    ho, wo = conv_out_hw(h, w, pc.ksize, stride, pad, False)
+    out = torch.empty((n, ho, wo, pc.cout), device=x1.device, dtype=BF16)
+    lib.call("dc_conv_small_cin_bf16", x1.data_ptr(), pc.w.data_ptr(), _ptr(pc.bias), out.data_ptr(), n, h, w, c1,
+             pc.cout, pc.ksize, stride, pad if pc.ksize == 3 else 0, ho, wo, _stream())
+    if out_scale != 1.0:
+        raise ValueError("out_scale unsupported on the small-cin path")
+    return out
+
+
+def _conv_small_cout(x1, pc, gn_ab, gn_silu, out_f32):
+    out = torch.empty((*x1.shape[:3], pc.cout), device=x1.device, dtype=F32 if out_f32 else BF16)
+    lib.call("dc_conv_small_cout_bf16", x1.data_ptr(), pc.w.data_ptr(), _ptr(pc.bias), _ptr(gn_ab), int(gn_silu),
+             0 if gn_ab is None else gn_ab.shape[0], out.data_ptr(), int(out_f32), *x1.shape, pc.cout, pc.ksize, _stream())
+    return out
 
 
 def conv(x1, pc, *, x2=None, gn_ab=None, gn_silu=False, row_add=None, residual=None, stride=1, pad=1,
@@ -212,108 +300,53 @@ def conv(x1, pc, *, x2=None, gn_ab=None, gn_silu=False, row_add=None, residual=N
         c2 = x2.shape[3]
     assert c1 + c2 == pc.cin, f"channel mismatch {c1}+{c2} vs {pc.cin}"
     k = pc.ksize
-    if k == 1:
-        ho, wo = h, w
-    else:
-        hin, win = (2 * h, 2 * w) if upsample else (h, w)
-        ho = (hin + (2 if pad else 1) - 3) // stride + 1
-        wo = (win + (2 if pad else 1) - 3) // stride + 1
     if pc.kind == "small_cin":
         assert x2 is None and gn_ab is None and residual is None and row_add is None and not upsample and not out_f32 and out is None
-        out = torch.empty((n, ho, wo, pc.cout), device=x1.device, dtype=BF16)
-        lib.call("dc_conv_small_cin_bf16", x1.data_ptr(), pc.w.data_ptr(), _ptr(pc.bias), out.data_ptr(), n, h, w, c1,
-                 pc.cout, k, stride, pad if k == 3 else 0, ho, wo, _stream())
-        if out_scale != 1.0:
-            raise ValueError("out_scale unsupported on the small-cin path")
-        return out
+        return _conv_small_cin(x1, pc, stride, pad, out_scale)
     if pc.kind == "small_cout":
         assert x2 is None and residual is None and row_add is None and not upsample and stride == 1 and (k == 1 or pad == 1) and out is None
-        out = torch.empty((n, h, w, pc.cout), device=x1.device, dtype=F32 if out_f32 else BF16)
-        gb = 0 if gn_ab is None else gn_ab.shape[0]
-        lib.call("dc_conv_small_cout_bf16", x1.data_ptr(), pc.w.data_ptr(), _ptr(pc.bias), _ptr(gn_ab), int(gn_silu), gb,
-                 out.data_ptr(), int(out_f32), n, h, w, c1, pc.cout, k, _stream())
-        return out
-    cout_eff = pc.cout // 2 if pc.geglu else pc.cout
-    if out is None:
-        out = torch.empty((n, ho, wo, cout_eff), device=x1.device, dtype=F32 if out_f32 else BF16)
-    else:
-        assert out.is_contiguous() and out.numel() == n * ho * wo * cout_eff and out.dtype == (F32 if out_f32 else BF16)
-        out = out.view(n, ho, wo, cout_eff)
-    m = n * ho * wo
-    ln_parts, ln_eps, ln_scratch = 0, 0.0, None
+        return _conv_small_cout(x1, pc, gn_ab, gn_silu, out_f32)
+    ln, ln_eps = None if ln_stats is None else "pairs", 0.0
     if ln_partials is not None:
         if ln_stats is not None:
             raise ValueError("pass ln_stats or ln_partials, not both")
         ln_stats, ln_eps = ln_partials
-        _chk(ln_stats, F32, "ln_partials")
-        assert ln_stats.dim() == 3 and ln_stats.shape[0] == m and ln_stats.shape[2] == 2
-        ln_parts = int(ln_stats.shape[1])
-    if ln_stats is not None or stats_out is not None:
-        splitk = 1                          # the folded LayerNorm / row statistics live in the unsplit bf16 epilogue
-    elif pc.geglu and splitk is None:
-        splitk = 1                          # ... and so does GEGLU
+        assert ln_stats.dim() == 3 and ln_stats.shape[1] > 0 and ln_stats.shape[2] == 2
+        ln = int(ln_stats.shape[1])
     if gn_ab is not None:
         _chk(gn_ab, F32, "gn_ab")
         assert gn_ab.shape[1] == pc.cin
+    if row_add is not None:
+        assert row_add.dtype == F32 and row_add.is_cuda and row_add.shape == (n, pc.cout) and row_add.stride(1) == 1
+    p = conv_plan(n, h, w, c1, c2, cout=pc.cout, ksize=k, geglu=pc.geglu, ln_folded=pc.ln_eps is not None, bias=pc.bias is not None,
+                  gn_batch=0 if gn_ab is None else gn_ab.shape[0], gn_silu=gn_silu, row_add_stride=None if row_add is None else row_add.stride(0),
+                  residual=residual is not None, stride=stride, pad=pad, upsample=upsample, out_scale=out_scale, out_f32=out_f32, act=act,
+                  splitk=splitk, ln=ln, ln_eps=ln_eps, stats_out=stats_out is not None, gn_part=gn_part)
+    m = p.m
+    if out is None:
+        out = torch.empty(p.out_shape, device=x1.device, dtype=p.out_dtype)
+    else:
+        assert out.is_contiguous() and out.numel() == m * p.out_shape[3] and out.dtype == p.out_dtype
+        out = out.view(p.out_shape)
     if residual is not None:
         _chk(residual, BF16, "residual")
         assert residual.numel() == m * pc.cout
-    if (ln_stats is None) != (pc.ln_eps is None):
-        raise ValueError("ln_stats must be given exactly when the weights carry a folded LayerNorm")
     if ln_stats is not None:
-        _chk(ln_stats, F32, "ln_stats")
-        assert (ln_parts > 0 or tuple(ln_stats.shape) == (m, 2)) and x2 is None and gn_ab is None and k == 1
+        _chk(ln_stats, F32, "ln_partials" if ln_partials is not None else "ln_stats")
+        assert ln_stats.shape[0] == m and (ln != "pairs" or tuple(ln_stats.shape) == (m, 2)) and x2 is None and gn_ab is None and k == 1
     if stats_out is not None:
         _chk(stats_out, F32, "stats_out")
         assert tuple(stats_out.shape) == (m, row_stats_parts(pc.cout), 2) and k == 1 and not pc.geglu and not out_f32
-    ras = 0
-    if row_add is not None:
-        assert row_add.dtype == F32 and row_add.is_cuda and row_add.shape == (n, pc.cout) and row_add.stride(1) == 1
-        ras = row_add.stride(0)
-    d = ConvDesc(x1=x1.data_ptr(), x2=_ptr(x2), w=pc.w.data_ptr(), bias=_ptr(pc.bias), gn_ab=_ptr(gn_ab),
-                 row_add=_ptr(row_add), residual=_ptr(residual), out=out.data_ptr(), splitk_ws=0,
-                 N=n, H=h, W=w, C1=c1, C2=c2, Cout=pc.cout, ksize=k, stride=stride, pad=int(pad), upsample=int(upsample),
-                 Ho=ho, Wo=wo, gn_silu=int(gn_silu), epilogue=1 if pc.geglu else 0, out_f32=int(out_f32),
-                 out_scale=float(out_scale), splitk=DC_SPLITK_AUTO if splitk is None else int(splitk or 1),
-                 gn_batch=0 if gn_ab is None else gn_ab.shape[0], act=int(act), row_add_stride=int(ras), ln_stats=_ptr(ln_stats), ln_colsum=_ptr(pc.colsum if ln_stats is not None else None),
-                 stats_out=_ptr(stats_out), gn_part_out=0, ln_parts=ln_parts, ln_eps=float(ln_eps), ln_scratch=_ptr(ln_scratch))
-    route = None                            # the library's decision for `d`, while `d` is as it was asked
-    if splitk is None:                      # the library picks the split (csrc/igemm.hip: splitk_pick); from here on it is explicit
-        route = conv_route(d)
-        d.splitk = splitk = route.splitk
-    ws = _scratch((splitk, m, pc.cout), x1.device, "splitk") if splitk > 1 else None
-    d.splitk_ws = _ptr(ws)
-    if ln_parts > 0 and route is None:
-        route = conv_route(d)
-    if ln_parts > 0 and route.ln_first:
-        # scratch for (mean, rstd) only where the dispatcher runs the finalize pass first (the row-panel kernel finalizes in its
-        # prologue): the library's own routing decides, not a Python restatement of it
-        ln_scratch = _scratch((m, 2), x1.device, "ln_scratch")
-        d.ln_scratch = ln_scratch.data_ptr()
-    part = None
-    if gn_part and GN_EPILOGUE_STATS and not out_f32 and not pc.geglu and splitk == 1 and ln_stats is None:
-        chunks = lib.load().dc_conv_gn_part_chunks(d)
-        if chunks > 0:
-            part = _scratch((chunks, n, pc.cout, 2), x1.device, "gn_part")
-            d.gn_part_out = part.data_ptr()
-            route = None                    # (asked without the statistics epilogue)
-    meta = None
-    if lib.TIMER is not None:
-        kk = pc.cin * k * k
-        kernel = (conv_route(d) if route is None else route).kernel
-        if kernel == "conv3x3_tile":
-            fam = "conv3x3_tile_kernel (3x3 stride-1 halo-tile conv)"
-        elif kernel == "igemm":
-            fam = "igemm_kernel (strided / GN-on-load gather GEMM)"
-        else:
-            fam = "gemm_dma_kernel + gemm_wide_kernel + gemm_p8_kernel + gemm_rowpanel_kernel (1x1 conv / linear GEMM family)"
-        # algorithmic bytes: every operand once — activations (low-res input for the fused upsample), weights, output, residual
-        nbytes = 2.0 * (n * h * w * pc.cin + pc.cout * kk + m * cout_eff * (2 if out_f32 else 1) + (m * pc.cout if residual is not None else 0))
-        meta = _meta(fam, f"{k}x{k} s{stride} up{int(upsample)} M={m} N={pc.cout} K={kk} gn={int(gn_ab is not None)} geglu={int(pc.geglu)} "
-                          f"ln={int(ln_stats is not None)} splitk={splitk}", 2.0 * m * pc.cout * kk, nbytes)
-    lib.call("dc_conv_igemm_bf16", d, _stream(), meta=meta)
-    if part is not None:
-        out.gn_part = part
+    d = ConvDesc.from_buffer_copy(p.desc)   # the plan's descriptor, with the pointers of this launch
+    d.x1, d.x2, d.w, d.bias, d.gn_ab, d.row_add = x1.data_ptr(), _ptr(x2), pc.w.data_ptr(), _ptr(pc.bias), _ptr(gn_ab), _ptr(row_add)
+    d.residual, d.out, d.stats_out, d.ln_stats = _ptr(residual), out.data_ptr(), _ptr(stats_out), _ptr(ln_stats)
+    d.ln_colsum = _ptr(pc.colsum if ln_stats is not None else None)
+    got = {what: _scratch(shape, x1.device, what) for what, shape in p.scratch}
+    if got:
+        d.splitk_ws, d.ln_scratch, d.gn_part_out = _ptr(got.get("splitk")), _ptr(got.get("ln_scratch")), _ptr(got.get("gn_part"))
+    lib.call("dc_conv_igemm_bf16", d, _stream(), meta=p.meta)
+    if "gn_part" in got:
+        out.gn_part = got["gn_part"]
     return out
 
 

@@ -10,9 +10,9 @@ Plain module (imported by tests/test_edge_coverage.py on the CPU and tests/test_
 * `run_on_fills`: one launcher on a guarded workspace of exactly its dc_*_ws_bytes, under three fills of the workspace (the NaN
   pattern, zeros, what a launch on other inputs left): guards, nothing unwritten, finite, bitwise equal outputs.  The GPU test of
   every launcher that takes a caller-owned workspace goes through it (tests/test_edge_coverage.py keeps the census).
-  `CONV_SCRATCH_CASES` / `conv_scratch_kinds`: the conv cases whose launch is handed a scratch by ops.conv (ops._scratch).
+  `CONV_SCRATCH_CASES`: the conv cases whose launch is handed a scratch by ops.conv (ops._scratch); which ones: `case_plan(c).scratch`.
 * `conv_key` / `attention_key`: the kernel instance a launch runs, from the dispatcher's own queries (dc_conv_route and
-  dc_conv_instance, dc_attention_route).
+  dc_conv_instance, dc_attention_route).  `case_plan`: ops.conv_plan of a conv case, the descriptor and scratches of its launch.
 * `conv_operands`: the seeded operands of a conv case, drawn once for tests/test_gpu_edges.py, tests/test_gpu_conv_bits.py and
   tools/record_conv_bits.py.
 * `f32_conv_key`: the same as `conv_key` for the fp32 extractor conv (dc_conv3x3_f32_route).
@@ -24,10 +24,13 @@ Plain module (imported by tests/test_edge_coverage.py on the CPU and tests/test_
 * `CONV_CASES`, `ATTN_CASES`, `NORM_CASES`, `F32_CONV_CASES`: the tables.  Every conv / attention case declares the instance it
   targets; tests/test_edge_coverage.py proves that every instance the dispatcher can reach has a case and that every case routes
   where it says."""
+import ctypes
 import math
 from dataclasses import dataclass
 
 import torch
+
+from diffcodec_amd import ops as _ops
 
 GUARD = 256                                   # guard elements on each side of a view
 NAN_BITS = {torch.bfloat16: 0x7FA5, torch.float32: 0x7FA5A5A5, torch.uint8: 0xA5,    # uint8 has no NaN: the byte 0xA5 stands in
@@ -203,23 +206,11 @@ class ConvCase:
     splitk: int = 1
     note: str = ""
 
-    @property
-    def ho(self):
-        if self.k == 1:
-            return self.h
-        hin = 2 * self.h if self.up else self.h
-        return (hin + (2 if self.pad else 1) - 3) // self.stride + 1
-
-    @property
-    def wo(self):
-        if self.k == 1:
-            return self.w
-        win = 2 * self.w if self.up else self.w
-        return (win + (2 if self.pad else 1) - 3) // self.stride + 1
-
-    @property
-    def m(self):
-        return self.n * self.ho * self.wo
+    out_hw = property(lambda s: _ops.conv_out_hw(s.h, s.w, s.k, s.stride, s.pad, s.up))
+    ho = property(lambda s: s.out_hw[0])
+    wo = property(lambda s: s.out_hw[1])
+    m = property(lambda s: s.n * s.ho * s.wo)
+    row_add_pitch = property(lambda s: s.cout + 8)      # row_add is a pitched view: its stride is part of the descriptor
 
     def label(self):
         f = [n for n in ("gn", "gn_silu", "row_add", "residual", "out_f32", "geglu", "stats_out", "gn_part", "up") if getattr(self, n)]
@@ -231,24 +222,18 @@ class ConvCase:
                 f"M={self.m} [{','.join(f)}]")
 
 
-def case_desc(c):
-    """The dc_conv_desc ops.conv builds for case `c` (dummy non-null pointers: the route query reads flags, not memory)."""
-    from diffcodec_amd import lib
-    from diffcodec_amd.lib import ConvDesc
-    P = 16
-    ln_parts = c.ln if isinstance(c.ln, int) else 0
-    splitk = 1 if (c.ln is not None or c.stats_out) else c.splitk
-    d = ConvDesc(x1=P, x2=P if c.c2 else 0, w=P, bias=P, gn_ab=P if c.gn else 0, row_add=P if c.row_add else 0,
-                 residual=P if c.residual else 0, out=P, splitk_ws=P if splitk > 1 else 0, N=c.n, H=c.h, W=c.w, C1=c.c1, C2=c.c2,
-                 Cout=c.cout, ksize=c.k, stride=c.stride, pad=int(c.pad), upsample=int(c.up), Ho=c.ho, Wo=c.wo,
-                 gn_silu=int(c.gn_silu), epilogue=1 if c.geglu else 0, out_f32=int(c.out_f32), out_scale=float(c.out_scale),
-                 splitk=int(splitk), gn_batch=c.n if c.gn else 0, act=int(c.act), row_add_stride=0,
-                 ln_stats=P if c.ln is not None else 0, ln_colsum=P if c.ln is not None else 0, stats_out=P if c.stats_out else 0,
-                 gn_part_out=0, ln_parts=ln_parts, ln_eps=1e-5 if ln_parts else 0.0, ln_scratch=0)
-    if c.gn_part and not c.out_f32 and not c.geglu and splitk == 1 and c.ln is None:
-        if lib.load().dc_conv_gn_part_chunks(d) > 0:
-            d.gn_part_out = P
-    return d
+def case_plan(c):
+    """ops.conv_plan of the launch ops.conv makes for case `c` with the operands of `conv_operands` (needs the library, not a GPU)"""
+    return _ops.conv_plan(c.n, c.h, c.w, c.c1, c.c2, cout=c.cout, ksize=c.k, geglu=c.geglu, ln_folded=c.ln is not None, gn_batch=c.n * c.gn,
+                          gn_silu=c.gn_silu, row_add_stride=c.row_add_pitch if c.row_add else None, residual=c.residual, stride=c.stride,
+                          pad=c.pad, upsample=c.up, out_scale=c.out_scale, out_f32=c.out_f32, act=c.act, splitk=c.splitk, ln=c.ln, ln_eps=1e-5,
+                          stats_out=c.stats_out, gn_part=c.gn_part)
+
+
+def desc_fields(d):
+    """(every non-pointer field of a dc_conv_desc by name, the names of its non-null pointer fields): what a plan and a launch share"""
+    fields = type(d)._fields_
+    return ({n: getattr(d, n) for n, t in fields if t is not ctypes.c_void_p}, [n for n, t in fields if t is ctypes.c_void_p and getattr(d, n)])
 
 
 def conv_key(d):
@@ -259,8 +244,7 @@ def conv_key(d):
       gemm_rowpanel GN (GroupNorm partials out);
       gemm_wide     ST (statistics outputs of the epi 1 / 2 kernels) and TN (160- or 128-column tile);
       igemm         KS3 (3x3 gather), GN (GroupNorm on load)."""
-    from diffcodec_amd import ops
-    r, t = ops.conv_route(d), ops.conv_instance(d)
+    r, t = _ops.conv_route(d), _ops.conv_instance(d)
     key = (r.kernel, r.variant, r.epi, r.splitk > 1, r.ln_first)
     if r.kernel == "conv3x3_tile":
         key += (("gn", bool(t["GN"])), ("up", bool(d.upsample)), ("narrow", d.Wo < 16), ("tn", t["TN"]), ("nst", t["NSTB"]),
@@ -282,14 +266,12 @@ def enumerate_conv_keys():
     """Every instance key dc_conv_route yields over a descriptor grid that spans each routing flag: 1x1 shapes in the regime of
     each GEMM kernel x every epilogue / statistics / LayerNorm / split-K option, and 3x3 shapes (tile-aligned, narrow 8x8, odd,
     strided, upsampled, Cout <= 32) x GroupNorm on load, concat, epilogue and split-K options.  -> {key: example descriptor label}"""
-    from diffcodec_amd import lib
     keys = {}
 
     def add(c):
-        d = case_desc(c)
         try:
-            k = conv_key(d)
-        except lib.HipLaunchError:
+            k = conv_key(case_plan(c).desc)
+        except _ops.lib.HipLaunchError:
             return
         keys.setdefault(k, c.label())
 
@@ -528,7 +510,7 @@ def conv_operands(ops, c, i, device="cuda"):
         kw["gn_silu"] = c.gn_silu
     if c.row_add:
         kw["row_add"] = guards.setdefault("row_add", _g((c.n, c.cout), F32, torch.randn(c.n, c.cout, generator=gen).to(device),
-                                                          pitch=c.cout + 8)).view
+                                                          pitch=c.row_add_pitch)).view
     if c.residual:
         kw["residual"] = guards.setdefault("residual", _g((c.n, ho, wo, c.cout), BF,
                                                           torch.randn(c.n, ho, wo, c.cout, generator=gen).to(device))).view
@@ -545,16 +527,9 @@ def conv_operands(ops, c, i, device="cuda"):
     return pc, guards, x1, kw
 
 
-def conv_scratch_kinds(c, gn_part_out):
-    """the scratches ops.conv allocates (ops._scratch) for a case, by its own rules: the split-K slabs when it splits (never with a
-    folded LayerNorm or row statistics out), (mean, rstd) when the route finalizes the LayerNorm first (key[4]), the GroupNorm
-    partials when the launch emits them (`gn_part_out`: dc_conv_gn_part_chunks > 0, known only with the library)"""
-    split = c.splitk > 1 and c.ln is None and not c.stats_out
-    return ["splitk"] * split + ["ln_scratch"] * bool(c.key[4]) + ["gn_part"] * bool(gn_part_out)
-
-
-# the cases whose launch is handed a scratch by ops.conv (a GroupNorm-partials request the launch cannot honour asks for none)
-CONV_SCRATCH_CASES = [i for i, c in enumerate(CONV_CASES) if conv_scratch_kinds(c, c.gn_part)]
+# the cases whose launch is handed a scratch by ops.conv, selected without the library from what each case declares: split-K,
+# LayerNorm finalize first (key[3], key[4]), GroupNorm partials asked for.  tests/test_edge_coverage.py holds the selection to the plans.
+CONV_SCRATCH_CASES = [i for i, c in enumerate(CONV_CASES) if c.key[3] or c.key[4] or c.gn_part]
 
 
 # ------------------------------------------------------------------------------------------ attention instances
@@ -563,8 +538,7 @@ HEAD_DIMS = (8, 16, 32, 40, 64, 80, 128, 160)
 
 def attention_key(b, heads, nq, nk, d):
     """(D, QB, SHORT, RAGGED, PP) of the attn_kernel instance dc_attention_bf16 launches (dc_attention_route)"""
-    from diffcodec_amd import ops
-    return tuple(int(v) for v in ops.attention_route(b, heads, nq, nk, d))
+    return tuple(int(v) for v in _ops.attention_route(b, heads, nq, nk, d))
 
 
 def enumerate_attention_keys():
@@ -690,13 +664,9 @@ class SmallCase:
     gn: bool = False
     out_f32: bool = False
 
-    @property
-    def ho(self):
-        return self.h if self.k == 1 else (self.h + (2 if self.pad else 1) - 3) // self.stride + 1
-
-    @property
-    def wo(self):
-        return self.w if self.k == 1 else (self.w + (2 if self.pad else 1) - 3) // self.stride + 1
+    out_hw = property(lambda s: _ops.conv_out_hw(s.h, s.w, s.k, s.stride, s.pad, False))
+    ho = property(lambda s: s.out_hw[0])
+    wo = property(lambda s: s.out_hw[1])
 
     @property
     def strip_kernel(self):
@@ -755,8 +725,7 @@ class F32ConvCase:
 
 
 def f32_conv_route(cin, h, w, cout, stride):
-    from diffcodec_amd import ops
-    return ops.conv3x3_f32_route(cin, h, w, cout, stride)
+    return _ops.conv3x3_f32_route(cin, h, w, cout, stride)
 
 
 def f32_conv_key(cin, h, w, cout, stride):

@@ -34,14 +34,6 @@ def _overlaps(a, b):
     return a0 < b1 and b0 < a1
 
 
-def _shape_label(x1, pc, kw, m, splitk):
-    """same string form as the in-situ kernel table (ops.conv's timer label)"""
-    k = pc.ksize
-    return (f"{k}x{k} s{kw.get('stride', 1)} up{int(bool(kw.get('upsample', False)))} M={m} N={pc.cout} K={pc.cin * k * k} "
-            f"gn={int(kw.get('gn_ab') is not None)} geglu={int(pc.geglu)} ln={int(kw.get('ln_stats') is not None or kw.get('ln_partials') is not None)} "
-            f"splitk={splitk}")
-
-
 class LaunchShadow:
     def __init__(self, record=None, prefix="shadow"):
         self.stats = {}            # key -> [count, worst ratio]
@@ -112,7 +104,7 @@ class LaunchShadow:
             yr = y.reshape(m, c)[rows.to(y.device)]
             flags = ",".join(f for f in ("x2", "gn_ab", "row_add", "residual", "ln_stats", "ln_partials", "stats_out") if kw.get(f) is not None)
             flags += (",gn_silu" if kw.get("gn_silu") else "") + (",geglu" if pc.geglu else "") + (f",act={kw['act']}" if kw.get("act") else "")
-            what = f"{_shape_label(x1, pc, kw, m, rt.splitk if rt else 1)} [{flags}]"
+            what = f"{pc.ksize}x{pc.ksize} {tuple(x1.shape)} -> {tuple(y.shape)} splitk={rt.splitk if rt else 1} [{flags}]"
             self._note(key, L.check(yr, r, s, y.dtype), what)
             so = kw.get("stats_out")
             if so is not None:

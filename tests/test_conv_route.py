@@ -1,7 +1,7 @@
 """CPU: the dispatcher's route query (dc_conv_route: host code, launches nothing) — its kernel codes match the header, the
 query `ops.rowpanel_takes` that steers the transformer's proj_in agrees with the independent closed form of tests/block_ref.py on
 every shape the models launch, and the split-K the library picks under DC_SPLITK_AUTO is the rule `ops.py` used to state
-(tests/splitk_rule_ref.py), restricted to the splits the route accepts."""
+(tests/splitk_rule_ref.py), restricted to the splits the route accepts; `ops.conv_plan` of a picked split routes as its descriptor."""
 import collections
 import itertools
 import math
@@ -11,6 +11,7 @@ import re
 import pytest
 
 import block_ref
+import edge_cases as E
 import splitk_rule_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -227,3 +228,17 @@ def test_other_values_below_one_still_mean_one(ops, splitk):
 def test_auto_is_the_header_s_constant(ops):
     src = open(os.path.join(ROOT, "include", "diffcodec_hip.h")).read()
     assert int(re.search(r"#define DC_SPLITK_AUTO \((-?\d+)\)", src).group(1)) == ops.DC_SPLITK_AUTO
+
+
+def test_conv_plan_of_a_picked_split_routes_as_its_descriptor(ops):
+    """every edge case again with splitk=None, the library's pick (what ops.conv and ops.linear ask by default): the split in the plan's
+    descriptor is explicit and the one the route of the final descriptor (slabs, finalize-first scratch, GroupNorm partials set)
+    accepts, and the slabs are asked for exactly when it splits"""
+    import dataclasses
+    picked = set()
+    for c in E.CONV_CASES:
+        p = E.case_plan(dataclasses.replace(c, splitk=None))
+        r = ops.conv_route(p.desc)
+        assert p.desc.splitk == r.splitk >= 1 and bool(p.desc.splitk_ws) == (r.splitk > 1) == ("splitk" in dict(p.scratch)), c.label()
+        picked.add(r.splitk)
+    assert len(picked) > 2, picked

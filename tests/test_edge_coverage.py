@@ -2,7 +2,8 @@
 instance it declares, and the checks the GPU edge tests rely on (guarded buffers, the flat and peaked attention input families held
 to oracle/launch_ref.py) reject the faults they are there to catch.  Caller-owned workspaces: E.run_on_fills rejects an overrun, a
 read of an unwritten slot and an unwritten output; every dc_*_ws_bytes of the signature tables has a guarding GPU module
-(WS_QUERY_TESTS) and grows with N no faster than N; ops.conv asks for the scratch the library states."""
+(WS_QUERY_TESTS) and grows with N no faster than N; ops.conv_plan asks for the scratch the library states, and plans every conv case
+as the launch before the planner was recorded to (tests/golden/conv_plans.json)."""
 import functools
 import json
 import math
@@ -59,7 +60,7 @@ def test_every_conv_instance_has_a_case(conv_keys):
 @pytest.mark.parametrize("i", range(len(E.CONV_CASES)), ids=[c.label() for c in E.CONV_CASES])
 def test_conv_case_routes_where_it_declares(lib, i):
     c = E.CONV_CASES[i]
-    got = E.conv_key(E.case_desc(c))
+    got = E.conv_key(E.case_plan(c).desc)
     assert got == c.key, f"{c.label()}: declared {E.key_str(c.key)}, routes to {E.key_str(got)}"
 
 
@@ -805,59 +806,60 @@ def test_run_on_fills_rejects_a_kept_buffer_that_depends_on_the_fill_and_refuses
 
 
 # ------------------------------------------------------------------------------------------ ops.conv's scratch and the library's figure
-def _conv_on_the_host(monkeypatch, c):
-    """ops.conv of a case with host tensors of the right shapes and the launch replaced by a recorder ->
-    (the descriptor it built, [(what, bytes)] it asked ops._scratch for)"""
-    import types
-    from diffcodec_amd import ops
-    asked, descs = [], []
-    monkeypatch.setattr(ops, "_chk", lambda *a: None)
-    monkeypatch.setattr(ops, "_stream", lambda: 0)
+CONV_QUERIES = ("dc_conv_route", "dc_conv_instance", "dc_conv_gn_part_chunks", "dc_conv_igemm_ws_bytes")
 
-    def scratch(shape, device, what):
-        asked.append((what, 4 * math.prod(shape)))
-        return torch.empty(shape, dtype=torch.float32)
 
-    def call(name, d, *rest, meta=None):
-        assert name == "dc_conv_igemm_bf16"
-        descs.append(type(d).from_buffer_copy(d))
+RECORDED_PLANS = json.load(open(os.path.join(ROOT, "tests", "golden", "conv_plans.json")))
 
-    monkeypatch.setattr(ops, "_scratch", scratch)
-    monkeypatch.setattr(ops.lib, "call", call)
-    bf, f32 = torch.bfloat16, torch.float32
-    cin = c.c1 + c.c2
-    pc = types.SimpleNamespace(cout=c.cout, cin=cin, ksize=c.k, geglu=c.geglu, kind="igemm", ln_eps=1e-5 if c.ln is not None else None,
-                               w=torch.empty(c.cout, c.k * c.k, cin, dtype=bf), bias=torch.empty(c.cout), colsum=torch.empty(c.cout))
-    kw = dict(stride=c.stride, pad=c.pad, upsample=c.up, out_scale=c.out_scale, out_f32=c.out_f32, splitk=c.splitk, act=c.act,
-              gn_part=c.gn_part)
-    if c.c2:
-        kw["x2"] = torch.empty(c.n, c.h, c.w, c.c2, dtype=bf)
-    if c.gn:
-        kw.update(gn_ab=torch.empty(c.n, cin, 2), gn_silu=c.gn_silu)
-    if c.row_add:
-        kw["row_add"] = torch.empty(c.n, c.cout)
-    if c.residual:
-        kw["residual"] = torch.empty(c.n, c.ho, c.wo, c.cout, dtype=bf)
-    if c.ln == "pairs":
-        kw["ln_stats"] = torch.empty(c.m, 2)
-    elif c.ln is not None:
-        kw["ln_partials"] = (torch.empty(c.m, c.ln, 2), 1e-5)
-    if c.stats_out:
-        kw["stats_out"] = torch.empty(c.m, ops.row_stats_parts(c.cout), 2)
-    ops.conv(torch.empty(c.n, c.h, c.w, c.c1, dtype=bf), pc, **kw)
+
+def counted_plan(lib, monkeypatch, c, timer):
+    """(E.case_plan(c) with lib.TIMER set or not, the library queries it made by name)"""
+    counts, real = dict.fromkeys(CONV_QUERIES, 0), lib.load()
+
+    class Counting:
+        def __getattr__(self, name):
+            counts[name] = counts.get(name, 0) + 1
+            return getattr(real, name)
+
+    monkeypatch.setattr(lib, "load", Counting)
+    monkeypatch.setattr(lib, "TIMER", object() if timer else None)
+    p = E.case_plan(c)
     monkeypatch.undo()
-    assert len(descs) == 1
-    return descs[0], asked
+    return p, counts
+
+
+@pytest.mark.parametrize("i", range(len(E.CONV_CASES)), ids=[c.label() for c in E.CONV_CASES])
+def test_conv_plan_is_what_the_launch_was_recorded_to_be(lib, monkeypatch, i):
+    """ops.conv_plan against the recording of ops.conv from before the planner (seams patched, host tensors, a stand-in for row_add,
+    the timer set; recorded twice, identical): descriptor fields, which pointers are set, the scratches in order with their bytes,
+    the output and the timer's meta are equal, and the plan, meta included, makes no more library queries than that launch did.
+    Without the timer: no meta, and a route query only where a decision needs one (raw LayerNorm partials; every split is explicit)."""
+    c = E.CONV_CASES[i]
+    rec = RECORDED_PLANS["cases"][f"{i:03d} {c.label()}"]
+    p, counts = counted_plan(lib, monkeypatch, c, timer=True)
+    fields, present = E.desc_fields(p.desc)
+    assert fields == dict(zip(RECORDED_PLANS["fields"], rec["desc"])), c.label()
+    assert present == rec["present"], c.label()
+    assert [[what, 4 * math.prod(shape)] for what, shape in p.scratch] == rec["scratch"], c.label()
+    assert [list(p.out_shape), str(p.out_dtype).replace("torch.", "")] == rec["out"] and p.m == math.prod(p.out_shape[:3])
+    fam, label, flops, nbytes = rec["meta"]
+    assert p.meta == (RECORDED_PLANS["families"][fam], label, flops, nbytes), (c.label(), p.meta)
+    assert all(counts[q] <= n for q, n in zip(CONV_QUERIES, rec["queries"])), (c.label(), counts, rec["queries"])
+    q, untimed = counted_plan(lib, monkeypatch, c, timer=False)
+    assert q.meta is None and E.desc_fields(q.desc) == (fields, present) and q.scratch == p.scratch
+    assert untimed["dc_conv_route"] == (1 if isinstance(c.ln, int) else 0)
+    assert untimed["dc_conv_gn_part_chunks"] == counts["dc_conv_gn_part_chunks"] and untimed["dc_conv_instance"] == 0
 
 
 @pytest.mark.parametrize("i", E.CONV_SCRATCH_CASES, ids=[E.CONV_CASES[i].label() for i in E.CONV_SCRATCH_CASES])
-def test_conv_asks_for_the_scratch_the_library_states(lib, monkeypatch, i):
-    """ops.conv sizes the split-K workspace itself (splitk x M x Cout floats): pinned here to dc_conv_igemm_ws_bytes of the
+def test_conv_asks_for_the_scratch_the_library_states(lib, i):
+    """ops.conv_plan sizes the split-K workspace itself (splitk x M x Cout floats): pinned here to dc_conv_igemm_ws_bytes of the
     descriptor it built, for every case that is handed a scratch; the (mean, rstd) scratch is M pairs and the GroupNorm partials
     dc_conv_gn_part_chunks x N x Cout pairs, asked for exactly when the route finalizes first / the launch emits them"""
     from diffcodec_amd import ops
     c = E.CONV_CASES[i]
-    d, asked = _conv_on_the_host(monkeypatch, c)
+    p = E.case_plan(c)
+    d, asked = p.desc, [(what, 4 * math.prod(shape)) for what, shape in p.scratch]
     assert E.conv_key(d) == c.key
     L_ = lib.load()
     r = ops.conv_route(d)
@@ -875,17 +877,17 @@ def test_conv_asks_for_the_scratch_the_library_states(lib, monkeypatch, i):
     if d.gn_part_out:
         want.append(("gn_part", L_.dc_conv_gn_part_chunks(d) * c.n * c.cout * 2 * 4))
     assert asked == want and want, (c.label(), asked, want)
-    assert [w for w, _ in want] == E.conv_scratch_kinds(c, bool(d.gn_part_out))
 
 
 def test_conv_scratch_cases_are_every_case_that_is_handed_one(lib):
     from diffcodec_amd import ops
+    kinds = set()
     for i, c in enumerate(E.CONV_CASES):
-        d = E.case_desc(c)
-        r = ops.conv_route(d)
-        handed = r.splitk > 1 or r.ln_first or bool(d.gn_part_out)
-        assert handed == (i in E.CONV_SCRATCH_CASES), c.label()
-    kinds = {k for i in E.CONV_SCRATCH_CASES for k in E.conv_scratch_kinds(E.CONV_CASES[i], bool(E.case_desc(E.CONV_CASES[i]).gn_part_out))}
+        p = E.case_plan(c)
+        r = ops.conv_route(p.desc)
+        handed = r.splitk > 1 or r.ln_first or bool(p.desc.gn_part_out)
+        assert handed == bool(p.scratch) == (i in E.CONV_SCRATCH_CASES), c.label()
+        kinds |= {what for what, _ in p.scratch}
     assert kinds == {"splitk", "ln_scratch", "gn_part"}
 
 

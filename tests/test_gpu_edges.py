@@ -68,7 +68,8 @@ def _capture(lib):
 def test_conv_edge(ops, record, i):
     from diffcodec_amd import lib
     c = E.CONV_CASES[i]
-    assert E.conv_key(E.case_desc(c)) == c.key, c.label()
+    plan = E.case_plan(c)
+    assert E.conv_key(plan.desc) == c.key, c.label()
     ho, wo, m = c.ho, c.wo, c.m
     cout_eff = c.cout // 2 if c.geglu else c.cout
     pc, guards, x1, kw = E.conv_operands(ops, c, i, DEV)
@@ -85,6 +86,8 @@ def test_conv_edge(ops, record, i):
         torch.cuda.synchronize()
         outs.append((og, sog, y))
     assert len(seen) == 2 and E.conv_key(seen[0]) == c.key, (c.label(), [E.key_str(E.conv_key(d)) for d in seen])
+    for d in seen:                              # the plan and the launch cannot part: every field, and which pointers are set
+        assert E.desc_fields(d) == E.desc_fields(plan.desc), (c.label(), E.desc_fields(d), E.desc_fields(plan.desc))
     for name, g in guards.items():
         g.assert_intact(f"{c.label()} operand {name}")
     og, sog, y = outs[0]
@@ -118,6 +121,7 @@ def test_conv_scratch_of_any_contents(ops, monkeypatch, i):
     and bit for bit those of the unpatched launch"""
     from diffcodec_amd import lib
     c = E.CONV_CASES[i]
+    plan = E.case_plan(c)
     cout_eff = c.cout // 2 if c.geglu else c.cout
     pc, guards, x1, kw = E.conv_operands(ops, c, i, DEV)
     handed = []
@@ -148,7 +152,7 @@ def test_conv_scratch_of_any_contents(ops, monkeypatch, i):
         assert og.unwritten() == 0 and bool(torch.isfinite(og.view).all()), what
         gp = getattr(y, "gn_part", None)
         if tag != "plain":
-            assert sorted(w for w, _ in handed) == sorted(E.conv_scratch_kinds(c, gp is not None)), (what, [w for w, _ in handed])
+            assert [(w, g.shape) for w, g in handed] == plan.scratch and (gp is not None) == ("gn_part" in dict(plan.scratch)), (what, plan.scratch)
             slabs = sum(g.view.numel() * 4 for w, g in handed if w == "splitk")          # what ops.conv sized, against the library's figure
             assert slabs == lib.load().dc_conv_igemm_ws_bytes(seen[-1]), (what, slabs)
             for w, g in handed:
