@@ -11,12 +11,9 @@
 // The nearest-2x upsample of diffusers' Upsample2D is fused: the halo is taken from the low-resolution input and the
 // fragment positions are halved per tap.
 //
-// The weight tile of each tap goes global -> LDS by `global_load_lds_dwordx4` (LDS-DMA: no VGPR staging, no ds_write)
-// into a ring of NSTB stages; a counted `s_waitcnt vmcnt` + one raw `s_barrier` per K-step keep NSTB-2 stages in
-// flight across the barrier, so the K-loop is MFMA/LDS-paced instead of load-latency-paced.
-//
-// LDS images are row-major 128-B rows with the 16-B chunk index XORed by (row & 7): ds_write_b128 of a row piece and
-// the v_mfma_f32_16x16x32_bf16 fragment ds_read_b128 are both bank-conflict-free, and rows stay whole 128-B lines.
+// The weight tile of each tap goes global -> LDS by LDS-DMA (stage layout: dc_kstage.h; the halo image of the unpipelined
+// path uses the same 128-byte rows and XOR) into a ring of NSTB stages; a counted `s_waitcnt vmcnt` + one raw `s_barrier` per
+// K-step keep NSTB-2 stages in flight across the barrier, so the K-loop is MFMA/LDS-paced instead of load-latency-paced.
 #include "dc_epilogue.h"
 #include <cstdlib>
 #include <utility>
@@ -31,9 +28,6 @@
 #endif
 
 namespace {
-
-typedef const void __attribute__((address_space(1))) * gptr_t;
-typedef void __attribute__((address_space(3))) * lptr_t;
 
 template <int... I, class F>
 __device__ __forceinline__ void dc_static_for(std::integer_sequence<int, I...>, F&& f)
@@ -145,7 +139,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_tile_kernel(const dc_conv_desc
         h_pix[i] = pix;
         h_lds[i] = FAST ? hp * HP + (q << 4) : hp * 128 + ((q ^ (hp & 7)) << 4);
     }
-    // weight-tile DMA: piece g (8 rows) of a stage; lane -> row 8g + (lane>>3), LDS slot lane&7 = source chunk ^ (row&7)
+    // weight-tile DMA: piece g = wave + 4 i of a stage (dc_kstage.h)
     const char* b_src[NB];
 #pragma unroll
     for (int i = 0; i < NB; ++i) {
@@ -212,7 +206,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_tile_kernel(const dc_conv_desc
         char* base = sB0 + slot * B_BYTES;
 #pragma unroll
         for (int i = 0; i < NB; ++i)
-            __builtin_amdgcn_global_load_lds((gptr_t)(b_src[i] + off), (lptr_t)(base + (wave + 4 * i) * 1024), 16, 0, 0);
+            dc_dma16(b_src[i] + off, base + (wave + 4 * i) * DC_KPIECE);
     };
 
     auto issue_b_at = [&](int cc, int tap, int slot) {   // the same with (slice, tap) known: no division in the unrolled K loop
@@ -223,7 +217,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_tile_kernel(const dc_conv_desc
         char* base = sB0 + slot * B_BYTES;
 #pragma unroll
         for (int i = 0; i < NB; ++i)
-            __builtin_amdgcn_global_load_lds((gptr_t)(b_src[i] + off), (lptr_t)(base + (wave + 4 * i) * 1024), 16, 0, 0);
+            dc_dma16(b_src[i] + off, base + (wave + 4 * i) * DC_KPIECE);
     };
 
     // FAST specialised epilogues: the bias (+ the sample's time-embedding row) is the accumulators' initial value — fetched in
@@ -246,7 +240,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_tile_kernel(const dc_conv_desc
     }
 
     // One K-step (tap): all 2 x (TN + TM) fragment reads first (two register sets), then the step's LDS-DMA pieces, which
-    // the schedule spreads between the MFMAs — same reasoning as gemm_dma.hip's K-step.
+    // the schedule spreads between the MFMAs (dc_sched_reads_mfma_dma in dc_kstage.h).
     bf16x8 wf[2][TN], xf[2][TM];
     auto load_frags = [&](int tap, int buf) {
         const char* sB = sB0 + buf * B_BYTES;
@@ -262,7 +256,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_tile_kernel(const dc_conv_desc
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             const int qq = 4 * s + fq;
-            const int bsw = (qq ^ (fr & 7)) << 4;       // weight rows: (row & 7) == (fr & 7)
+            const int bsw = (qq ^ (fr & 7)) << 4;       // = dc_kstage_frag_off(s, fq, fr), sharing qq with the halo read below
 #pragma unroll
             for (int tm = 0; tm < TM; ++tm)
                 xf[s][tm] = *(const bf16x8*)(sH + prow[tm] * 128 + ((qq ^ (prow[tm] & 7)) << 4));
@@ -272,22 +266,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_tile_kernel(const dc_conv_desc
         }
     };
     auto mfma_frags = [&]() {
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-                for (int tm = 0; tm < TM; ++tm)
-                    acc[tn][tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[s][tn], xf[s][tm], acc[tn][tm], 0, 0, 0);
-        constexpr int NMF = 2 * TN * TM;
-        constexpr int PER = NMF / (NB + 1) > 0 ? NMF / (NB + 1) : 1;
-        __builtin_amdgcn_sched_group_barrier(0x100, 2 * (TN + TM), 0);              // every fragment read first
-#pragma unroll
-        for (int i = 0; i < NB; ++i) {
-            __builtin_amdgcn_sched_group_barrier(0x008, PER, 0);                    // a few MFMAs ...
-            __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);                      // ... then one LDS-DMA piece
-        }
-        __builtin_amdgcn_sched_group_barrier(0x008, NMF - NB * PER, 0);
+        dc_mfma_kstep(acc, wf, xf);
+        dc_sched_reads_mfma_dma<2 * TN * TM, 2 * (TN + TM), NB>();
     };
 
     unsigned long long ts0 = 0, ts1 = 0, ts2 = 0, ts3 = 0, ta = 0, tb = 0, tc = 0, s_sync = 0, s_work = 0, s_halo = 0;
@@ -308,7 +288,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_tile_kernel(const dc_conv_desc
         }
         int b_lane[2];
 #pragma unroll
-        for (int s = 0; s < 2; ++s) b_lane[s] = H_BYTES + ((wn * TN) * 16 + fr) * 128 + (((4 * s + fq) ^ (fr & 7)) << 4);
+        for (int s = 0; s < 2; ++s) b_lane[s] = H_BYTES + ((wn * TN) * 16 + fr) * 128 + dc_kstage_frag_off(s, fq, fr);
         bf16x8 xa[2][TM], wb[2][TN];
         auto rd_half = [&](int tap, int s, int slot_off) {
             const int ky = tap / 3, kx = tap - 3 * ky;
@@ -323,20 +303,13 @@ __global__ __launch_bounds__(256, 2) void conv3x3_tile_kernel(const dc_conv_desc
             for (int tn = 0; tn < TN; ++tn) wb[s][tn] = *(const bf16x8*)(bp + tn * 2048);
         };
         auto mfma_half = [&](int s) {
-#pragma unroll
-            for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-                for (int tm = 0; tm < TM; ++tm)
-                    acc[tn][tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wb[s][tn], xa[s][tm], acc[tn][tm], 0, 0, 0);
+            dc_mfma_khalf(acc, wb[s], xa[s]);
         };
         constexpr int NMF = TN * TM, NRD = TN + TM;
         issue_halo(c_begin);
         issue_b(0, 0);
         store_halo(c_begin);
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        dc_ring_sync<0>();
         rd_half(0, 0, 0);
 #pragma unroll
         for (int st = 1; st < NSTB; ++st) issue_b(st, st);
@@ -368,8 +341,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_tile_kernel(const dc_conv_desc
                 constexpr int VMN = NB * (NSTB - 2) + ((tap >= 1 && tap <= NSTB - 1) ? NHU : 0);
                 static_assert(VMN < 64, "vmcnt field");
                 __builtin_amdgcn_s_waitcnt(0x0070 | (VMN & 15) | ((VMN >> 4) << 14));
-                __builtin_amdgcn_s_barrier();
-                asm volatile("" ::: "memory");
+                dc_wg_barrier();
                 DC_NOW(tc);
 #ifdef DC_STAMP
                 s_work += tb - ta;
@@ -408,10 +380,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_tile_kernel(const dc_conv_desc
                 // every wave passed the mid-step barrier of tap 8 with its halo reads returned: the image is free
                 DC_NOW(ta);
                 store_halo(cc + 1);
-                __builtin_amdgcn_sched_barrier(0);
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-                asm volatile("" ::: "memory");
+                dc_wait_lgkm();
+                dc_wg_barrier();
                 rd_half(0, 0, (step & (NSTB - 1)) * B_BYTES);
 #ifdef DC_STAMP
                 DC_NOW(tb);
@@ -449,10 +419,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_tile_kernel(const dc_conv_desc
         }
         if (more_c) {
             DC_NOW(ta);
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's reads of the halo image have returned
-            __builtin_amdgcn_s_barrier();                        // every wave is past its last read of the halo image
-            asm volatile("" ::: "memory");
+            dc_wait_lgkm();                                      // this wave's reads of the halo image have returned
+            dc_wg_barrier();                                     // every wave is past its last read of the halo image
             store_halo(cc + 1);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // visible after the next K-step's barrier
 #ifdef DC_STAMP
@@ -503,10 +471,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_tile_kernel(const dc_conv_desc
     constexpr bool stg = FAST && !GENERIC && !SH;                     // (the generic epilogue keeps its direct stores; the launcher
                                                                  //  sends Cout % 8 != 0 to the other kernel)
     if constexpr (stg) {
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // every wave is past its last fragment read: LDS is free
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        dc_wait_lgkm();                                          // every wave is past its last fragment read: LDS is free
+        dc_wg_barrier();
     }
 #ifdef DC_STAMP
     unsigned long long te1 = 0, te2 = 0, te3 = 0;

@@ -158,6 +158,11 @@ __device__ __forceinline__ float dc_wave_max(float v)
     return v;
 }
 
+template <int N>
+__device__ __forceinline__ void wait_vmcnt()
+{
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
 // One K-step hand-over of an LDS ring filled by LDS-DMA: wait until all but the N youngest vector-memory operations of
 // this wave have landed AND until every LDS read this wave has issued has returned, then the workgroup barrier.
 // The lgkmcnt(0) is what makes the ring safe to refill: hipcc software-pipelines the last fragment reads of a K-step past
@@ -166,18 +171,28 @@ __device__ __forceinline__ float dc_wave_max(float v)
 // tiles that differ from run to run (found with tools/find_nondeterminism.py on the unrolled TM=2 tile conv).  The
 // sched_barrier keeps the step's MFMAs in front of the wait (so the wait is normally already satisfied), the compiler
 // barrier after s_barrier keeps the next step's LDS reads behind it.
+// (The three pieces serve the kernels whose wait and barrier are apart — ping-pong phases — or whose wait counts LDS operations only.)
 template <int N>
-__device__ __forceinline__ void wait_vmcnt()
+__device__ __forceinline__ void dc_wait_vm_lgkm()
 {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
+}
+__device__ __forceinline__ void dc_wait_lgkm()
+{
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
+__device__ __forceinline__ void dc_wg_barrier()
+{
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
 }
 template <int N>
 __device__ __forceinline__ void dc_ring_sync()
 {
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    dc_wait_vm_lgkm<N>();
+    dc_wg_barrier();
 }
 
 // GroupNorm statistics from a conv / GEMM epilogue: `s` / `q` = this lane's (sum, sum of squares) over its pixel rows for the 4

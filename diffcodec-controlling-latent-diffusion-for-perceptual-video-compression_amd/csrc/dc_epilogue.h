@@ -12,6 +12,7 @@
 // forms are pinned per instance by tests/test_gpu_conv_bits.py.
 #pragma once
 #include "dc_conv_route.h"
+#include "dc_kstage.h"                       // the other half of each kernel: the K loop's operand stage
 
 // which steps of the chain run: compile-time constants in the specialised epilogues (the call folds to straight-line code), run-time
 // values in the generic ones

@@ -3,10 +3,7 @@
 // ControlNet zero-convs: call sites flownet.py:87-124, pipeline.py:358-367) whenever no transform is needed on load.
 //
 // Per workgroup: 256 threads = 4 waves as 2(m) x 2(n), tile BM x BN, BK = 64 (one 128-byte line per row per K-step).
-// Both operand tiles go global -> LDS with `global_load_lds_dwordx4` (no VGPR staging, no ds_write): one wave
-// instruction lands 8 rows x 128 B; the LDS image is lane-linear as the DMA requires, and the bank swizzle
-// (16-byte chunk index XOR (row & 7)) is applied on the per-lane SOURCE address and again on the fragment read, so
-// the v_mfma_f32_16x16x32_bf16 fragment ds_read_b128 stay conflict-free.  NST LDS stages form a ring: the DMA of
+// Both operand tiles go global -> LDS by LDS-DMA in the swizzled stage layout of dc_kstage.h.  NST LDS stages form a ring: the DMA of
 // K-step k+NST-1 is issued right after the barrier that opens step k, and a counted `s_waitcnt vmcnt(N)` (never 0 in
 // the loop) leaves NST-2 stages in flight across every raw `s_barrier` — one barrier per K-step.
 #include "dc_epilogue.h"
@@ -29,9 +26,6 @@
 #endif
 
 namespace {
-
-typedef const void __attribute__((address_space(1))) * gptr_t;
-typedef void __attribute__((address_space(3))) * lptr_t;
 
 // EPI: epilogue specialisation chosen by the launcher from the descriptor.  With every fusion a run-time flag, the unrolled
 // (tm, tn) epilogue was 6,300 instructions in 336 basic blocks — a branch (and often a wait) per flag per 4 outputs — and took
@@ -86,8 +80,7 @@ __global__ __launch_bounds__(256, 2) void gemm_dma_kernel(const dc_conv_desc d)
     }
     const int nk = kt_end - kt_begin;
 
-    // ---- per-lane DMA sources.  Piece g (8 rows) of a stage: rows [8g, 8g+8); lane s -> row 8g + (s>>3), LDS slot s&7,
-    //      which must hold source chunk (s&7) ^ (row&7).
+    // ---- per-lane DMA sources: piece g = wave + 4 i of the stage (dc_kstage.h)
     const char* src1[NGW];                            // row base in x1 (or W) incl. the swizzled chunk offset
     const char* src2[NGW];                            // row base in x2 (second K range) — A rows only
     int ldsoff[NGW];
@@ -96,8 +89,8 @@ __global__ __launch_bounds__(256, 2) void gemm_dma_kernel(const dc_conv_desc d)
     for (int i = 0; i < NGW; ++i) {
         const int g = wave + 4 * i;
         const int row = g * 8 + (lane >> 3);
-        const int chunk = (lane & 7) ^ (row & 7);
-        ldsoff[i] = g * 1024;
+        const int chunk = dc_kstage_src_chunk(lane, row);
+        ldsoff[i] = g * DC_KPIECE;
         if (g * 8 < BM) {
             int m = m0 + row;
             m = m < M ? m : M - 1;                    // clamp: rows past M are computed and discarded
@@ -114,16 +107,17 @@ __global__ __launch_bounds__(256, 2) void gemm_dma_kernel(const dc_conv_desc d)
         kt = kt < kt_end ? kt : kt_end - 1;           // past-the-end stages re-read the last one (keeps vmcnt counts constant)
         char* base = smem + slot * STAGE;
         if (kt < c1_steps) {                          // first K range (the only one without a channel concat): no per-piece select
+            // (the builtin, not dc_dma16: see dc_kstage.h)
 #pragma unroll
             for (int i = 0; i < NGW; ++i)
-                __builtin_amdgcn_global_load_lds((gptr_t)(src1[i] + (long long)kt * 128), (lptr_t)(base + ldsoff[i]), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds((dc_gptr_t)(src1[i] + (long long)kt * 128), (dc_lptr_t)(base + ldsoff[i]), 16, 0, 0);
             return;
         }
 #pragma unroll
         for (int i = 0; i < NGW; ++i) {
             const bool is_a = (wave + 4 * i) * 8 < BM;                    // wave-uniform
             const char* p = is_a ? src2[i] + (long long)(kt - c1_steps) * 128 : src1[i] + (long long)kt * 128;
-            __builtin_amdgcn_global_load_lds((gptr_t)p, (lptr_t)(base + ldsoff[i]), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((dc_gptr_t)p, (dc_lptr_t)(base + ldsoff[i]), 16, 0, 0);
         }
     };
 
@@ -133,20 +127,15 @@ __global__ __launch_bounds__(256, 2) void gemm_dma_kernel(const dc_conv_desc d)
 #pragma unroll
         for (int j = 0; j < TM; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    // One K-step.  All 2 x (TN + TM) fragment reads of the step are issued up front (both 32-wide k halves, two register
-    // sets), so the reads of the second half land while the MFMAs of the first run; left to itself hipcc keeps one weight
-    // fragment live at a time and waits lgkmcnt(0) in front of every group of TM MFMAs — the full LDS latency once per 4
-    // MFMAs.  The next stage's LDS-DMA pieces are issued AFTER the reads in program order (a DMA is an LDS store to the
-    // compiler: it may not sink below reads that precede it, but it may be scheduled among the MFMAs that follow it) and
-    // are spread between the MFMAs, one per few MFMAs: an LDS-DMA wave-instruction holds the wave's issue for 60-100 cycles,
-    // which a leading block of NGW of them would add to every K-step in front of the first MFMA.
+    // One K-step: all 2 x (TN + TM) fragment reads up front, the next stage's NGW LDS-DMA pieces issued AFTER them in program order and
+    // spread between the MFMAs (dc_sched_reads_mfma_dma in dc_kstage.h says why).
     bf16x8 wf[2][TN], xf[2][TM];
     auto load_frags = [&](int slot) {
         const char* sA = smem + slot * STAGE;
         const char* sB = sA + BM * 128;
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            const int swz = ((4 * s + fq) ^ (fr & 7)) << 4;
+            const int swz = dc_kstage_frag_off(s, fq, fr);
 #pragma unroll
             for (int tm = 0; tm < TM; ++tm) xf[s][tm] = *(const bf16x8*)(sA + ((wm * TM + tm) * 16 + fr) * 128 + swz);
 #pragma unroll
@@ -154,22 +143,8 @@ __global__ __launch_bounds__(256, 2) void gemm_dma_kernel(const dc_conv_desc d)
         }
     };
     auto mfma_frags = [&]() {
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-                for (int tm = 0; tm < TM; ++tm)
-                    acc[tn][tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[s][tn], xf[s][tm], acc[tn][tm], 0, 0, 0);
-        constexpr int NMF = 2 * TN * TM;
-        constexpr int PER = NMF / (NGW + 1) > 0 ? NMF / (NGW + 1) : 1;
-        __builtin_amdgcn_sched_group_barrier(0x100, 2 * (TN + TM), 0);              // every fragment read first
-#pragma unroll
-        for (int i = 0; i < NGW; ++i) {
-            __builtin_amdgcn_sched_group_barrier(0x008, PER, 0);                    // a few MFMAs ...
-            __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);                      // ... then one LDS-DMA piece
-        }
-        __builtin_amdgcn_sched_group_barrier(0x008, NMF - NGW * PER, 0);
+        dc_mfma_kstep(acc, wf, xf);
+        dc_sched_reads_mfma_dma<2 * TN * TM, 2 * (TN + TM), NGW>();
     };
 
     // bias for this lane's output channels: fetched now so its latency hides under the K loop

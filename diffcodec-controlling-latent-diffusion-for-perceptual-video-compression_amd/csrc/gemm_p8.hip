@@ -31,9 +31,6 @@
 
 namespace {
 
-typedef const void __attribute__((address_space(1))) * gptr_t;
-typedef void __attribute__((address_space(3))) * lptr_t;
-
 constexpr int P8_HALF = 128 * 128;                  // bytes of a half tile
 constexpr int P8_BUF = 4 * P8_HALF;                 // one K tile
 constexpr int P8_RING = 2 * P8_BUF;                 // 128 KB
@@ -43,23 +40,6 @@ constexpr int P8_PAR_CS = P8_PAR_BIAS + 1024;
 constexpr int P8_PAR_LN = P8_PAR_CS + 1024;
 constexpr int P8_LDS = P8_PAR_LN + 2048;
 constexpr int P8_GM = 8;                            // row tiles per group of the tile order (see gemm_p8_kernel)
-
-__device__ __forceinline__ void p8_barrier()
-{
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-template <int N>
-__device__ __forceinline__ void p8_wait_vm_lgkm()
-{
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void p8_wait_lgkm()
-{
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-}
 
 // EPI: 1 bias, 3 folded LayerNorm + bias, 4 GEGLU, 5 folded LayerNorm + GEGLU (the numbering of gemm_dma.hip)
 template <int EPI>
@@ -91,15 +71,14 @@ __global__ __launch_bounds__(512, 2) void gemm_p8_kernel(const dc_conv_desc d)
     const int tile_n = in_group / rows;
     const int m0 = tile_m << 8, n0 = tile_n << 8;
 
-    // ---- DMA sources.  Piece j of a half tile = its rows [8j, 8j+8); this wave issues pieces `wave` and `wave + 8`; lane s ->
-    //      row 8j + (s >> 3), LDS slot s & 7, which holds source chunk (s & 7) ^ (row & 7).
+    // ---- DMA sources.  This wave issues pieces `wave` and `wave + 8` of a half tile (piece layout: dc_kstage.h).
     //      Sources are a workgroup-uniform base (SGPRs: tile origin + K offset of the half tile) plus a 32-bit per-lane offset, so a
     //      piece costs no vector address arithmetic.
     uint32_t offx[2], offw[2];                       // H0 / H1 (H3 = + 64 rows, H2 = + 32 rows: in the uniform base)
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int row = (wave + 8 * i) * 8 + (lane >> 3);
-        const int chunk = (lane & 7) ^ (row & 7);
+        const int chunk = dc_kstage_src_chunk(lane, row);
         offx[i] = (uint32_t)(((row >> 6) * 128 + (row & 63)) * K + chunk * 8) * 2u;
         int wn = n0 + (row >> 5) * 64 + (row & 31);
         // columns past Cout (whole 64-column wave slices of a half-full last tile) are computed on valid rows and never stored: row
@@ -118,14 +97,14 @@ __global__ __launch_bounds__(512, 2) void gemm_p8_kernel(const dc_conv_desc d)
         const uint32_t ko = (uint32_t)kt * 128u;     // the K offset rides in the 32-bit lane offset (one v_add_u32 per piece), the rest in SGPRs
 #pragma unroll
         for (int i = 0; i < 2; ++i)
-            __builtin_amdgcn_global_load_lds((gptr_t)(sb + (size_t)(uint32_t)((is_x ? offx[i] : offw[i]) + ko)), (lptr_t)(base + i * 8192), 16, 0, 0);
+            dc_dma16(sb + (size_t)(uint32_t)((is_x ? offx[i] : offw[i]) + ko), base + i * 8192);
     };
 
     // ---- fragment read bases (byte offsets into a K tile's buffer; + 2048 per 16-row block, + half-tile offset)
     int xa_off[2], wb_off[2];
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-        const int swz = ((4 * s + fq) ^ (fr & 7)) << 4;
+        const int swz = dc_kstage_frag_off(s, fq, fr);
         xa_off[s] = (grp * 64 + fr) * 128 + swz;
         wb_off[s] = (wc * 32 + fr) * 128 + swz;
     }
@@ -161,10 +140,10 @@ __global__ __launch_bounds__(512, 2) void gemm_p8_kernel(const dc_conv_desc d)
     *(float*)(smem + P8_PAR_BIAS + pt * 4) = par_b;
     *(float*)(smem + P8_PAR_CS + pt * 4) = par_c;
     *(f32x2*)(smem + P8_PAR_LN + pt * 8) = par_mr;
-    if (nk > 1) p8_wait_vm_lgkm<6>();
-    else p8_wait_vm_lgkm<0>();
-    p8_barrier();                                    // tile 0 visible to every wave
-    if (grp == 1) p8_barrier();                      // group 1 runs one barrier behind
+    if (nk > 1) dc_wait_vm_lgkm<6>();
+    else dc_wait_vm_lgkm<0>();
+    dc_wg_barrier();                                    // tile 0 visible to every wave
+    if (grp == 1) dc_wg_barrier();                      // group 1 runs one barrier behind
 
     auto read_x = [&](const char* buf, int half_off) {
 #pragma unroll
@@ -181,14 +160,7 @@ __global__ __launch_bounds__(512, 2) void gemm_p8_kernel(const dc_conv_desc d)
     auto quadrant = [&](auto nh_c, auto mh_c, const bf16x8 (&wb)[2][2]) {
         constexpr int nh = decltype(nh_c)::value, mh = decltype(mh_c)::value;
         __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-                for (int tm = 0; tm < 4; ++tm)
-                    acc[nh * 2 + tn][mh * 4 + tm] =
-                        __builtin_amdgcn_mfma_f32_16x16x32_bf16(wb[s][tn], xa[s][tm], acc[nh * 2 + tn][mh * 4 + tm], 0, 0, 0);
+        dc_mfma_kstep<2, 4, nh * 2, mh * 4>(acc, wb, xa);
         __builtin_amdgcn_s_setprio(0);
     };
     using I0 = std::integral_constant<int, 0>;
@@ -205,31 +177,31 @@ __global__ __launch_bounds__(512, 2) void gemm_p8_kernel(const dc_conv_desc d)
         __builtin_amdgcn_sched_barrier(0);
         read_x(buf, 0);
         if (n1) issue_half(3, t + 1, P ^ 1);
-        p8_wait_lgkm();
-        p8_barrier();
+        dc_wait_lgkm();
+        dc_wg_barrier();
         quadrant(I0{}, I0{}, wb0);
-        p8_barrier();
+        dc_wg_barrier();
         // phase 2: W cols 32-63
         read_w(wb1, buf, 2 * P8_HALF);
         if (n2) issue_half(0, t + 2, P);
-        p8_wait_lgkm();
-        p8_barrier();
+        dc_wait_lgkm();
+        dc_wg_barrier();
         quadrant(I1{}, I0{}, wb1);
-        p8_barrier();
+        dc_wg_barrier();
         // phase 3: X rows 64-127
         read_x(buf, 3 * P8_HALF);
         if (n2) issue_half(1, t + 2, P);
-        p8_wait_lgkm();
-        p8_barrier();
+        dc_wait_lgkm();
+        dc_wg_barrier();
         quadrant(I1{}, I1{}, wb1);
-        p8_barrier();
+        dc_wg_barrier();
         // phase 4: no reads (W cols 0-31 are still in registers); all of tile t+1 must have landed before the next phase reads it
         if (n2) issue_half(2, t + 2, P);
-        if (n2) p8_wait_vm_lgkm<6>();
-        else p8_wait_vm_lgkm<0>();
-        p8_barrier();
+        if (n2) dc_wait_vm_lgkm<6>();
+        else dc_wait_vm_lgkm<0>();
+        dc_wg_barrier();
         quadrant(I0{}, I1{}, wb0);
-        p8_barrier();
+        dc_wg_barrier();
     };
     using BT = std::integral_constant<bool, true>;
     using BF = std::integral_constant<bool, false>;
@@ -243,7 +215,7 @@ __global__ __launch_bounds__(512, 2) void gemm_p8_kernel(const dc_conv_desc d)
         k_tile(I1{}, BF{}, t + 1);
     }
     if (t < nk) k_tile(I0{}, BF{}, t);
-    if (grp == 0) p8_barrier();                      // pairs with group 1's last barrier: no LDS read or DMA is pending past it
+    if (grp == 0) dc_wg_barrier();                      // pairs with group 1's last barrier: no LDS read or DMA is pending past it
 
     // ---- epilogue: rows staged through LDS, written as whole 16-byte pieces of contiguous output rows
     constexpr int OC = e_geglu ? 128 : 256;

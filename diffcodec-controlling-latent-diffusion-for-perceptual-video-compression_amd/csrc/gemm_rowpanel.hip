@@ -49,9 +49,6 @@
 
 namespace {
 
-typedef const void __attribute__((address_space(1))) * gptr_t;
-typedef void __attribute__((address_space(3))) * lptr_t;
-
 constexpr int RP_K = 320;                          // the only K this kernel is built for
 constexpr int RP_KS = RP_K / 32;                   // 32-wide MFMA k-steps
 constexpr int RP_SC = 64;                          // output columns per stage
@@ -131,33 +128,32 @@ __global__ __launch_bounds__(512, 2) void gemm_rowpanel_kernel(const dc_conv_des
         }
     }
 
-    // ---- W stage image in LDS: row n (64) x 640 B, 16-byte chunk c of row n stored at chunk position c ^ (n & 7) (the XOR
-    //      stays inside an aligned group of 8 chunks).  Piece g = 5 wave + i covers LDS bytes [1024 g, 1024 g + 1024): lane s
-    //      lands at flat chunk 64 g + s = (row n, position q) and must fetch source chunk q ^ (n & 7) of that row.
+    // ---- W stage image in LDS: 64 rows x 640 B, the row-panel layout of dc_kstage.h.  Piece g = 5 wave + i covers LDS bytes
+    //      [1024 g, 1024 g + 1024): lane s lands at flat chunk 64 g + s = (row n, position q).
     int woff[RP_P];
 #pragma unroll
     for (int i = 0; i < RP_P; ++i) {
         const int flat = (wave * RP_P + i) * 64 + lane;
         const int n = flat / 40, q = flat - n * 40;
-        woff[i] = n * 640 + ((q ^ (n & 7)) << 4);
+        woff[i] = n * DC_RP_KROW + (dc_kstage_rp_src_chunk(q, n) << 4);
     }
     auto issue_w = [&](int s, int slot) {
         s = s < S ? s : S - 1;                                      // past-the-end stages re-read the last one into a dead slot
         const char* src = (const char*)d.w + (long long)s * RP_WBYTES;
         char* base = smem + slot * RP_STAGE;
 #pragma unroll
-        for (int i = 0; i < RP_P; ++i)
-            __builtin_amdgcn_global_load_lds((gptr_t)(src + woff[i]), (lptr_t)(base + (wave * RP_P + i) * 1024), 16, 0, 0);
+        for (int i = 0; i < RP_P; ++i)              // (the builtin, not dc_dma16 / dc_dma4: see dc_kstage.h)
+            __builtin_amdgcn_global_load_lds((dc_gptr_t)(src + woff[i]), (dc_lptr_t)(base + (wave * RP_P + i) * DC_KPIECE), 16, 0, 0);
         if (extra) {
             const float* v = (wave == 0 ? d.bias : d.ln_colsum) + s * RP_SC + lane;
-            __builtin_amdgcn_global_load_lds((gptr_t)v, (lptr_t)(base + RP_WBYTES + wave * 256), 4, 0, 0);
+            __builtin_amdgcn_global_load_lds((dc_gptr_t)v, (dc_lptr_t)(base + RP_WBYTES + wave * 256), 4, 0, 0);
         }
     };
 
-    // fragment read addresses: W row 16 tn + fr, chunk 4 k + fq -> position ((k >> 1) << 3) | (((4 (k & 1) + fq)) ^ (fr & 7))
+    // fragment read addresses: W row 16 tn + fr, k-step k (dc_kstage_rp_frag_off: + (k >> 1) * 128 from the even / odd base)
     const int x7 = fr & 7;
-    const int rd_even = fr * 640 + ((fq ^ x7) << 4);
-    const int rd_odd = fr * 640 + (((4 + fq) ^ x7) << 4);
+    const int rd_even = fr * DC_RP_KROW + dc_kstage_rp_frag_off(0, fq, fr);
+    const int rd_odd = fr * DC_RP_KROW + dc_kstage_rp_frag_off(1, fq, fr);
 
     // wave-private staging (non-GEGLU: 32 rows x 128 B; GEGLU: 32 rows x 64 B), bank-conflict-free for the 8-byte MFMA-layout
     // writes and the 16-byte row reads: chunk XOR row bits, 8-byte halves swapped on alternate 8-row groups (dc_stage_swz)
@@ -182,29 +178,23 @@ __global__ __launch_bounds__(512, 2) void gemm_rowpanel_kernel(const dc_conv_des
     RP_STAMP_AT(0);
     issue_w(0, 0);
     issue_w(1, 1);
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    dc_ring_sync<0>();
     RP_STAMP_AT(1);
     for (int s = 0; s < S; ++s) {
         if (s > 0) {
             __builtin_amdgcn_sched_barrier(0);
             if (extra) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(RP_P + 1 + T + R + 2 * (F + G)) : "memory");
             else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(RP_P + T + R + 2 * (F + G)) : "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
+            dc_wg_barrier();
         }
         RP_STAMP_AT(2 + 3 * s);
         // ---- top of the stage: touch (s+2), residual (s), W (s+2)
         if (e_res) {
             const int s2 = s + 2 < S ? s + 2 : S - 1;
-            __builtin_amdgcn_global_load_lds((gptr_t)(touch_lane + s2 * (RP_SC * 2)),
-                                             (lptr_t)(smem + RP_NST * RP_STAGE + 8 * RP_STG + wave * RP_TOUCH), 4, 0, 0);
+            dc_dma4(touch_lane + s2 * (RP_SC * 2), smem + RP_NST * RP_STAGE + 8 * RP_STG + wave * RP_TOUCH);
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-                __builtin_amdgcn_global_load_lds((gptr_t)(res_lane + (long long)i * 8 * d.Cout * 2 + s * (RP_SC * 2)),
-                                                 (lptr_t)(stg + i * 1024), 16, 0, 0);
+                dc_dma16(res_lane + (long long)i * 8 * d.Cout * 2 + s * (RP_SC * 2), stg + i * 1024);
         }
         issue_w(s + 2, (s + 2) % RP_NST);
 

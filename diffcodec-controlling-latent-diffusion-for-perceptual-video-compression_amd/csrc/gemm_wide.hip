@@ -23,21 +23,6 @@
 
 namespace {
 
-typedef const void __attribute__((address_space(1))) * gptr_t;
-typedef void __attribute__((address_space(3))) * lptr_t;
-
-template <int N>
-__device__ __forceinline__ void wait_vm_lgkm()
-{
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void wg_barrier()
-{
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-
 // EPI as in gemm_dma.hip: 1 bias, 2 bias + scale + residual, 3 folded LayerNorm + bias, 4 GEGLU, 5 folded LayerNorm + GEGLU.
 // ST (EPI 1 / 2): bit 0 = LayerNorm row statistics of the output requested (`stats_out`), bit 1 = GroupNorm partials (`gn_part_out`).
 // A compile-time choice: the sums cost 24 vector operations per 16 x 16 block (480 per wave and tile), most launches of this kernel
@@ -77,8 +62,7 @@ __global__ __launch_bounds__(512, 2) void gemm_wide_kernel(const dc_conv_desc d)
     const int tile_n = bid % n_tiles, tile_m = bid / n_tiles;
     const int m0 = tile_m * BM, n0 = tile_n * BN;
 
-    // ---- per-lane DMA sources: piece g = wave + 8 i covers stage rows [8g, 8g+8); lane s -> row 8g + (s>>3), LDS slot s&7,
-    //      which must hold source chunk (s&7) ^ (row&7)
+    // ---- per-lane DMA sources: piece g = wave + 8 i of the stage (dc_kstage.h)
     //      Addresses are a workgroup-uniform base (SGPRs: tile origin of the operand) + a 32-bit per-lane offset that also carries the K
     //      offset of the stage (one v_add_u32 per piece; a 64-bit per-lane pointer costs two registers and a 64-bit vector add per piece,
     //      issued while the partner group's MFMAs hold the vector port — gemm_p8.hip measured 2-3 % for the same change).
@@ -93,7 +77,7 @@ __global__ __launch_bounds__(512, 2) void gemm_wide_kernel(const dc_conv_desc d)
         int g = wave + 8 * i;
         g = g < NP ? g : NP - 1;
         const int row = g * 8 + (lane >> 3);
-        const int chunk = (lane & 7) ^ (row & 7);
+        const int chunk = dc_kstage_src_chunk(lane, row);
         if (row < BM) {
             int m = m0 + row;
             m = m < M ? m : M - 1;                    // clamp: rows past M are computed and discarded
@@ -117,7 +101,7 @@ __global__ __launch_bounds__(512, 2) void gemm_wide_kernel(const dc_conv_desc d)
             const bool is_a = g * 8 < BM;                                        // wave-uniform
             const char* p = is_a ? ((second ? bx2 : bx1) + (size_t)(uint32_t)((second ? off2[i] : off1[i]) + (second ? ko2 : ko1)))
                                  : (bw + (size_t)(uint32_t)(off1[i] + ko1));
-            __builtin_amdgcn_global_load_lds((gptr_t)p, (lptr_t)(base + g * 1024), 16, 0, 0);
+            dc_dma16(p, base + g * DC_KPIECE);
         }
     };
 
@@ -133,7 +117,7 @@ __global__ __launch_bounds__(512, 2) void gemm_wide_kernel(const dc_conv_desc d)
         const char* sB = sA + BM * 128;
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            const int swz = ((4 * s + fq) ^ (fr & 7)) << 4;
+            const int swz = dc_kstage_frag_off(s, fq, fr);
 #pragma unroll
             for (int tm = 0; tm < TM; ++tm) xf[s][tm] = *(const bf16x8*)(sA + (wrow + tm * 16 + fr) * 128 + swz);
 #pragma unroll
@@ -142,13 +126,7 @@ __global__ __launch_bounds__(512, 2) void gemm_wide_kernel(const dc_conv_desc d)
     };
     auto mfma_frags = [&]() {
         __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-                for (int tm = 0; tm < TM; ++tm)
-                    acc[tn][tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[s][tn], xf[s][tm], acc[tn][tm], 0, 0, 0);
+        dc_mfma_kstep(acc, wf, xf);
         __builtin_amdgcn_s_setprio(0);
     };
 
@@ -176,20 +154,20 @@ __global__ __launch_bounds__(512, 2) void gemm_wide_kernel(const dc_conv_desc d)
         constexpr int P = decltype(pc)::value;
         issue_stage(0, 0);
         if (nk > 1) issue_stage(1, 1);
-        if (nk > 1) wait_vm_lgkm<P>();
-        else wait_vm_lgkm<0>();                       // this wave's pieces of stage 0 have landed
-        if (grp == 1) wg_barrier();                   // the extra barrier that puts group 1 half a K-step behind group 0
+        if (nk > 1) dc_wait_vm_lgkm<P>();
+        else dc_wait_vm_lgkm<0>();                       // this wave's pieces of stage 0 have landed
+        if (grp == 1) dc_wg_barrier();                   // the extra barrier that puts group 1 half a K-step behind group 0
         for (int k = 0; k < nk; ++k) {
-            wg_barrier();                             // opens this group's L phase: every wave's pieces of stage k have landed
+            dc_wg_barrier();                             // opens this group's L phase: every wave's pieces of stage k have landed
             load_frags(k % NST);
             const bool more = k + 2 < nk;
             if (more) issue_stage(k + 2, (k + 2) % NST);
-            if (more) wait_vm_lgkm<P>();              // own pieces of stage k+1 landed (stage k+2 stays in flight), reads returned
-            else wait_vm_lgkm<0>();
-            wg_barrier();                             // opens this group's M phase (and the other group's L phase)
+            if (more) dc_wait_vm_lgkm<P>();              // own pieces of stage k+1 landed (stage k+2 stays in flight), reads returned
+            else dc_wait_vm_lgkm<0>();
+            dc_wg_barrier();                             // opens this group's M phase (and the other group's L phase)
             mfma_frags();
         }
-        if (grp == 0) wg_barrier();                   // pairs with group 1's last L-to-M barrier
+        if (grp == 0) dc_wg_barrier();                   // pairs with group 1's last L-to-M barrier
     };
     if (my_pieces == PMAX) pipeline(std::integral_constant<int, PMAX>{});
     else pipeline(std::integral_constant<int, PMAX - 1>{});

@@ -200,11 +200,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(const dc_conv_desc d)
                 const int row = (wm * TM + tm) * 16 + fr;
                 xf[tm] = *(const bf16x8*)(sA + qq * (BM * 16) + ((row ^ qq) << 4));
             }
-#pragma unroll
-            for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-                for (int tm = 0; tm < TM; ++tm)
-                    acc[tn][tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[tn], xf[tm], acc[tn][tm], 0, 0, 0);
+            dc_mfma_khalf(acc, wf, xf);
         }
     };
 
